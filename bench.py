@@ -9,7 +9,9 @@ N*1024 independent channels: no data-path collective, weak scaling.
 
 Launch: `python bench.py` (1 GPU) or
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W`.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line; `--full` adds everything
+else (cold start, load cost, copy / envelope diagnostics, the other workloads, CPU baselines).  `--dump-outputs DIR` writes
+what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -134,7 +136,7 @@ def build_workload(workload, args, world, rank, local_rank):
         dtype = "int16 (exact: int8-split MFMA, int32 accumulate)"
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         path = eng.path
         samples_per_step = (hi - lo) * n
     elif workload in ("rtest_const_types", "rtest_load_types", "rtest_prog_types"):
@@ -166,7 +168,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         path = eng.kernel
         samples_per_step = (hi - lo) * n
     elif workload == "cic_dec_r64":
@@ -190,7 +192,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         samples_per_step = (hi - lo) * n
         step()
         path = "cic_dec_" + eng.path
@@ -218,7 +220,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         samples_per_step = (hi - lo) * n
         step()
         path = ("cic_intr_" if interp else "cic_dec_") + eng.path
@@ -242,7 +244,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         samples_per_step = (hi - lo) * n
         path = "polydec"
     elif workload == "polyintr":
@@ -263,7 +265,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x)
+            return eng.run(x)
         samples_per_step = (hi - lo) * n
         step()
         path = "polyintr_" + eng.path
@@ -284,7 +286,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, n_sample)
+            return eng.run(x, n_sample)
         samples_per_step = (hi - lo) * n
         path = "intgdump"
     elif workload == "mvavg":
@@ -306,7 +308,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, 1024, out=y)
+            return eng.run(x, 1024, out=y)
         samples_per_step = (hi - lo) * n
         step()
         path = "mvavg_" + eng.path
@@ -330,7 +332,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         samples_per_step = (hi - lo) * n
         step()
         path = "cic_intr_" + eng.path
@@ -357,7 +359,7 @@ def build_workload(workload, args, world, rank, local_rank):
         dtype = "int64 (CIC wrap arithmetic, FIR exact dot product)"
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         path = "ddc_" + eng.path
         samples_per_step = (hi - lo) * n
         coeffs = None
@@ -377,7 +379,7 @@ def build_workload(workload, args, world, rank, local_rank):
         coeffs = None
 
         def step():
-            eng.run(x, y)
+            return eng.run(x, y)
         path = "cic_dec"
         samples_per_step = (hi - lo) * n
 
@@ -500,9 +502,10 @@ def run_inproc(args):
     for _ in range(args.warmup):
         step()
     per = []
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
         per.append(node.last_ms())
     dt = time.perf_counter() - t0
     kmax = sum(m for _, m in per) / len(per)                      # mean over the steps of the slowest shard's kernel time
@@ -520,6 +523,8 @@ def run_inproc(args):
                         "shards_per_device": shards_on_dev,
                         "kernel_ms_per_shard_last_step": per[-1][0]},
            "cpu_baseline": None}
+    if args.dump_outputs:
+        out["dump_outputs"] = dump_outputs(named_outputs(last), args.dump_outputs)
     print(json.dumps(out), flush=True)
 
 
@@ -540,10 +545,11 @@ def settle_clocks(step, seconds):
     return n
 
 
-def measure(w, steps, warmup, barrier, settle_s=0.0):
+def measure(w, steps, warmup, barrier, settle_s=0.0, probe_clock=False):
     """Optional clock pre-conditioning (settle_clocks), W untimed steps, then exactly `steps` timed steps bracketed by
     barrier + synchronize.  Returns wall seconds, the dominant kernel's (avg, min) duration from HIP events on the launch
-    stream, and the whole-step event time (ms)."""
+    stream, and the whole-step event time (ms).  w["last_out"]: what the last timed step returned (the output arrays a
+    caller of the step receives; --dump-outputs).  probe_clock (--full): time one spin kernel behind the steps."""
     step, eng = w["step"], w["eng"]
     w["settle_steps"] = settle_clocks(step, settle_s)
     for _ in range(warmup):
@@ -552,20 +558,23 @@ def measure(w, steps, warmup, barrier, settle_s=0.0):
     barrier()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(steps):
-        step()
+        last = step()
     ev1.record()
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
     ev_ms = ev0.elapsed_time(ev1) / steps
-    try:    # shader clock right behind the timed steps (a 40 us spin kernel, outside the timed region): the clock state the row ran in
-        import ac_dsp_amd as A
-        w["clock_mhz_after"] = round(A.diag_shader_clock_mhz(torch.cuda.current_device()), 1)
-    except Exception:   # noqa: BLE001  (a diagnostic: never fails a bench line)
-        w["clock_mhz_after"] = None
+    w["last_out"] = last
+    if probe_clock:
+        try:    # shader clock right behind the timed steps (a 40 us spin kernel, outside the timed region): the clock state the row ran in
+            import ac_dsp_amd as A
+            w["clock_mhz_after"] = round(A.diag_shader_clock_mhz(torch.cuda.current_device()), 1)
+        except Exception:   # noqa: BLE001  (a diagnostic: never fails a bench line)
+            w["clock_mhz_after"] = None
     if hasattr(eng, "kernel_stats"):
         k_avg, k_min = eng.kernel_stats(min(steps, 64))   # HIP events around the dominant kernel, on the stream it is launched on
     else:                                                # handles without a kernel timer: events around the whole step
@@ -575,6 +584,43 @@ def measure(w, steps, warmup, barrier, settle_s=0.0):
 
 PROFILE_TAGS = {w_: w_ for w_ in ("fir255", "fir255_dense", "fir255_wide", "fir1023", "cic_dec", "ddc", "polydec", "cic_intr", "polyintr", "intgdump", "mvavg",
                                    "rtest_const_types", "rtest_load_types", "rtest_prog_types", "cic_dec_r7m2n4", "cic_intr_r7m2n5", "cic_dec_r64")}
+
+
+DUMP_BYTES = 32 << 20      # --dump-outputs: bytes written per process at most (the last step's outputs, or a fixed sample of them)
+
+
+def dump_outputs(outs, dirname):
+    """--dump-outputs DIR: the arrays the last timed step returned, as DIR/<name>.npy -- float32 for containers of 16 bits and
+    narrower, float64 for wider ones (exact below 2^53).  An output larger than its share of DUMP_BYTES is written as a fixed,
+    seeded sample of whole rows (channels), kept in channel order; the sample depends only on the output's shape, so two builds
+    run with the same arguments write the same positions.  Returns {name: description} for the JSON line."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outs))
+    info = {}
+    for name, t in outs.items():
+        t = t.reshape(t.shape[0], -1) if t.dim() >= 2 else t.reshape(1, -1)
+        fdt = torch.float32 if t.element_size() <= 2 else torch.float64
+        rows, cols = t.shape
+        fsize = 4 if fdt == torch.float32 else 8
+        keep_rows, keep_cols = rows, cols
+        if rows * cols * fsize > share:
+            keep_rows = max(1, min(rows, share // max(1, cols * fsize)))
+            keep_cols = min(cols, share // (keep_rows * fsize))
+        idx = np.arange(rows) if keep_rows == rows else np.sort(np.random.default_rng(0xACD5).choice(rows, keep_rows, replace=False))
+        sel = t.index_select(0, torch.as_tensor(idx, device=t.device))[:, :keep_cols]
+        arr = sel.to(fdt).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        info[name] = {"shape": [rows, cols], "source_dtype": str(t.dtype).replace("torch.", ""), "written": list(arr.shape),
+                      "dtype": arr.dtype.name, "rows": "all" if keep_rows == rows else "seeded sample (numpy default_rng(0xACD5))",
+                      "cols": "all" if keep_cols == cols else "first %d" % keep_cols}
+    return info
+
+
+def named_outputs(last, suffix=""):
+    """The last step's return value as {name: tensor}: one output array, or one per shard (--inproc)."""
+    if isinstance(last, (list, tuple)):
+        return {"y_shard%d%s" % (i, suffix): t for i, t in enumerate(last)}
+    return {} if last is None else {"y" + suffix: last}
 
 
 def roofline_of(w, k_avg, k_min, ev_ms):
@@ -693,6 +739,11 @@ def main():
                     "(shader-clock ramp from idle; 0 = cold start, the K timed steps then include the DVFS transient)")
     ap.add_argument("--inproc", action="store_true", help="one process, one node-level handle (acdsp_node_*) with --gpus shards, instead "
                     "of one process per GPU")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the cold-start run and load cost, the shader-clock probe, the "
+                    "copy / envelope diagnostics, every other workload (`secondary`) and the CPU baselines.  Off: set up, warm up, time the "
+                    "--steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed step computed to DIR/<name>.npy "
+                    "(float32 / float64; a fixed seeded sample of rows when larger than %d MiB)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
 
     if args.inproc:
@@ -734,7 +785,7 @@ def main():
             dist.barrier()
 
     cold = None
-    if args.settle > 0 and world == 1:
+    if args.full and args.settle > 0 and world == 1:
         # the same W + K steps from an idle GPU first (what `--settle 0` prints as the headline): the DVFS transient of a cold start
         torch.cuda.synchronize()
         time.sleep(1.0)
@@ -742,7 +793,11 @@ def main():
         cold = {"ms_per_step": cdt / args.steps * 1e3, "value": w["samples_per_step"] * args.steps / cdt / 1e6, "kernel_ms_avg": ck,
                 "roofline_frac": w["bytes_per_sample"] * w["samples_per_step"] / (ck * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "note": "same W warm-up + K timed steps started 1 s after the GPU went idle, no pre-conditioning"}
-    dt, k_avg, k_min, ev_ms = measure(w, args.steps, args.warmup, barrier, args.settle)
+    dt, k_avg, k_min, ev_ms = measure(w, args.steps, args.warmup, barrier, args.settle, probe_clock=args.full)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(named_outputs(w.pop("last_out"), "_rank%d" % rank if world > 1 else ""), args.dump_outputs)
+    w.pop("last_out", None)
     samples_per_step = w["samples_per_step"]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64)
@@ -764,18 +819,21 @@ def main():
                        "parallelism": "channel-slice x%d, no collectives" % world},
             "roofline": roofline_of(w, k_avg, k_min, ev_ms),
             "event_ms_per_step": ev_ms,
-            "clock_mhz_after": w.get("clock_mhz_after"),
             "clock_settle": {"seconds": args.settle, "steps": w["settle_steps"],
                              "note": "untimed pre-conditioning in front of the W warm-up steps (same step, same data): the shader clock needs "
                                      "20-40 ms of load to settle from idle; --settle 0 measures the cold-start transient instead"},
         }
-        if world == 1:
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if args.full:
+            out["clock_mhz_after"] = w.get("clock_mhz_after")
+        if args.full and world == 1:
             diag_of(w, k_avg, out["roofline"])
         if w.get("placement"):
             out["config"]["placement"] = w["placement"]
         if cold is not None:
             out["cold_start"] = cold
-        if world == 1 and args.workload == "fir255" and not args.no_secondary:
+        if args.full and world == 1 and args.workload == "fir255" and not args.no_secondary:
             # what a fresh process pays before its first output (one code object with every kernel): tools/load_cost.py as a child process
             try:
                 import subprocess
@@ -787,7 +845,7 @@ def main():
             out["mfma_roofline"] = mfma_roofline_of(w, k_avg)
         fin, fc, fa, fo = w["fmts"]
         cpu_args = (w["n_taps"], w["coeffs"], fin, fc, fa, fo, w["seed"])
-        if world == 1 and not args.no_secondary and args.workload == "fir255" and not (args.channels or args.samples or args.stim_bits):
+        if args.full and world == 1 and not args.no_secondary and args.workload == "fir255" and not (args.channels or args.samples or args.stim_bits):
             # every other workload in the same process, 10 timed steps each behind 5 warm-up steps (one resident workload at a
             # time: config 3 alone holds 86 GB); measured BEFORE the CPU baseline, whose 10 s leave the GPU idle and in a low
             # power state (the first workload behind it measured 15 % slow)
@@ -796,7 +854,8 @@ def main():
             sec = {}
             for name in SECONDARY:
                 w2 = build_workload(name, args, 1, 0, local_rank)
-                dt2, ka2, km2, ev2 = measure(w2, 10, 5, lambda: None, args.settle)
+                dt2, ka2, km2, ev2 = measure(w2, 10, 5, lambda: None, args.settle, probe_clock=True)
+                w2.pop("last_out", None)
                 r2 = roofline_of(w2, ka2, km2, ev2)
                 sec[name] = {"workload": w2["name"], "kernel_path": w2["path"], "ms_per_step": dt2 / 10 * 1e3,
                              "Msamples_per_s": w2["samples_per_step"] * 10 / dt2 / 1e6, "kernel_ms_avg": ka2,
@@ -818,15 +877,15 @@ def main():
                 del w2
                 torch.cuda.empty_cache()
             out["secondary"] = sec
-        if world == 1 and not args.no_cpu_baseline and cpu_args[1] is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and cpu_args[1] is not None:
             out["cpu_baseline"] = cpu_baseline_fir(*cpu_args)
             if args.workload in ("fir255", "fir255_dense"):
                 ref = cpu_baseline_ref_headers()
                 if ref is not None:
                     out["cpu_baseline_ref_headers"] = ref
-        elif world == 1 and not args.no_cpu_baseline and args.workload == "cic_dec":
+        elif args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cic_dec":
             out["cpu_baseline"] = cpu_baseline_cic(fin, fo, cpu_args[6])
-        if world == 1 and not args.no_cpu_baseline and args.workload == "fir255":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "fir255":
             out["cfg1_cpu"] = cpu_cfg1()
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -855,12 +914,12 @@ def self_launch(n):
 
 def cpu_baseline_ref_headers():
     """The reference's own header-only loop (ac_fir_load_coeffs::run -> firShiftReg + MAC, /root/reference/include/ac_dsp/
-    ac_fir_load_coeffs.h:180-188,320-365) timed on this node's host cores: tests/_bin/cref_bench is prebuilt by
-    __graft_entry__.build() in the build container from tools/gen_golden/cref_bench.cpp (the reference's headers compiled where they
+    ac_fir_load_coeffs.h:180-188,320-365) timed on this node's host cores: oracle/_ref/cref_bench is prebuilt by
+    __graft_entry__.build() on a build host (oracle/Makefile `ref`) from tools/gen_golden/cref_bench.cpp (the reference's headers compiled where they
     lie over this repo's include/ac_types subset -- hlslibs/ac_types is not in the image, so this times the reference's loop
     structure and ac_channel traffic, not Siemens' ac_int arithmetic).  Only the binary travels.  None when it is missing."""
     import subprocess
-    exe = os.path.join(ROOT, "tests", "_bin", "cref_bench")
+    exe = os.path.join(ROOT, "oracle", "_ref", "cref_bench")
     if not os.path.isfile(exe):
         return None
     cores = host_cores()
@@ -907,7 +966,7 @@ def cpu_cfg1():
                               "sample": "%d calls of 64 x the 1024-sample record (fresh filter object each), %.1f s wall" % (reps, dt)}
     except (OSError, KeyError, IndexError, ValueError) as e:
         out["oracle_port"] = {"error": repr(e)}
-    exe = os.path.join(ROOT, "tests", "_bin", "cref_bench")
+    exe = os.path.join(ROOT, "oracle", "_ref", "cref_bench")
     if os.path.isfile(exe):
         try:
             txt = subprocess.run([exe, "1", str(1 << 21), "cfg1"], capture_output=True, text=True, timeout=120).stdout

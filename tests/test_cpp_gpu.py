@@ -2,8 +2,8 @@
 
 tb_*.cpp are this repo's own testbenches (same stimulus, vectors and pass criteria as the reference's
 tests/rtest_*.cpp).  rtest_* are the reference's testbenches themselves, compiled UNCHANGED against our
-headers by __graft_entry__.build() in the build container (binaries only travel; the reference sources
-never enter the repo); they are run when present."""
+headers into oracle/_ref/ by __graft_entry__.build() on a build host (oracle/Makefile `ref`; binaries
+only travel; the reference sources never enter the repo); they are run when present."""
 import os
 import re
 import subprocess
@@ -33,9 +33,10 @@ def kernel_runs(out):
 
 
 TBS = ("tb_tiny", "tb_fir", "tb_cic", "tb_batched", "tb_polydec", "tb_reg_share", "tb_poly_intr", "tb_intg_dump", "tb_mv_avg", "tb_wide", "tb_node")
-# tests/_bin arrived prebuilt (the snapshot of a build container that ran __graft_entry__.build()): then the reference's rtest_*
-# binaries must have arrived with it -- a lost binary is a failure there, not a skip
-PREBUILT = all(os.path.exists(os.path.join(BIN, t)) for t in TBS)
+# oracle/_ref/ exists once __graft_entry__.build() ran with the reference checkout present (a build host; the directory travels
+# with the tree): then every rtest_* binary must be in it -- a lost binary is a failure there, not a skip
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
+PREBUILT = os.path.isdir(REF_BIN)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -61,10 +62,10 @@ HOST_LEGS = [pytest.param(None, id="default"), pytest.param("0", id="host_small_
 @pytest.mark.parametrize("name", ["ac_fir_const_coeffs", "ac_fir_load_coeffs", "ac_fir_prog_coeffs", "ac_cic_dec_full",
                                   "ac_cic_intr_full"])
 def test_reference_rtest_binary_unchanged(name, small_macs):
-    exe = os.path.join(BIN, "rtest_" + name)
+    exe = os.path.join(REF_BIN, "rtest_" + name)
     if not os.path.exists(exe):
-        assert not PREBUILT, "tests/_bin holds prebuilt testbenches but %s is missing: __graft_entry__.build() did not run with /root/reference" % exe
-        pytest.skip("rtest binary not prebuilt (needs /root/reference at build time)")
+        assert not PREBUILT, "oracle/_ref holds reference-testbench builds but %s is missing: rerun __graft_entry__.build() with the reference checkout" % exe
+        pytest.skip("rtest binary not prebuilt (oracle/_ref is built only where the reference checkout is present)")
     env = {"ACDSP_TRACE": "1"}
     if small_macs is not None:
         env["ACDSP_HOST_SMALL_MACS"] = small_macs
