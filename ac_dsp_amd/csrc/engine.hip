@@ -1,7 +1,7 @@
 // engine.hip -- the C ABI of libacdsp.so (declared in include/acdsp.h): what every operator family shares -- error state, device check,
 // device memory helpers, the stimulus generator, the diagnostics of bench.py -- plus the state blobs and the stream files.
 // The families live in engine_fir.hip, engine_cic.hip, engine_ddc.hip, engine_poly.hip (poly_dec, poly_intr) and engine_misc.hip
-// (intg_dump, mv_avg); engine_common.hpp holds the handle structs and helpers they share.
+// (intg_dump, mv_avg); engine_common.hpp holds the handle structs and the building blocks they are made of.
 #include "engine_common.hpp"
 
 using namespace acdsp;
@@ -430,6 +430,15 @@ bool state_compatible(const StateHdr &blob, const StateHdr &mine) {
          blob.p2 == mine.p2 && blob.p3 == mine.p3;
 }
 
+// device image of an input-history blob `s` (payload `src`) of another history length than the handle's (`mine`): the newest
+// min(blob, mine) samples of every channel are kept, older ones zero
+std::vector<unsigned char> relen_image(const StateHdr &s, const StateHdr &mine, const unsigned char *src) {
+  const size_t eb = mine.elem_bytes, pm = (size_t)mine.per_channel, pb = (size_t)s.per_channel, keep = pm < pb ? pm : pb;
+  std::vector<unsigned char> img((size_t)mine.n_channels * pm * eb, 0);
+  for (size_t c = 0; c < mine.n_channels; c++) { memcpy(&img[(c * pm + (pm - keep)) * eb], src + (c * pb + (pb - keep)) * eb, keep * eb); }
+  return img;
+}
+
 }  // namespace
 
 extern "C" {
@@ -446,7 +455,7 @@ int32_t acdsp_fir_state_get(acdsp_fir_t h, void *buf, uint64_t cap_bytes) {
   HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous: the state of the last call must have landed
   if (h->rt_hybrid && !h->rt_valid && (rc = fir_rt_from_hist(h))) { return rc; }
   memcpy(buf, &s, sizeof s);
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->use_rt ? (const void *)h->d_rt[h->rt_hybrid ? h->cur_rt : h->cur] : h->d_hist[h->cur], pay, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->use_rt ? (const void *)fir_rt_cur(h) : h->hist.cur(), pay, hipMemcpyDeviceToHost));
   return ACDSP_OK;
 }
 
@@ -470,16 +479,13 @@ int32_t acdsp_fir_state_set(acdsp_fir_t h, const void *buf, uint64_t bytes) {
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
   if (relen) {
-    const size_t eb = mine.elem_bytes, pm = (size_t)mine.per_channel, pb = (size_t)s.per_channel, keep = pm < pb ? pm : pb;
-    std::vector<unsigned char> img((size_t)mine.n_channels * pm * eb, 0);
-    const unsigned char *src = (const unsigned char *)buf + sizeof s;
-    for (size_t c = 0; c < mine.n_channels; c++) { memcpy(&img[(c * pm + (pm - keep)) * eb], src + (c * pb + (pb - keep)) * eb, keep * eb); }
-    HIP_TRY(hipMemcpy(h->d_hist[h->cur], img.data(), img.size(), hipMemcpyHostToDevice));
+    const std::vector<unsigned char> img = relen_image(s, mine, (const unsigned char *)buf + sizeof s);
+    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
     return ACDSP_OK;
   }
-  HIP_TRY(hipMemcpy(h->use_rt ? (void *)h->d_rt[h->rt_hybrid ? h->cur_rt : h->cur] : h->d_hist[h->cur], (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->use_rt ? (void *)fir_rt_cur(h) : h->hist.cur(), (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
   if (h->rt_hybrid) {   // partial sums of unknown coefficients and samples: the next n_taps - 1 outputs come from them, the history starts empty
-    HIP_TRY(hipMemset(h->d_hist[h->cur], 0, (size_t)h->d.n_channels * h->hl * h->in_eb));
+    HIP_TRY(hipMemset(h->hist.cur(), 0, h->hist.bytes()));
     h->rt_valid = true; h->rt_since = 0;
   }
   return ACDSP_OK;
@@ -496,7 +502,7 @@ int32_t acdsp_cic_state_get(acdsp_cic_t h, void *buf, uint64_t cap_bytes) {
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
   memcpy(buf, &s, sizeof s);
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->d_hist[h->cur], pay, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
   return ACDSP_OK;
 }
 
@@ -522,13 +528,10 @@ int32_t acdsp_cic_state_set(acdsp_cic_t h, const void *buf, uint64_t bytes) {
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
   if (relen) {
-    const size_t eb = mine.elem_bytes, pm = (size_t)mine.per_channel, pb = (size_t)s.per_channel, keep = pm < pb ? pm : pb;
-    std::vector<unsigned char> img((size_t)mine.n_channels * pm * eb, 0);
-    const unsigned char *src = (const unsigned char *)buf + sizeof s;
-    for (size_t c = 0; c < mine.n_channels; c++) { memcpy(&img[(c * pm + (pm - keep)) * eb], src + (c * pb + (pb - keep)) * eb, keep * eb); }
-    HIP_TRY(hipMemcpy(h->d_hist[h->cur], img.data(), img.size(), hipMemcpyHostToDevice));
+    const std::vector<unsigned char> img = relen_image(s, mine, (const unsigned char *)buf + sizeof s);
+    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
   } else {
-    HIP_TRY(hipMemcpy(h->d_hist[h->cur], (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->hist.cur(), (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
   }
   h->t_total = s.t_total;
   return ACDSP_OK;
@@ -565,7 +568,7 @@ int32_t acdsp_ddc_state_get(acdsp_ddc_t h, void *buf, uint64_t cap_bytes) {
   memcpy(buf, &s, sizeof s);
   if (h->fused) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->d_hist[h->cur], pay, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
     return ACDSP_OK;
   }
   const uint64_t nc = (uint64_t)acdsp_cic_state_size(h->cic);
@@ -586,7 +589,7 @@ int32_t acdsp_ddc_state_set(acdsp_ddc_t h, const void *buf, uint64_t bytes) {
   if (rc) { return rc; }
   if (h->fused) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h->d_hist[h->cur], (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->hist.cur(), (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
     h->t_total = s.t_total;
     return ACDSP_OK;
   }

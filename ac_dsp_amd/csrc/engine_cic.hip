@@ -60,7 +60,7 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   if (desc->n_channels < 1) { return fail(ACDSP_EINVAL, "CIC: n_channels=%d must be positive", desc->n_channels); }
   if (desc->n_channels > 65535) { return fail(ACDSP_EUNSUPPORTED, "CIC: n_channels=%d outside 1..65535", desc->n_channels); }
   if ((rc = check_device(desc->device))) { return rc; }
-  acdsp_cic *h = new acdsp_cic();
+  std::unique_ptr<acdsp_cic> h(new acdsp_cic());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   h->it = it;
   h->in_eb = elem_bytes(desc->in.W);
@@ -70,34 +70,26 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   const int64_t mem = desc->interp ? (int64_t)desc->N * h->me + 1 : (int64_t)desc->N * desc->R * h->me - 1;
   h->hl = round_up((int)(mem > 1 ? mem : 1) + 16, kCicTile);   // + 16: the 16-aligned input windows of fir_gen
   h->warm = h->hl;
+  // FIR identity of both directions: h = z^-(N-1) * boxcar(R*M')^N, all arithmetic mod 2^64 (then mod 2^outW)
+  cic2_stage1_taps(desc->R * h->me, desc->N, &h->h_taps);
+  static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
+  FirGenPlan probe;
+  std::vector<uint32_t> fr;
+  // decimator on the matrix cores through that identity (fir_gen.hip): where the taps have a plan at both ends of the window offsets
+  h->gen_ok = !desc->interp && !h->wide && !no_gen && fits_container(desc->in, h->in_eb) &&
+              fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 15, &probe, &fr) &&   // worst-case window offset
+              fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 0, &probe, &fr);
   {
     // two-stage decimator (cic2.hip) where R = R1 R2 with a compiled stage-1 rate: its chunk 0 starts `wu` steps of 256 R1 inputs early,
     // so the handle keeps that much input history (the samples beyond the filter memory only ever feed warm-up values the combs cancel)
     // (below R = 32 the one-stage FIR identity serves the rates it has a plan for; where it has none -- R M N too many taps, e.g. R 24 M 2 N 4 -- the
     // two-stage kernel takes over there as well instead of the recurrence kernel)
-    bool one_stage = false;
-    if (!desc->interp && !h->wide && desc->R < 32 && (desc->in.W + (desc->in.S ? 0 : 1) + 7) / 8 <= h->in_eb && getenv("ACDSP_NO_GEN") == nullptr) {
-      const int L = desc->R * h->me;
-      std::vector<uint64_t> c(1, 1);
-      for (int st = 0; st < desc->N; st++) {
-        std::vector<uint64_t> nx(c.size() + L - 1, 0);
-        for (size_t i = 0; i < c.size(); i++) { for (int j = 0; j < L; j++) { nx[i + j] += c[i]; } }
-        c.swap(nx);
-      }
-      std::vector<int64_t> t((size_t)desc->N - 1, 0);
-      for (uint64_t v : c) { t.push_back((int64_t)v); }
-      FirGenPlan probe;
-      std::vector<uint32_t> fr;
-      one_stage = fir_gen_plan(t.data(), (int)t.size(), desc->R, 15, &probe, &fr) && fir_gen_plan(t.data(), (int)t.size(), desc->R, 0, &probe, &fr);
-    }
+    const bool one_stage = h->gen_ok && desc->R < 32;
     static const bool no_c2 = getenv("ACDSP_NO_CIC2") != nullptr;         // A/B knob: recurrence kernel as before
     static const bool c2_all = getenv("ACDSP_CIC2_ALL") != nullptr;       // A/B knob: also where the one-stage FIR identity fits (R < 32)
-    const int in_bits = desc->in.W + (desc->in.S ? 0 : 1);
-    if (!desc->interp && !h->wide && !no_c2 && (desc->R >= 32 || c2_all || !one_stage) && (in_bits + 7) / 8 <= h->in_eb && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) &&
+    if (!desc->interp && !h->wide && !no_c2 && (desc->R >= 32 || c2_all || !one_stage) && fits_container(desc->in, h->in_eb) && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) &&
         cic2_factor(h->in_eb, desc->R, h->me, desc->N, &h->c2_R1, &h->c2_R2, &h->c2_wu)) {
       cic2_stage1_taps(h->c2_R1, desc->N, &h->c2_taps);
-      FirGenPlan probe;
-      std::vector<uint32_t> fr;
       h->c2_ok = fir_gen_plan(h->c2_taps.data(), (int)h->c2_taps.size(), h->c2_R1, 15, &probe, &fr) &&
                  fir_gen_plan(h->c2_taps.data(), (int)h->c2_taps.size(), h->c2_R1, 0, &probe, &fr);
       if (h->c2_ok) {
@@ -106,58 +98,27 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
       }
     }
   }
-  const size_t hb = (size_t)desc->n_channels * h->hl * h->in_eb;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = hipMalloc(&h->d_hist[i], hb);
-    if (e == hipSuccess) { e = hipMemset(h->d_hist[i], 0, hb); }
-  }
-  {
-    // FIR identity of both directions: h = z^-(N-1) * boxcar(R*M')^N, all arithmetic mod 2^64 (then mod 2^outW)
-    const int L = desc->R * h->me;
-    std::vector<uint64_t> c(1, 1);
-    for (int st = 0; st < desc->N; st++) {
-      std::vector<uint64_t> nx(c.size() + L - 1, 0);
-      for (size_t i = 0; i < c.size(); i++) { for (int j = 0; j < L; j++) { nx[i + j] += c[i]; } }
-      c.swap(nx);
-    }
-    h->h_taps.assign((size_t)desc->N - 1, 0);
-    for (uint64_t v : c) { h->h_taps.push_back((int64_t)v); }
-    FirGenPlan probe;
-    std::vector<uint32_t> fr;
-    static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
-    if (e == hipSuccess && ((desc->interp && !no_gen) || h->wide)) {   // interpolator (and wide.hip): polyphase FIR kernel reads the taps themselves
-      e = hipMalloc((void **)&h->d_taps, h->h_taps.size() * sizeof(int64_t));
-      if (e == hipSuccess) { e = hipMemcpy(h->d_taps, h->h_taps.data(), h->h_taps.size() * sizeof(int64_t), hipMemcpyHostToDevice); }
-      // ... and, where the shape is compiled in, the same identity phase by phase on the matrix cores
-      const int R = desc->R, n_taps = (int)h->h_taps.size(), kmax = (n_taps + R - 1) / R;
-      const int px = (desc->in.W + (desc->in.S ? 0 : 1) + 7) / 8;
-      if (e == hipSuccess && desc->interp && !h->wide && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) && ((px <= 2 && h->in_eb == 2) || (px <= 4 && h->in_eb == 4)) && R <= 32) {
-        std::vector<int64_t> E((size_t)R * kmax, 0);
-        for (int r = 0; r < R; r++) { for (int k = 0; k < kmax; k++) { if (r + R * k < n_taps) { E[(size_t)r * kmax + k] = h->h_taps[(size_t)(r + R * k)]; } } }
-        std::vector<uint32_t> frag;
-        std::vector<int64_t> ucorr;
-        FirUpPlan pl;
-        if (fir_up_plan(E.data(), R, kmax, h->in_eb, &pl, &frag, &ucorr) && pl.pc <= 3 && pl.nb == 1 && fir_up_shape_ok(h->in_eb, h->in_eb, pl.nb, R, h->out_eb)) {
-          e = hipMalloc((void **)&h->d_upfrag, frag.size() * sizeof(uint32_t));
-          if (e == hipSuccess) { e = hipMalloc((void **)&h->d_upcorr, ucorr.size() * sizeof(int64_t)); }
-          if (e == hipSuccess) { e = hipMemcpy(h->d_upfrag, frag.data(), frag.size() * sizeof(uint32_t), hipMemcpyHostToDevice); }
-          if (e == hipSuccess) { e = hipMemcpy(h->d_upcorr, ucorr.data(), ucorr.size() * sizeof(int64_t), hipMemcpyHostToDevice); }
-          h->up_plan = pl; h->up_px = h->in_eb; h->up_ok = e == hipSuccess;
-        }
+  if ((rc = h->hist.init(desc->n_channels, h->hl, h->in_eb))) { return rc; }
+  if ((desc->interp && !no_gen) || h->wide) {   // interpolator (and wide.hip): polyphase FIR kernel reads the taps themselves
+    if ((rc = h->d_taps.alloc_upload(h->h_taps))) { return rc; }
+    // ... and, where the shape is compiled in, the same identity phase by phase on the matrix cores
+    const int R = desc->R, n_taps = (int)h->h_taps.size(), kmax = (n_taps + R - 1) / R;
+    if (desc->interp && !h->wide && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) && fits_container(desc->in, h->in_eb) && (h->in_eb == 2 || h->in_eb == 4) && R <= 32) {
+      std::vector<int64_t> E((size_t)R * kmax, 0);
+      for (int r = 0; r < R; r++) { for (int k = 0; k < kmax; k++) { if (r + R * k < n_taps) { E[(size_t)r * kmax + k] = h->h_taps[(size_t)(r + R * k)]; } } }
+      std::vector<uint32_t> frag;
+      std::vector<int64_t> ucorr;
+      FirUpPlan pl;
+      if (fir_up_plan(E.data(), R, kmax, h->in_eb, &pl, &frag, &ucorr) && pl.pc <= 3 && pl.nb == 1 && fir_up_shape_ok(h->in_eb, h->in_eb, pl.nb, R, h->out_eb)) {
+        if ((rc = h->d_upfrag.alloc_upload(frag)) || (rc = h->d_upcorr.alloc_upload(ucorr))) { return rc; }
+        h->up_plan = pl; h->up_px = h->in_eb; h->up_ok = true;
       }
     }
-    h->gen_ok = e == hipSuccess && !desc->interp && !h->wide && !no_gen && (desc->in.W + (desc->in.S ? 0 : 1) + 7) / 8 <= h->in_eb &&
-                fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 15, &probe, &fr) &&   // worst-case window offset
-                fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 0, &probe, &fr);
-    if (h->gen_ok) { e = hipMalloc((void **)&h->d_gfrag, (size_t)16 * 3 * 8 * 64 * 4 * sizeof(uint32_t)); }
-    if (h->c2_ok && e == hipSuccess) { e = hipMalloc((void **)&h->d_c2frag, (size_t)16 * 3 * 8 * 64 * 4 * sizeof(uint32_t)); }
   }
-  if (e != hipSuccess || h->tm.init() != ACDSP_OK) {
-    acdsp_cic_destroy(h);
-    return fail(ACDSP_EHIP, "CIC state allocation failed: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  if (h->gen_ok && (rc = h->gen.init())) { return rc; }
+  if (h->c2_ok && (rc = h->c2.init())) { return rc; }
+  if ((rc = h->tm.init())) { return rc; }
+  *out = h.release();
   if (trace_handles()) { fprintf(stderr, "[acdsp] cic_create interp=%d R=%d M=%d N=%d n_channels=%d\n", desc->interp, desc->R, desc->M, desc->N, desc->n_channels); }
   return ACDSP_OK;
 }
@@ -166,16 +127,6 @@ int32_t acdsp_cic_destroy(acdsp_cic_t h) {
   if (!h) { return ACDSP_OK; }
   if (trace_handles()) { fprintf(stderr, "[acdsp] cic_destroy kernel_runs=%lld\n", (long long)h->tm.count); }
   (void)hipSetDevice(h->d.device);
-  if (h->d_gfrag) { (void)hipFree(h->d_gfrag); }
-  if (h->d_c2frag) { (void)hipFree(h->d_c2frag); }
-  if (h->d_taps) { (void)hipFree(h->d_taps); }
-  if (h->d_upfrag) { (void)hipFree(h->d_upfrag); }
-  if (h->d_upcorr) { (void)hipFree(h->d_upcorr); }
-  for (int i = 0; i < 2; i++) {
-    if (h->d_hist[i]) { (void)hipFree(h->d_hist[i]); }
-  }
-  h->tm.destroy();
-  h->st.destroy();
   delete h;
   return ACDSP_OK;
 }
@@ -186,8 +137,7 @@ int32_t acdsp_cic_clone(acdsp_cic_t h, acdsp_cic_t *out) {
   int rc = acdsp_cic_create(&h->d, &c);
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(c->d_hist[0], h->d_hist[h->cur], (size_t)h->d.n_channels * h->hl * h->in_eb, hipMemcpyDeviceToDevice));
-  c->cur = 0;
+  if ((rc = c->hist.copy_from(h->hist))) { return rc; }
   c->t_total = h->t_total;
   *out = c;
   return ACDSP_OK;
@@ -200,7 +150,7 @@ int32_t acdsp_cic_reset(acdsp_cic_t h) {
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < 2; i++) { HIP_TRY(hipMemset(h->d_hist[i], 0, (size_t)h->d.n_channels * h->hl * h->in_eb)); }
+  if ((rc = h->hist.zero())) { return rc; }
   h->t_total = 0;
   return ACDSP_OK;
 }
@@ -267,7 +217,7 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   p.vec_ok = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0);
   p.out_simple = (p.out.F == p.in.F && p.out.O == ACDSP_WRAP) ? ((p.out.S && p.out.W >= h->it.W) ? 2 : 1) : 0;
   p.in_stride = in_stride; p.out_stride = out_stride; p.n_in = n_in;
-  p.x = d_in; p.y = d_out; p.hist = h->d_hist[h->cur];
+  p.x = d_in; p.y = d_out; p.hist = h->hist.cur();
   // chunking: aim at >= 4096 waves, keep the warm-up below ~6 % of a chunk
   const int64_t groups = (d.n_channels + 63) / 64;
   int64_t chunk = (n_in * groups + 4095) / 4096;
@@ -276,45 +226,26 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   p.chunk = (chunk + kCicTile - 1) / kCicTile * kCicTile;
   // decimator on the matrix cores when the FIR identity fits and the rows are slot-aligned
   bool use_gen = h->gen_ok && !d.interp && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
-  const uint32_t *gfrag = nullptr;
-  FirGenPlan gpl;
+  const uint32_t *gfrag = nullptr, *c2frag = nullptr;
+  const FirGenPlan *gpl = nullptr, *c2pl = nullptr;
   if (use_gen) {
-    const int fm = (int)(p.first % 16);
-    if (!h->gen_have[fm]) {
-      std::vector<uint32_t> fr;
-      if (!fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), d.R, fm, &h->gen_plan[fm], &fr)) { use_gen = false; }
-      else {
-        HIP_TRY(hipMemcpyAsync(h->d_gfrag + (size_t)fm * 3 * 8 * 64 * 4, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));   // fr is a stack vector
-        h->gen_have[fm] = true;
-      }
-    }
-    if (use_gen) { gfrag = h->d_gfrag + (size_t)fm * 3 * 8 * 64 * 4; gpl = h->gen_plan[fm]; }
+    if ((rc = h->gen.get(h->h_taps, d.R, (int)(p.first % 16), s, &gpl, &gfrag))) { return rc; }
+    use_gen = gpl != nullptr;
   }
   // ... or in two stages (R = R1 R2, cic2.hip) where the one-stage window does not fit: complete chunks there, the ragged end on the recurrence kernel
   bool use_c2 = h->c2_ok && !use_gen && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
-  const uint32_t *c2frag = nullptr;
   if (use_c2) {
-    const int fm = (int)(p.first % 16);
-    if (!h->c2_have[fm]) {
-      std::vector<uint32_t> fr;
-      if (!fir_gen_plan(h->c2_taps.data(), (int)h->c2_taps.size(), h->c2_R1, fm, &h->c2_plan[fm], &fr)) { use_c2 = false; }
-      else {
-        HIP_TRY(hipMemcpyAsync(h->d_c2frag + (size_t)fm * 3 * 8 * 64 * 4, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));   // fr is a stack vector
-        h->c2_have[fm] = true;
-      }
-    }
-    if (use_c2) { c2frag = h->d_c2frag + (size_t)fm * 3 * 8 * 64 * 4; }
+    if ((rc = h->c2.get(h->c2_taps, h->c2_R1, (int)(p.first % 16), s, &c2pl, &c2frag))) { return rc; }
+    use_c2 = c2pl != nullptr;
   }
-  const bool use_intr_fir = d.interp && h->d_taps != nullptr && !h->wide;
+  const bool use_intr_fir = d.interp && h->d_taps && !h->wide;
   h->last_path = h->wide ? ACDSP_PATH_WIDE : (use_gen ? ACDSP_PATH_MFMA_GEN : (use_intr_fir ? ACDSP_PATH_LOSSLESS64 : 0));
   HIP_TRY(hipEventRecord(h->tm.start(), s));
   hipError_t e;
   if (h->wide) {
     CicWideParams pw;
     pw.p = p; pw.out = make_wfmt(d.out);
-    e = launch_cic_wide(pw, h->d_taps, (int)h->h_taps.size(), no, s);
+    e = launch_cic_wide(pw, h->d_taps.get<int64_t>(), (int)h->h_taps.size(), no, s);
   } else if (use_gen) {
     FirParams k;
     memset(&k, 0, sizeof k);
@@ -322,8 +253,8 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
     k.in = p.in; k.out = p.out; k.acc = p.out; k.cf = p.in;
     k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl;
     k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in;
-    k.x = d_in; k.y = d_out; k.hist = h->d_hist[h->cur];
-    e = launch_fir_gen(k, gpl, gfrag, 1, h->it.W, p.first, no, s);
+    k.x = d_in; k.y = d_out; k.hist = h->hist.cur();
+    e = launch_fir_gen(k, *gpl, gfrag, 1, h->it.W, p.first, no, s);
   } else if (use_intr_fir) {
     // whole steps of 32 input slots on the matrix cores; the head (history, earlier-call phase) and the tail (the call's
     // last input emits only its first iteration, ac_cic_intr_full.h:200-205) on the polyphase VALU kernel
@@ -343,7 +274,7 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
         memset(&k, 0, sizeof k);
         k.n_ch = d.n_channels; k.in = p.in; k.out = p.out; k.acc = p.out; k.cf = p.in;
         k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in; k.x = d_in; k.y = d_out;
-        e = launch_fir_up(k, h->up_plan, h->up_px, h->d_upfrag, h->d_upcorr, 1, h->it.W, p.out_simple, 0, -1, slot_a, n_steps, out_off, s);
+        e = launch_fir_up(k, h->up_plan, h->up_px, h->d_upfrag.get<uint32_t>(), h->d_upcorr.get<int64_t>(), 1, h->it.W, p.out_simple, 0, -1, slot_a, n_steps, out_off, s);
         if (e == hipSuccess) {
           q_a = (int64_t)d.R * (p.t_prev + 16 * slot_a); q_b = (int64_t)d.R * (p.t_prev + 16 * (slot_a + 32 * n_steps));
           h->last_path = ACDSP_PATH_MFMA_GEN;
@@ -354,16 +285,16 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
     }
     if (q_b > q_a) {
       e = hipSuccess;
-      if (q_a > lo) { p.q_from = lo; p.q_to = q_a; e = launch_cic_intr_fir(p, h->d_taps, (int)h->h_taps.size(), s); }
-      if (e == hipSuccess && p.q_end > q_b) { p.q_from = q_b; p.q_to = p.q_end; e = launch_cic_intr_fir(p, h->d_taps, (int)h->h_taps.size(), s); }
+      if (q_a > lo) { p.q_from = lo; p.q_to = q_a; e = launch_cic_intr_fir(p, h->d_taps.get<int64_t>(), (int)h->h_taps.size(), s); }
+      if (e == hipSuccess && p.q_end > q_b) { p.q_from = q_b; p.q_to = p.q_end; e = launch_cic_intr_fir(p, h->d_taps.get<int64_t>(), (int)h->h_taps.size(), s); }
       p.q_from = p.q_to = 0;
     } else {
-      e = launch_cic_intr_fir(p, h->d_taps, (int)h->h_taps.size(), s);
+      e = launch_cic_intr_fir(p, h->d_taps.get<int64_t>(), (int)h->h_taps.size(), s);
     }
   } else {
     int64_t covered = 0;
     e = hipSuccess;
-    if (use_c2) { e = launch_cic2(p, h->c2_plan[p.first % 16], c2frag, h->c2_R1, h->c2_R2, h->c2_wu, no, s, &covered); }
+    if (use_c2) { e = launch_cic2(p, *c2pl, c2frag, h->c2_R1, h->c2_R2, h->c2_wu, no, s, &covered); }
     if (e == hipSuccess && covered < no) {
       if (covered > 0) {            // the ragged end of the call: outputs from `covered` on, i.e. emitting samples from first + covered R on
         p.emit_from = p.first + covered * d.R;
@@ -378,10 +309,10 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "CIC kernel launch failed: %s", hipGetErrorString(e)); }
   HIP_TRY(hipEventRecord(h->tm.stop(), s));
   h->tm.commit();
-  const int nxt = hist_next_index(h->cur, p.n_in >= p.hl);
-  e = launch_cic_hist_update(p, h->d_hist[nxt], s);
+  const int nxt = h->hist.next(p.n_in >= p.hl);
+  e = launch_cic_hist_update(p, h->hist.at(nxt), s);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "CIC state kernel launch failed: %s", hipGetErrorString(e)); }
-  h->cur = nxt;
+  h->hist.commit(nxt);
   h->t_total += n_in;
   return ACDSP_OK;
 }
@@ -395,32 +326,8 @@ int32_t acdsp_cic_run_host(acdsp_cic_t h, const void *h_in, int64_t n_in, void *
   if (no > out_cap || (no > 0 && !h_out)) { return fail(ACDSP_EINVAL, "cic_run_host: output capacity %lld < %lld", (long long)out_cap, (long long)no); }
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
-  const int64_t si = (n_in + 15) / 16 * 16, so = (no + 7) / 8 * 8 + 8;
-  static const bool no_pin = getenv("ACDSP_NO_PINNED") != nullptr;
-  if ((size_t)h->d.n_channels * si * h->in_eb <= Staging::kPinBytes && (size_t)h->d.n_channels * so * h->out_eb <= Staging::kPinBytes && !no_pin) {
-    if ((rc = h->st.ensure_pinned())) { return rc; }
-    for (int c = 0; c < h->d.n_channels; c++) {
-      memcpy((char *)h->st.pin_in + (size_t)c * si * h->in_eb, (const char *)h_in + (size_t)c * n_in * h->in_eb, (size_t)n_in * h->in_eb);
-    }
-    int64_t got = 0;
-    if ((rc = acdsp_cic_run(h, h->st.pin_in, si, n_in, h->st.pin_out, so, &got, nullptr))) { return rc; }
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    for (int c = 0; c < h->d.n_channels && no > 0; c++) {
-      memcpy((char *)h_out + (size_t)c * no * h->out_eb, (const char *)h->st.pin_out + (size_t)c * so * h->out_eb, (size_t)no * h->out_eb);
-    }
-    return ACDSP_OK;
-  }
-  if ((rc = h->st.ensure((size_t)h->d.n_channels * si * h->in_eb, (size_t)h->d.n_channels * so * h->out_eb))) { return rc; }
-  HIP_TRY(hipMemcpy2D(h->st.d_in, (size_t)si * h->in_eb, h_in, (size_t)n_in * h->in_eb, (size_t)n_in * h->in_eb,
-                      (size_t)h->d.n_channels, hipMemcpyHostToDevice));
-  int64_t no2 = 0;
-  if ((rc = acdsp_cic_run(h, h->st.d_in, si, n_in, h->st.d_out, so, &no2, nullptr))) { return rc; }
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  if (no > 0) {
-    HIP_TRY(hipMemcpy2D(h_out, (size_t)no * h->out_eb, h->st.d_out, (size_t)so * h->out_eb, (size_t)no * h->out_eb,
-                        (size_t)h->d.n_channels, hipMemcpyDeviceToHost));
-  }
-  return ACDSP_OK;
+  const HostRows r = {h->d.n_channels, h_in, n_in, (n_in + 15) / 16 * 16, h->in_eb, h_out, no, (no + 7) / 8 * 8 + 8, no, h->out_eb};
+  return run_host_staged(h->st, r, true, [&](const void *d_in, void *d_out, bool) { return acdsp_cic_run(h, d_in, r.si, n_in, d_out, r.so, nullptr, nullptr); });
 }
 
 int32_t acdsp_cic_last_kernel_ms(acdsp_cic_t h, float *ms) {

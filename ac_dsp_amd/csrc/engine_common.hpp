@@ -1,7 +1,10 @@
-// engine_common.hpp -- what the translation units of the C-ABI layer share (round 5: engine.hip, 2 700 lines of every operator family,
-// split per family: engine.hip = entry points common to all + diagnostics + state blobs + stream files, engine_fir.hip, engine_cic.hip,
-// engine_ddc.hip, engine_poly.hip, engine_misc.hip).  Host-side object model: one handle = n independent reference filter objects whose
-// state lives in HBM and carries across run() calls.  There is no CPU compute path: every run() launches HIP kernels.
+// engine_common.hpp -- what the translation units of the C-ABI layer share: engine.hip (entry points common to all + diagnostics + state
+// blobs + stream files) and one file per operator family, engine_fir.hip, engine_cic.hip, engine_ddc.hip, engine_poly.hip, engine_misc.hip.
+// Host-side object model: one handle = n independent reference filter objects whose state lives in HBM and carries across run() calls.
+// There is no CPU compute path: every run() launches HIP kernels.
+// Building blocks of the handles, each the single owner of what the families used to spell out one by one: DevBuf (one device allocation),
+// History (the ping-pong input history), PhasePlans (per first % 16 fir_gen plans with their fragments), Staging + run_host_staged (the
+// host-buffer calls), sat_free_bound / fits_container (arithmetic of the path decisions), Timer (event ring).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,7 +12,9 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "wide_kernels.hpp"
@@ -44,10 +49,6 @@ inline bool stream_is_capturing(hipStream_t s) {
     if (e_ != hipSuccess) { return fail(ACDSP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } \
   } while (0)
 
-// history buffer the state kernel of a call writes: the current one (in place) when the call's input alone defines the new
-// history, else the other one
-inline int hist_next_index(int cur, bool in_place) { return in_place ? cur : (cur ^ 1); }
-
 // max_w: 64 for IN / COEFF and every class without a wide path; 128 for ACC / OUT of the FIR classes and OUT of the CIC classes
 // (wide.hip).  Unsigned types of the full container width are not representable in the signed raw words and are refused.
 inline int check_fmt(const acdsp_fmt_t &f, const char *name, int max_w = 64) {
@@ -69,28 +70,53 @@ inline bool trace_handles() {
 inline int elem_bytes(int W) { return W <= 16 ? 2 : (W <= 32 ? 4 : (W <= 64 ? 8 : 16)); }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// The one sample-width predicate of the matrix-core paths: do the value bits of `f` (an unsigned type needs one more) fit `eb` byte planes?
+inline bool fits_container(const acdsp_fmt_t &f, int eb) { return (f.W + (f.S ? 0 : 1) + 7) / 8 <= eb; }
+
+// sum of |c[i]|
+inline unsigned __int128 sum_abs(const int64_t *c, size_t n) {
+  unsigned __int128 sa = 0;
+  for (size_t i = 0; i < n; i++) { sa += (unsigned __int128)(c[i] < 0 ? -(__int128)c[i] : (__int128)c[i]); }
+  return sa;
+}
+
+// "A saturating accumulator that cannot saturate is a wrapping one": is  ((sa * max|x|) << lshift >> rshift) + lsb_slack  inside the top value
+// of ACC_TYPE `acc` (the SYMMETRIC range of a signed type, so that none of the three saturating modes acts)?  sa = sum|c| over every term of a
+// partial sum (or the number of unit-weight terms); lshift / rshift move the products to the accumulator's fraction (0 <= rshift < 64);
+// lsb_slack = one LSB per term whose product is quantised on the way, + 1 (0 where nothing is dropped).  The callers keep their own
+// preconditions (signedness, Q modes, pre-add widths); the answer decides whether a handle drops saturation, so a wrong "yes" is a silent
+// parity error: every step that could leave 128 bits answers "no".
+inline bool sat_free_bound(unsigned __int128 sa, const acdsp_fmt_t &in, const acdsp_fmt_t &acc, int lshift, int rshift, size_t lsb_slack) {
+  const unsigned __int128 xmax = in.S ? ((unsigned __int128)1 << (in.W - 1)) : (((unsigned __int128)1 << in.W) - 1);
+  const unsigned __int128 top = ((unsigned __int128)1 << (acc.W - (acc.S ? 1 : 0))) - 1;
+  unsigned __int128 b = sa * xmax;                       // W_in, W_coeff <= 64, but sums of 2^10 taps (sa < 2^74) times 2^64 may overflow
+  if (sa != 0 && b / sa != xmax) { return false; }
+  if (lshift > 0 && (b >> (127 - lshift)) != 0) { return false; }
+  b = ((b << lshift) >> rshift) + (unsigned __int128)lsb_slack;
+  return b <= top;
+}
+
 // HIP-event timing of the main kernel of each run(), recorded on the launch stream.
 // A ring of event pairs so that a whole timed region can be read back afterwards.
 struct Timer {
   static const int kRing = 64;
-  hipEvent_t e0[kRing], e1[kRing];
+  hipEvent_t e0[kRing] = {}, e1[kRing] = {};
   int64_t count = 0;  // runs recorded so far
-  bool ok = false;
-  int init() {
-    for (int i = 0; i < kRing; i++) { e0[i] = nullptr; e1[i] = nullptr; }
-    for (int i = 0; i < kRing; i++) {
-      HIP_TRY(hipEventCreate(&e0[i]));
-      HIP_TRY(hipEventCreate(&e1[i]));
-    }
-    ok = true;
-    return ACDSP_OK;
-  }
-  void destroy() {
-    if (!ok) { return; }
+  Timer() = default;
+  Timer(const Timer &) = delete;
+  Timer &operator=(const Timer &) = delete;
+  ~Timer() {
     for (int i = 0; i < kRing; i++) {
       if (e0[i]) { (void)hipEventDestroy(e0[i]); }
       if (e1[i]) { (void)hipEventDestroy(e1[i]); }
     }
+  }
+  int init() {
+    for (int i = 0; i < kRing; i++) {
+      HIP_TRY(hipEventCreate(&e0[i]));
+      HIP_TRY(hipEventCreate(&e1[i]));
+    }
+    return ACDSP_OK;
   }
   hipEvent_t start() { return e0[count % kRing]; }
   hipEvent_t stop() { return e1[count % kRing]; }
@@ -117,38 +143,190 @@ struct Timer {
   }
 };
 
+// Move-only owner of one device allocation.  The destructor frees on the calling thread's current device: acdsp_*_destroy makes the
+// handle's device current before it deletes the handle.
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p_, o.p_); return *this; }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p_) { (void)hipFree(p_); p_ = nullptr; }
+  }
+  // (a live buffer is freed first: the caller has made sure that no kernel still reads it)
+  int alloc(size_t bytes) {
+    release();
+    HIP_TRY(hipMalloc(&p_, bytes));
+    return ACDSP_OK;
+  }
+  int alloc_zeroed(size_t bytes) {
+    const int rc = alloc(bytes);
+    return rc ? rc : zero(bytes);
+  }
+  int zero(size_t bytes) {
+    HIP_TRY(hipMemset(p_, 0, bytes));
+    return ACDSP_OK;
+  }
+  int upload(const void *host, size_t bytes) {   // synchronous
+    HIP_TRY(hipMemcpy(p_, host, bytes, hipMemcpyHostToDevice));
+    return ACDSP_OK;
+  }
+  template <typename T>
+  int alloc_upload(const std::vector<T> &v) {
+    const int rc = alloc(v.size() * sizeof(T));
+    return rc ? rc : upload(v.data(), v.size() * sizeof(T));
+  }
+  template <typename T = void>
+  T *get() const { return static_cast<T *>(p_); }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  void *p_ = nullptr;
+};
+
+// The ping-pong input history of a handle: rows x hl containers, all zero at creation.  A captured HIP graph has both buffers' addresses
+// baked into its kernel arguments, so the two allocations live exactly as long as the handle.
+class History {
+ public:
+  int init(int rows, int hl, int elem_bytes) {
+    bytes_ = (size_t)rows * hl * elem_bytes;
+    for (DevBuf &b : buf_) {
+      const int rc = b.alloc_zeroed(bytes_);
+      if (rc) { return rc; }
+    }
+    return ACDSP_OK;
+  }
+  size_t bytes() const { return bytes_; }   // of one buffer
+  int index() const { return cur_; }
+  void *cur() const { return buf_[cur_].get(); }
+  // index of the buffer the state kernel of a call writes: the current one (in place) when the call's input alone defines the new
+  // history, else the other one ...
+  int next(bool in_place) const { return in_place ? cur_ : (cur_ ^ 1); }
+  void *at(int i) const { return buf_[i].get(); }
+  // ... which becomes the current one once that kernel is enqueued
+  void commit(int next) { cur_ = next; }
+  int zero() {   // (the caller has drained the device)
+    for (DevBuf &b : buf_) {
+      if (b) { const int rc = b.zero(bytes_); if (rc) { return rc; } }
+    }
+    return ACDSP_OK;
+  }
+  // clone: this (fresh) history takes the current state of `o` (same geometry)
+  int copy_from(const History &o) {
+    HIP_TRY(hipMemcpy(buf_[0].get(), o.cur(), bytes_, hipMemcpyDeviceToDevice));
+    cur_ = 0;
+    return ACDSP_OK;
+  }
+
+ private:
+  DevBuf buf_[2];
+  size_t bytes_ = 0;
+  int cur_ = 0;
+};
+
+// words of one fir_gen fragment slab: fir_gen_plan gives at most 3 coefficient byte planes x 8 K-blocks, each [64 lanes][4] dwords
+constexpr int kGenMaxPlanes = 3, kGenMaxBlocks = 8;
+constexpr size_t kGenFragWords = (size_t)kGenMaxPlanes * kGenMaxBlocks * 64 * 4;
+
+// fir_gen plans of one tap set for each window offset first % 16 (a decimator's calls start at any phase), built and uploaded on the first use
+// of a phase; the fragments share one device slab of 16.
+class PhasePlans {
+ public:
+  int init() { return frag_.alloc(16 * kGenFragWords * sizeof(uint32_t)); }
+  // *plan = the plan of phase `fm` and *frag its device fragments, or *plan = nullptr where the taps have no plan at that phase (the caller
+  // falls back or refuses: not an error here).  A non-zero return is a HIP failure.
+  int get(const std::vector<int64_t> &taps, int R, int fm, hipStream_t s, const FirGenPlan **plan, const uint32_t **frag) {
+    uint32_t *d = frag_.get<uint32_t>() + (size_t)fm * kGenFragWords;
+    *plan = nullptr;
+    if (!((have_ >> fm) & 1)) {
+      std::vector<uint32_t> fr;
+      if (!fir_gen_plan(taps.data(), (int)taps.size(), R, fm, &plan_[fm], &fr) || fr.size() > kGenFragWords) { return ACDSP_OK; }
+      HIP_TRY(hipMemcpyAsync(d, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipStreamSynchronize(s));   // fr is a stack vector
+      have_ |= 1u << fm;
+    }
+    *plan = &plan_[fm];
+    *frag = d;
+    return ACDSP_OK;
+  }
+
+ private:
+  FirGenPlan plan_[16];
+  uint32_t have_ = 0;
+  DevBuf frag_;   // [16][kGenFragWords]
+};
+
+// Buffers of the host-side calls (run_host_staged)
 struct Staging {
-  void *d_in = nullptr, *d_out = nullptr;
+  DevBuf d_in, d_out;
   size_t cap_in = 0, cap_out = 0;
   // Small calls (the drop-in run() of one channel, ac_fir_prog_coeffs: ONE sample per call, reference ac_fir_prog_coeffs.h:281):
   // a pinned, device-mapped host buffer the kernels read and write directly -- no H2D / D2H copy calls, one synchronisation.
   static const size_t kPinBytes = 64 * 1024;
   void *pin_in = nullptr, *pin_out = nullptr;
+  static bool pinned_enabled() { static const bool off = getenv("ACDSP_NO_PINNED") != nullptr; return !off; }   // A/B knob: always the device staging buffers
+  Staging() = default;
+  Staging(const Staging &) = delete;
+  Staging &operator=(const Staging &) = delete;
+  ~Staging() {
+    if (pin_in) { (void)hipHostFree(pin_in); }
+    if (pin_out) { (void)hipHostFree(pin_out); }
+  }
   int ensure_pinned() {
     if (!pin_in) { HIP_TRY(hipHostMalloc(&pin_in, kPinBytes, hipHostMallocMapped)); }
     if (!pin_out) { HIP_TRY(hipHostMalloc(&pin_out, kPinBytes, hipHostMallocMapped)); }
     return ACDSP_OK;
   }
   int ensure(size_t bin, size_t bout) {
+    int rc;
     if (bin > cap_in) {
-      if (d_in) { (void)hipFree(d_in); }
-      HIP_TRY(hipMalloc(&d_in, bin));
+      cap_in = 0;
+      if ((rc = d_in.alloc(bin))) { return rc; }
       cap_in = bin;
     }
     if (bout > cap_out) {
-      if (d_out) { (void)hipFree(d_out); }
-      HIP_TRY(hipMalloc(&d_out, bout));
+      cap_out = 0;
+      if ((rc = d_out.alloc(bout))) { return rc; }
       cap_out = bout;
     }
     return ACDSP_OK;
   }
-  void destroy() {
-    if (d_in) { (void)hipFree(d_in); }
-    if (d_out) { (void)hipFree(d_out); }
-    if (pin_in) { (void)hipHostFree(pin_in); }
-    if (pin_out) { (void)hipHostFree(pin_out); }
-  }
 };
+
+// One host-buffer call: `rows` rows of n_in containers of in_eb bytes, packed in h_in, go into device rows of `si` containers; `run(d_in,
+// d_out, pinned)` performs the family's device run() on the NULL stream (rows of si / so containers) and returns its status; after one
+// synchronisation n_out containers of out_eb bytes per row come back into h_out, whose rows are out_pitch containers apart.
+// pin_small: calls whose padded images both fit Staging::kPinBytes go through the pinned buffers instead.
+struct HostRows {
+  int rows;
+  const void *h_in; int64_t n_in, si; int in_eb;
+  void *h_out; int64_t n_out, so, out_pitch; int out_eb;
+};
+template <typename Run>
+int run_host_staged(Staging &st, const HostRows &r, bool pin_small, Run run) {
+  const size_t rows = (size_t)r.rows, bin = rows * r.si * r.in_eb, bout = rows * r.so * r.out_eb;
+  const size_t in_row = (size_t)r.n_in * r.in_eb, out_row = (size_t)r.n_out * r.out_eb;
+  int rc;
+  if (pin_small && bin <= Staging::kPinBytes && bout <= Staging::kPinBytes && Staging::pinned_enabled()) {
+    if ((rc = st.ensure_pinned())) { return rc; }
+    for (size_t c = 0; c < rows; c++) { memcpy((char *)st.pin_in + c * r.si * r.in_eb, (const char *)r.h_in + c * in_row, in_row); }
+    if ((rc = run(st.pin_in, st.pin_out, true))) { return rc; }
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    for (size_t c = 0; c < rows; c++) { memcpy((char *)r.h_out + c * r.out_pitch * r.out_eb, (const char *)st.pin_out + c * r.so * r.out_eb, out_row); }
+    return ACDSP_OK;
+  }
+  if ((rc = st.ensure(bin, bout))) { return rc; }
+  if (in_row > 0) { HIP_TRY(hipMemcpy2D(st.d_in.get(), (size_t)r.si * r.in_eb, r.h_in, in_row, in_row, rows, hipMemcpyHostToDevice)); }
+  if ((rc = run(st.d_in.get(), st.d_out.get(), false))) { return rc; }
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  if (out_row > 0) {
+    HIP_TRY(hipMemcpy2D(r.h_out, (size_t)r.out_pitch * r.out_eb, st.d_out.get(), (size_t)r.so * r.out_eb, out_row, rows, hipMemcpyDeviceToHost));
+  }
+  return ACDSP_OK;
+}
 
 }  // namespace eng
 }  // namespace acdsp
@@ -156,6 +334,9 @@ struct Staging {
 using namespace acdsp;   // (the handle structs live in the global namespace: they are the opaque types of include/acdsp.h)
 using acdsp::eng::Timer;
 using acdsp::eng::Staging;
+using acdsp::eng::DevBuf;
+using acdsp::eng::History;
+using acdsp::eng::PhasePlans;
 
 struct acdsp_fir {
   acdsp_fir_desc_t d;
@@ -169,9 +350,8 @@ struct acdsp_fir {
   bool small_call = false;   // set by run_host around a call that fits the pinned buffers (launch-bound: see acdsp_fir_run)
   int rt_eb = 8;
   int path;
-  void *d_hist[2] = {nullptr, nullptr};
-  int64_t *d_rt[2] = {nullptr, nullptr};
-  int cur = 0;
+  History hist;
+  DevBuf d_rt[2];               // reg_trans[] (use_rt), ping-pong: indexed by the history's index, or by cur_rt (rt_hybrid)
   // TRANSPOSED with loadable coefficients, exact-sum class (rt_hybrid): reg_trans[] differs from an input history only while partial sums
   // of an EARLIER coefficient set are still in it -- for the n_taps - 1 samples behind a coefficient change (or a loaded state blob).  Those
   // samples run the exact-order kernel on reg_trans; everything else is the same dot product as SHIFT_REG and runs the matrix-core kernels
@@ -181,20 +361,20 @@ struct acdsp_fir {
   bool in_flip = false;
   bool rt_hybrid = false, rt_valid = true;
   int64_t rt_since = 0;         // samples since the last coefficient change / state load, saturating at n_taps - 1
-  int cur_rt = 0;               // rt_hybrid: index of the current reg_trans buffer (the history has `cur`)
-  int64_t *d_coeffs = nullptr;
-  uint32_t *d_frag = nullptr;   // [n_sets][2][nb][64][4] Toeplitz byte-plane fragments
-  int64_t *d_corr = nullptr;    // [n_sets] 128 * sum(c)
+  int cur_rt = 0;               // rt_hybrid: index of the current reg_trans buffer (the history has its own)
+  DevBuf d_coeffs;
+  DevBuf d_frag;                // [n_sets][2][nb][64][4] Toeplitz byte-plane fragments
+  DevBuf d_corr;                // [n_sets] 128 * sum(c)
   FirMfmaPlan plan;             // worst case over the coefficient sets (bounds for the epilogue choice)
   bool mfma_ok = false;
   int mfma_cshift = 0;          // the fragments hold the coefficients scaled by 2^mfma_cshift (narrow types: engine_fir.hip, set_coeffs)
-  uint32_t *d_gfrag = nullptr;  // fragments of the generalised (wide-input) MFMA kernel
+  DevBuf d_gfrag;               // fragments of the generalised (wide-input) MFMA kernel
   FirGenPlan gplan;
   bool gen_ok = false;
   // class B on the matrix cores (fir_gen.hip, LZ ring shapes): gplan / d_gfrag hold the plan of the effective taps, lzp the residue table
   bool lz_ok = false;
   FirLossyPlan lzp;
-  uint32_t *d_lzcl = nullptr;
+  DevBuf d_lzcl;
   int64_t n_runs = 0;             // run() calls that launched kernels (ACDSP_TRACE)
   int kclass = 0;                 // acdsp_fir_kernel_class
   std::vector<int64_t> h_coeffs;  // last coefficient set (for clone)
@@ -209,29 +389,23 @@ struct acdsp_cic {
   // decimator through its FIR identity on the matrix cores (fir_gen.hip): taps, and per (first mod 16) plans / fragments
   std::vector<int64_t> h_taps;
   bool gen_ok = false;
-  bool gen_have[16] = {false};
-  FirGenPlan gen_plan[16];
-  uint32_t *d_gfrag = nullptr;   // [16][3*8*64*4]
+  PhasePlans gen;
   // decimator in two stages (cic2.hip): R = c2_R1 * c2_R2, stage-1 taps z^-(N-1) boxcar(R1)^N with their per (first mod 16) plans / fragments
   bool c2_ok = false;
   int c2_R1 = 0, c2_R2 = 0, c2_wu = 0;
   std::vector<int64_t> c2_taps;
-  bool c2_have[16] = {false};
-  FirGenPlan c2_plan[16];
-  uint32_t *d_c2frag = nullptr;  // [16][3*8*64*4]
+  PhasePlans c2;
   int warm = 0;                  // inputs the recurrence kernel simulates in front of a chunk (the filter memory; hl may be longer: cic2.hip)
-  int64_t *d_taps = nullptr;     // interpolator: the identity's taps for the polyphase kernel
+  DevBuf d_taps;                 // interpolator: the identity's taps for the polyphase kernel
   // interpolator on the matrix cores (fir_up.hip): per-phase taps E_r[k] = h[r + R k]
   bool up_ok = false;
   int up_px = 0;
   FirUpPlan up_plan;
-  uint32_t *d_upfrag = nullptr;
-  int64_t *d_upcorr = nullptr;
+  DevBuf d_upfrag, d_upcorr;
   int last_path = 0;
   bool wide = false;    // INT_TYPE or OUT_TYPE wider than 64 bits: both directions through cic_wide_kernel (wide.hip)
   int64_t t_total = 0;  // inputs consumed so far (all calls)
-  void *d_hist[2] = {nullptr, nullptr};
-  int cur = 0;
+  History hist;
   Timer tm;
   Staging st;
 };
@@ -243,22 +417,22 @@ struct acdsp_ddc {
   bool fused = false;            // decided at creation / coefficient load; a handle never switches modes mid-stream
   // fused mode: the only state is the input history (stage B's window is recomputed from it) and the input count
   int hl = 0;
-  void *d_hist[2] = {nullptr, nullptr};
-  int cur = 0;
+  History hist;
   int64_t t_total = 0;
-  bool haveA[16] = {false};
-  FirGenPlan planA[16], planB;
-  uint32_t *d_fragA = nullptr, *d_fragB = nullptr;
+  PhasePlans plansA;
+  FirGenPlan planB;
+  DevBuf d_fragB;
   bool coeffs_set = false;
   // two-kernel mode: intermediate stream
-  void *d_mid = nullptr;
+  DevBuf d_mid;
   int64_t mid_cap = 0;
   Timer tm;
 };
 
-
 namespace acdsp {
 namespace eng {
+// current reg_trans[] buffer of a use_rt handle
+inline int64_t *fir_rt_cur(const acdsp_fir *h) { return h->d_rt[h->rt_hybrid ? h->cur_rt : h->hist.index()].get<int64_t>(); }
 // FIR helpers other families use (engine_fir.hip)
 std::vector<int64_t> effective_coeffs(const int64_t *c, int N, int ftype);
 int internal_ftype(int kind, int ftype);

@@ -11,6 +11,17 @@ static inline DFmt fir_acc_fmt(const acdsp_fir *h) {
   return a;
 }
 
+// the handle's formats as the class queries of the int8 MFMA kernel see them (epilogue class, register residency, MFMAs issued): the
+// fragments hold the coefficients scaled by 2^cshift, so COEFF_TYPE has cshift more fraction bits there (set_coeffs)
+static FirParams fir_class_params(const acdsp_fir *h, int cshift) {
+  FirParams k;
+  memset(&k, 0, sizeof k);
+  k.in = make_dfmt(h->d.in); k.cf = make_dfmt(h->d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(h->d.out);
+  k.cf.F += cshift;
+  k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
+  return k;
+}
+
 // ---------------------------------------------------------------------------------------------
 // FIR
 // ---------------------------------------------------------------------------------------------
@@ -98,7 +109,7 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   int rc = fir_validate(*desc);
   if (rc) { return rc; }
   if ((rc = check_device(desc->device))) { return rc; }
-  acdsp_fir *h = new acdsp_fir();
+  std::unique_ptr<acdsp_fir> h(new acdsp_fir());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   h->in_eb = elem_bytes(desc->in.W);
   h->out_eb = elem_bytes(desc->out.W);
@@ -132,31 +143,21 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   h->lossless = lossless && desc->acc.O == ACDSP_WRAP;
   h->coeffs_set = false;
   h->path = ACDSP_PATH_GENERIC;
-  const size_t hist_bytes = (size_t)desc->n_channels * h->hl * h->in_eb;
   const size_t n_sets = desc->coeffs_per_channel ? (size_t)desc->n_channels : 1;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = hipMalloc(&h->d_hist[i], hist_bytes);
-    if (e == hipSuccess) { e = hipMemset(h->d_hist[i], 0, hist_bytes); }
-    if (e == hipSuccess && h->use_rt) {
-      size_t rb = (size_t)desc->n_channels * desc->n_taps * h->rt_eb;
-      e = hipMalloc((void **)&h->d_rt[i], rb);
-      if (e == hipSuccess) { e = hipMemset(h->d_rt[i], 0, rb); }
-    }
+  const int nbk = fir_mfma_plan_blocks(desc->n_taps);
+  if ((rc = h->hist.init(desc->n_channels, h->hl, h->in_eb))) { return rc; }
+  for (DevBuf &rt : h->d_rt) {
+    if (h->use_rt && (rc = rt.alloc_zeroed((size_t)desc->n_channels * desc->n_taps * h->rt_eb))) { return rc; }
   }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_coeffs, n_sets * desc->n_taps * sizeof(int64_t)); }
-  {
-    const int nbk = fir_mfma_plan_blocks(desc->n_taps);
-    if (e == hipSuccess) { e = hipMalloc((void **)&h->d_frag, n_sets * sizeof(uint32_t) * 2 * (size_t)(nbk > 0 ? nbk : 1) * 64 * 4); }
+  if ((rc = h->d_coeffs.alloc(n_sets * desc->n_taps * sizeof(int64_t))) ||
+      (rc = h->d_frag.alloc(n_sets * sizeof(uint32_t) * 2 * (size_t)(nbk > 0 ? nbk : 1) * 64 * 4)) ||
+      (rc = h->d_corr.alloc(n_sets * sizeof(int64_t))) ||
+      (rc = h->d_gfrag.alloc(kGenFragWords * sizeof(uint32_t))) ||
+      (rc = h->d_lzcl.alloc(kLossyTabWords * sizeof(uint32_t))) ||
+      (rc = h->tm.init())) {
+    return rc;
   }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_corr, n_sets * sizeof(int64_t)); }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_gfrag, 3 * 8 * 64 * 4 * sizeof(uint32_t)); }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_lzcl, kLossyTabWords * sizeof(uint32_t)); }
-  if (e != hipSuccess || h->tm.init() != ACDSP_OK) {
-    acdsp_fir_destroy(h);
-    return fail(ACDSP_EHIP, "FIR state allocation failed: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  *out = h.release();
   if (trace_handles()) { fprintf(stderr, "[acdsp] fir_create kind=%d ftype=%d n_taps=%d n_channels=%d\n", desc->kind, desc->ftype, desc->n_taps, desc->n_channels); }
   return ACDSP_OK;
 }
@@ -165,17 +166,6 @@ int32_t acdsp_fir_destroy(acdsp_fir_t h) {
   if (!h) { return ACDSP_OK; }
   if (trace_handles()) { fprintf(stderr, "[acdsp] fir_destroy kernel_runs=%lld\n", (long long)h->n_runs); }
   (void)hipSetDevice(h->d.device);
-  for (int i = 0; i < 2; i++) {
-    if (h->d_hist[i]) { (void)hipFree(h->d_hist[i]); }
-    if (h->d_rt[i]) { (void)hipFree(h->d_rt[i]); }
-  }
-  if (h->d_coeffs) { (void)hipFree(h->d_coeffs); }
-  if (h->d_frag) { (void)hipFree(h->d_frag); }
-  if (h->d_corr) { (void)hipFree(h->d_corr); }
-  if (h->d_gfrag) { (void)hipFree(h->d_gfrag); }
-  if (h->d_lzcl) { (void)hipFree(h->d_lzcl); }
-  h->tm.destroy();
-  h->st.destroy();
   delete h;
   return ACDSP_OK;
 }
@@ -193,9 +183,9 @@ int32_t fir_rt_from_hist(acdsp_fir *h) {
   k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(d.out);
   k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl; k.use_rt = 1;
   k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
-  k.x = h->d_hist[h->cur]; k.in_stride = h->hl; k.n = h->hl;
-  k.coeffs = h->d_coeffs; k.rt = h->d_rt[h->cur_rt];
-  const hipError_t e = launch_fir_rt_update(k, h->d_rt[h->cur_rt ^ 1], nullptr);
+  k.x = h->hist.cur(); k.in_stride = h->hl; k.n = h->hl;
+  k.coeffs = h->d_coeffs.get<int64_t>(); k.rt = h->d_rt[h->cur_rt].get<int64_t>();
+  const hipError_t e = launch_fir_rt_update(k, h->d_rt[h->cur_rt ^ 1].get<int64_t>(), nullptr);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "reg_trans rebuild failed: %s", hipGetErrorString(e)); }
   HIP_TRY(hipDeviceSynchronize());
   h->cur_rt ^= 1;
@@ -234,7 +224,7 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
   // against h_coeffs), so the handle is without a set until the call succeeds
   h->coeffs_set = false;
   h->h_coeffs.clear();
-  HIP_TRY(hipMemcpy(h->d_coeffs, coeffs, n_sets * d.n_taps * sizeof(int64_t), hipMemcpyHostToDevice));
+  if ((rc = h->d_coeffs.upload(coeffs, n_sets * d.n_taps * sizeof(int64_t)))) { return rc; }
   h->mfma_ok = false;
   h->in_flip = false;
   {
@@ -250,22 +240,10 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
       const int need_i = d.in.I + 1 + (!d.in.S ? 1 : 0);
       sf = fa_ >= fi_ && d.acc.I >= need_i;
     }
-    const unsigned __int128 xmax = d.in.S ? ((unsigned __int128)1 << (d.in.W - 1)) : (((unsigned __int128)1 << d.in.W) - 1);
-    const unsigned __int128 top = ((unsigned __int128)1 << (d.acc.W - 1)) - 1;
     for (size_t st = 0; st < n_sets && sf; st++) {
       const std::vector<int64_t> eff = effective_coeffs(coeffs + st * d.n_taps, d.n_taps, ift_);
-      unsigned __int128 sa = 0;
-      for (int64_t v : eff) { sa += (unsigned __int128)(v < 0 ? -(__int128)v : (__int128)v); }
-      unsigned __int128 b = sa * xmax;                       // < 2^64 * 2^64 would overflow: W_in, W_coeff <= 64 but sums of 2^10 taps -- guard
-      if (sa != 0 && b / sa != xmax) { sf = false; break; }
-      if (fa_ >= fi_ + fc_) {
-        const int ls = fa_ - fi_ - fc_;
-        if (ls > 0 && (b >> (127 - ls)) != 0) { sf = false; break; }
-        b <<= ls;
-      } else {
-        b = (b >> (fi_ + fc_ - fa_)) + (unsigned __int128)eff.size() + 1;
-      }
-      sf = b <= top;
+      const unsigned __int128 sa = sum_abs(eff.data(), eff.size());
+      sf = fa_ >= fi_ + fc_ ? sat_free_bound(sa, d.in, d.acc, fa_ - fi_ - fc_, 0, 0) : sat_free_bound(sa, d.in, d.acc, 0, fi_ + fc_ - fa_, eff.size() + 1);
     }
     h->sat_free = sf;
     h->lossless = h->lossless_shape && (d.acc.O == ACDSP_WRAP || sf);
@@ -323,28 +301,17 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
       const int want = (h->out_eb == 2 && rse < 1 && rse > -14 && !no_cshift) ? 1 - rse : 0;
       if (want > 0) {
         build(want);
-        FirParams k;
-        memset(&k, 0, sizeof k);
-        k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(d.out);
-        k.cf.F += want;
-        k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
-        const int epi = ok ? fir_mfma_epilogue_class(k, worst) : 0;
+        const int epi = ok ? fir_mfma_epilogue_class(fir_class_params(h, want), worst) : 0;
         if (epi == 1 || epi == 2) { h->mfma_cshift = want; }
       }
       if (!h->mfma_cshift) { build(0); }
     }
     if (ok && d.coeffs_per_channel && worst.nb > fir_mfma_max_reg_blocks()) {
       // a set per channel needs the register-resident kernels: beyond 9 K-blocks only band-limited sets with the fast int16 epilogue
-      FirParams k;
-      memset(&k, 0, sizeof k);
-      k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(d.out);
-      k.cf.F += h->mfma_cshift;
-      k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
-      ok = fir_mfma_register_resident(k, worst);
+      ok = fir_mfma_register_resident(fir_class_params(h, h->mfma_cshift), worst);
     }
     if (ok) {
-      HIP_TRY(hipMemcpy(h->d_frag, frag.data(), frag.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(h->d_corr, corr.data(), corr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+      if ((rc = h->d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = h->d_corr.upload(corr.data(), corr.size() * sizeof(int64_t)))) { return rc; }
       h->plan = worst;
       h->mfma_ok = true;
       h->in_flip = flip;
@@ -354,11 +321,11 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
   h->gen_ok = false;
   static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
   if (!h->mfma_ok && h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel && !no_gen &&
-      (d.in.W + (d.in.S ? 0 : 1) + 7) / 8 <= h->in_eb) {
+      fits_container(d.in, h->in_eb)) {
     std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
     std::vector<uint32_t> gfrag;
     if (fir_gen_plan(eff.data(), d.n_taps, 1, 0, &h->gplan, &gfrag)) {
-      HIP_TRY(hipMemcpy(h->d_gfrag, gfrag.data(), gfrag.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      if ((rc = h->d_gfrag.upload(gfrag.data(), gfrag.size() * sizeof(uint32_t)))) { return rc; }
       h->gen_ok = true;
     }
   }
@@ -385,7 +352,7 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
     const bool anti = ift == kRsFoldEvenAnti || ift == kRsFoldOddAnti;
     bool ok = !no_lz && !no_gen && !h->wide && !h->lossless && !h->use_rt && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel &&
               (d.acc.O == ACDSP_WRAP || h->sat_free) && (d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && d.acc.S && d.acc.W <= 64 && sbits >= 1 && sbits <= 15 &&
-              (h->in_eb == 2 || h->in_eb == 4) && (d.in.W + (d.in.S ? 0 : 1) + 7) / 8 <= h->in_eb &&
+              (h->in_eb == 2 || h->in_eb == 4) && fits_container(d.in, h->in_eb) &&
               (lz_first || !fir_lossy_fast_ok(kq));
     if (ok && fold_odd) {
       const int need_i = d.in.I + 1 + ((d.acc.S && !d.in.S) ? 1 : 0);
@@ -413,9 +380,8 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
       const int single0 = fold_odd ? (d.n_taps - 1) / 2 : 0;
       ok = ok && fir_gen_lossy_table(h->gplan, coeffs, d.n_taps, n_pair, n_single, single0, anti ? 1 : 0, sbits, d.acc.Q == ACDSP_RND, &h->lzp, &tab);
       if (ok) {
-        h->lzp.d_tab = h->d_lzcl; h->lzp.acc_bits = acc_bits;
-        HIP_TRY(hipMemcpy(h->d_gfrag, gfrag.data(), gfrag.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->d_lzcl, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        h->lzp.d_tab = h->d_lzcl.get<uint32_t>(); h->lzp.acc_bits = acc_bits;
+        if ((rc = h->d_gfrag.upload(gfrag.data(), gfrag.size() * sizeof(uint32_t))) || (rc = h->d_lzcl.upload(tab.data(), tab.size() * sizeof(uint32_t)))) { return rc; }
         h->lz_ok = true;
       }
     }
@@ -444,11 +410,11 @@ int32_t acdsp_fir_clone(acdsp_fir_t h, acdsp_fir_t *out) {
   if (rc) { return rc; }
   if (h->coeffs_set && (rc = acdsp_fir_set_coeffs(c, h->h_coeffs.data()))) { acdsp_fir_destroy(c); return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(c->d_hist[0], h->d_hist[h->cur], (size_t)h->d.n_channels * h->hl * h->in_eb, hipMemcpyDeviceToDevice));
+  if ((rc = c->hist.copy_from(h->hist))) { return rc; }
   if (h->use_rt) {
-    HIP_TRY(hipMemcpy(c->d_rt[0], h->d_rt[h->rt_hybrid ? h->cur_rt : h->cur], (size_t)h->d.n_channels * h->d.n_taps * h->rt_eb, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(c->d_rt[0].get(), fir_rt_cur(h), (size_t)h->d.n_channels * h->d.n_taps * h->rt_eb, hipMemcpyDeviceToDevice));
   }
-  c->cur = 0; c->cur_rt = 0; c->rt_valid = h->rt_valid; c->rt_since = h->rt_since;
+  c->cur_rt = 0; c->rt_valid = h->rt_valid; c->rt_since = h->rt_since;
   *out = c;
   return ACDSP_OK;
 }
@@ -479,7 +445,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
   k.in_stride = in_stride; k.out_stride = out_stride; k.n = n;
   k.x = d_in; k.y = d_out;
-  k.hist = h->d_hist[h->cur]; k.coeffs = h->d_coeffs; k.rt = h->d_rt[hyb ? h->cur_rt : h->cur];
+  k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>(); k.rt = fir_rt_cur(h);
   // rt_hybrid: the first m outputs still carry partial sums of the previous coefficient set
   int64_t m_rt = 0;
   if (hyb) {
@@ -493,16 +459,16 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   int path = h->path;
   if (h->wide) {
     FirWideParams kw;
-    kw.p = k; kw.acc = make_wfmt(d.acc); kw.out = make_wfmt(d.out); kw.rt = h->d_rt[h->cur];
+    kw.p = k; kw.acc = make_wfmt(d.acc); kw.out = make_wfmt(d.out); kw.rt = h->d_rt[h->hist.index()].get();
     HIP_TRY(hipEventRecord(h->tm.start(), s));
     hipError_t ew = launch_fir_wide(kw, s);
     if (ew != hipSuccess) { return fail(ACDSP_EHIP, "wide FIR kernel launch failed: %s", hipGetErrorString(ew)); }
     HIP_TRY(hipEventRecord(h->tm.stop(), s));
     h->tm.commit();
-    const int nxw = hist_next_index(h->cur, !h->use_rt && k.n >= k.hl);
-    ew = h->use_rt ? launch_fir_wide_rt_update(kw, h->d_rt[nxw], s) : launch_fir_hist_update(k, h->d_hist[nxw], s);
+    const int nxw = h->hist.next(!h->use_rt && k.n >= k.hl);
+    ew = h->use_rt ? launch_fir_wide_rt_update(kw, h->d_rt[nxw].get(), s) : launch_fir_hist_update(k, h->hist.at(nxw), s);
     if (ew != hipSuccess) { return fail(ACDSP_EHIP, "wide FIR state kernel launch failed: %s", hipGetErrorString(ew)); }
-    h->cur = nxw;
+    h->hist.commit(nxw);
     return ACDSP_OK;
   }
   FirParams kraw = k;   // the state kernels always see the caller's samples
@@ -527,9 +493,9 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     if (!aligned) {
       const int64_t si = (n + 15) / 16 * 16;
       if ((rc = h->st.ensure((size_t)d.n_channels * si * h->in_eb, 0))) { return rc; }
-      HIP_TRY(hipMemcpy2DAsync(h->st.d_in, (size_t)si * h->in_eb, d_in, (size_t)in_stride * h->in_eb, (size_t)n * h->in_eb,
+      HIP_TRY(hipMemcpy2DAsync(h->st.d_in.get(), (size_t)si * h->in_eb, d_in, (size_t)in_stride * h->in_eb, (size_t)n * h->in_eb,
                                (size_t)d.n_channels, hipMemcpyDeviceToDevice, s));
-      k.x = h->st.d_in; k.in_stride = si;
+      k.x = h->st.d_in.get(); k.in_stride = si;
     }
   }
   // Small calls (the drop-in run() of one channel; ac_fir_prog_coeffs is ONE sample per call, reference ac_fir_prog_coeffs.h:281)
@@ -537,20 +503,20 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   const bool small = h->small_call;
   const bool fuse_hist = small && !flipped && (!h->use_rt || hyb) && (path == ACDSP_PATH_LOSSLESS64 || path == ACDSP_PATH_GENERIC ||
                                                 (path == ACDSP_PATH_MFMA_I8 && !h->mfma_cshift && fir_mfma_register_resident(k, h->plan)));   // single-wave workgroups
-  const int nxt_fused = hist_next_index(h->cur, false);
-  if (fuse_hist) { k.hist_next = h->d_hist[nxt_fused]; }
+  const int nxt_fused = h->hist.next(false);
+  if (fuse_hist) { k.hist_next = h->hist.at(nxt_fused); }
   if (!small) { HIP_TRY(hipEventRecord(h->tm.start(), s)); }
   hipError_t e;
   if (path == ACDSP_PATH_MFMA_I8) {
     FirParams km = k;    // (the fragments hold c << mfma_cshift: the kernel's shifts follow; the state kernels below keep the handle's formats)
     km.cf.F += h->mfma_cshift; km.lossless_shift -= h->mfma_cshift;
-    e = launch_fir_mfma(km, h->plan, d.coeffs_per_channel, h->d_frag, h->d_corr, s);
+    e = launch_fir_mfma(km, h->plan, d.coeffs_per_channel, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s);
   }
-  else if (path == ACDSP_PATH_MFMA_GEN) { e = launch_fir_gen(k, h->gplan, h->d_gfrag, 0, 0, 0, n, s); }
+  else if (path == ACDSP_PATH_MFMA_GEN) { e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, 0, n, s); }
   else if (path == ACDSP_PATH_MFMA_LOSSY) {
     // complete chunks on the matrix cores, the ragged rest (and calls shorter than a chunk) on the exact-order kernel
     int64_t cov = 0;
-    e = launch_fir_gen(k, h->gplan, h->d_gfrag, 0, 0, 0, n, s, &h->lzp, &cov);
+    e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, 0, n, s, &h->lzp, &cov);
     if (e == hipSuccess && cov < n) { FirParams kt = k; kt.t_begin = cov; e = launch_fir_generic(kt, s); }
   }
   else if (path == ACDSP_PATH_LOSSLESS64) { e = launch_fir_lossless64(k, s); }
@@ -570,7 +536,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
       FirParams kt = k;
       kt.use_rt = 1; kt.n = m_rt; kt.hist_next = nullptr;
       e = launch_fir_generic(kt, s);
-      if (e == hipSuccess && m_rt == n) { e = launch_fir_rt_update(kt, h->d_rt[h->cur_rt ^ 1], s); }
+      if (e == hipSuccess && m_rt == n) { e = launch_fir_rt_update(kt, h->d_rt[h->cur_rt ^ 1].get<int64_t>(), s); }
       if (e != hipSuccess) { return fail(ACDSP_EHIP, "FIR reg_trans kernel launch failed: %s", hipGetErrorString(e)); }
       if (m_rt == n) { h->cur_rt ^= 1; h->rt_valid = true; } else { h->rt_valid = false; }   // past the transition reg_trans is rebuilt on demand
     } else {
@@ -578,19 +544,19 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     }
     h->rt_since = h->rt_since + n >= (int64_t)d.n_taps - 1 ? (int64_t)d.n_taps - 1 : h->rt_since + n;
   }
-  if (fuse_hist) { h->cur = nxt_fused; return ACDSP_OK; }
+  if (fuse_hist) { h->hist.commit(nxt_fused); return ACDSP_OK; }
   // state carry.  A call of at least hl samples takes the new history from its input alone: written in place behind the
   // main kernel (same stream), no buffer flip -- the handle's host-side state is then the same after every call, which is what
   // lets any schedule of such calls be captured into a HIP graph.  Shorter calls (and reg_trans, which reads its old value)
   // go into the other buffer, then flip.
-  const int nxt = hist_next_index(h->cur, (!h->use_rt || hyb) && k.n >= k.hl);
+  const int nxt = h->hist.next((!h->use_rt || hyb) && k.n >= k.hl);
   if (h->use_rt && !hyb) {
-    e = launch_fir_rt_update(k, h->d_rt[nxt], s);
+    e = launch_fir_rt_update(k, h->d_rt[nxt].get<int64_t>(), s);
   } else {
-    e = launch_fir_hist_update(flipped ? kraw : k, h->d_hist[nxt], s);
+    e = launch_fir_hist_update(flipped ? kraw : k, h->hist.at(nxt), s);
   }
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "FIR state kernel launch failed: %s", hipGetErrorString(e)); }
-  h->cur = nxt;
+  h->hist.commit(nxt);
   return ACDSP_OK;
 }
 
@@ -601,31 +567,13 @@ int32_t acdsp_fir_run_host(acdsp_fir_t h, const void *h_in, int64_t n, void *h_o
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   const int64_t stride = (n + 15) / 16 * 16;  // rows 16-byte aligned and readable in whole 16-sample slots
-  const size_t bin = (size_t)h->d.n_channels * stride * h->in_eb, bout = (size_t)h->d.n_channels * stride * h->out_eb;
-  static const bool no_pin = getenv("ACDSP_NO_PINNED") != nullptr;   // A/B knob: always go through the device staging buffers
-  if (bin <= Staging::kPinBytes && bout <= Staging::kPinBytes && !no_pin) {
-    if ((rc = h->st.ensure_pinned())) { return rc; }
-    for (int c = 0; c < h->d.n_channels; c++) {
-      memcpy((char *)h->st.pin_in + (size_t)c * stride * h->in_eb, (const char *)h_in + (size_t)c * n * h->in_eb, (size_t)n * h->in_eb);
-    }
-    h->small_call = true;
-    rc = acdsp_fir_run(h, h->st.pin_in, stride, n, h->st.pin_out, stride, nullptr);
+  const HostRows r = {h->d.n_channels, h_in, n, stride, h->in_eb, h_out, n, stride, n, h->out_eb};
+  return run_host_staged(h->st, r, true, [&](const void *d_in, void *d_out, bool pinned) {
+    h->small_call = pinned;
+    const int rc_run = acdsp_fir_run(h, d_in, stride, n, d_out, stride, nullptr);
     h->small_call = false;
-    if (rc) { return rc; }
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    for (int c = 0; c < h->d.n_channels; c++) {
-      memcpy((char *)h_out + (size_t)c * n * h->out_eb, (const char *)h->st.pin_out + (size_t)c * stride * h->out_eb, (size_t)n * h->out_eb);
-    }
-    return ACDSP_OK;
-  }
-  if ((rc = h->st.ensure(bin, bout))) { return rc; }
-  HIP_TRY(hipMemcpy2D(h->st.d_in, (size_t)stride * h->in_eb, h_in, (size_t)n * h->in_eb, (size_t)n * h->in_eb,
-                      (size_t)h->d.n_channels, hipMemcpyHostToDevice));
-  if ((rc = acdsp_fir_run(h, h->st.d_in, stride, n, h->st.d_out, stride, nullptr))) { return rc; }
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  HIP_TRY(hipMemcpy2D(h_out, (size_t)n * h->out_eb, h->st.d_out, (size_t)stride * h->out_eb, (size_t)n * h->out_eb,
-                      (size_t)h->d.n_channels, hipMemcpyDeviceToHost));
-  return ACDSP_OK;
+    return rc_run;
+  });
 }
 
 int32_t acdsp_fir_reset(acdsp_fir_t h) {
@@ -633,9 +581,9 @@ int32_t acdsp_fir_reset(acdsp_fir_t h) {
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(hipMemset(h->d_hist[i], 0, (size_t)h->d.n_channels * h->hl * h->in_eb));
-    if (h->d_rt[i]) { HIP_TRY(hipMemset(h->d_rt[i], 0, (size_t)h->d.n_channels * h->d.n_taps * h->rt_eb)); }
+  if ((rc = h->hist.zero())) { return rc; }
+  for (DevBuf &rt : h->d_rt) {
+    if (rt && (rc = rt.zero((size_t)h->d.n_channels * h->d.n_taps * h->rt_eb))) { return rc; }
   }
   h->rt_valid = true; h->rt_since = h->d.n_taps - 1;
   return ACDSP_OK;
@@ -653,13 +601,7 @@ int32_t acdsp_fir_kernel_stats(acdsp_fir_t h, int32_t last_k, float *avg_ms, flo
 
 int32_t acdsp_fir_mfma_epilogue(acdsp_fir_t h) {
   if (!h || !h->coeffs_set || h->path != ACDSP_PATH_MFMA_I8) { return -1; }
-  const acdsp_fir_desc_t &d = h->d;
-  FirParams k;
-  memset(&k, 0, sizeof k);
-  k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(d.out);
-  k.cf.F += h->mfma_cshift;
-  k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
-  return fir_mfma_epilogue_class(k, h->plan) | (h->mfma_cshift << 8) | (h->in_flip ? 1 << 16 : 0);
+  return fir_mfma_epilogue_class(fir_class_params(h, h->mfma_cshift), h->plan) | (h->mfma_cshift << 8) | (h->in_flip ? 1 << 16 : 0);
 }
 
 int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples) {
@@ -667,13 +609,7 @@ int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples) {
   if (!h->coeffs_set) { return fail(ACDSP_ESTATE, "acdsp_fir_mfma_issued before acdsp_fir_set_coeffs"); }
   *per_1024_samples = 0;
   if (h->path == ACDSP_PATH_MFMA_I8) {
-    const acdsp_fir_desc_t &d = h->d;
-    FirParams k;
-    memset(&k, 0, sizeof k);
-    k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(d.out);
-    k.cf.F += h->mfma_cshift;
-    k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
-    *per_1024_samples = fir_mfma_issued_per_step(k, h->plan);
+    *per_1024_samples = fir_mfma_issued_per_step(fir_class_params(h, h->mfma_cshift), h->plan);
   }
   return ACDSP_OK;
 }

@@ -10,13 +10,12 @@ using namespace acdsp::eng;
 struct acdsp_intgdump {
   acdsp_intgdump_desc_t d;
   int in_eb, out_eb;
-  int64_t *d_temp[2] = {nullptr, nullptr};
-  int cur = 0;
-  int64_t *d_blk = nullptr;     // [3][cap] off / rounds / out
-  int32_t *d_chain = nullptr;   // [cap]
+  History temp;                 // temp[]: n_objects x CHN ACC raw words (int64), ping-pong like an input history
+  DevBuf d_blk;                 // int64 [3][cap] off / rounds / out
+  DevBuf d_chain;               // int32 [cap]
   int64_t blk_cap = 0;
   bool pending = false;         // the last call ended on a block that did not dump: temp[] is non-zero
-  bool temp_zero = true;        // d_temp[cur] is known to be all zero (create / reset / zeroed behind a general-kernel call that dumped everything):
+  bool temp_zero = true;        // temp.cur() is known to be all zero (create / reset / zeroed behind a general-kernel call that dumped everything):
                                 // what the tile / stream kernels rely on when they leave temp[] alone (advisor, round 5)
   int last_path = 0;            // acdsp_intgdump_path
   // block table of the last call: a stream that dumps on a fixed schedule passes the same n_sample[] every call, and then
@@ -41,10 +40,6 @@ extern "C" {
 int32_t acdsp_intgdump_destroy(acdsp_intgdump_t h) {
   if (!h) { return ACDSP_OK; }
   (void)hipSetDevice(h->d.device);
-  for (int i = 0; i < 2; i++) { if (h->d_temp[i]) { (void)hipFree(h->d_temp[i]); } }
-  if (h->d_blk) { (void)hipFree(h->d_blk); }
-  if (h->d_chain) { (void)hipFree(h->d_chain); }
-  h->st.destroy();
   delete h;
   return ACDSP_OK;
 }
@@ -59,17 +54,11 @@ int32_t acdsp_intgdump_create(const acdsp_intgdump_desc_t *desc, acdsp_intgdump_
   int rc;
   if ((rc = check_fmt(d.in, "IN_TYPE")) || (rc = check_fmt(d.acc, "ACC_TYPE")) || (rc = check_fmt(d.out, "OUT_TYPE"))) { return rc; }
   if ((rc = check_device(d.device))) { return rc; }
-  acdsp_intgdump *h = new acdsp_intgdump();
+  std::unique_ptr<acdsp_intgdump> h(new acdsp_intgdump());   // (check_device has made the device current: a failure below frees there)
   h->d = d;
   h->in_eb = elem_bytes(d.in.W); h->out_eb = elem_bytes(d.out.W);
-  hipError_t e = hipSuccess;
-  const size_t tb = (size_t)d.n_objects * d.chn * sizeof(int64_t);
-  for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = hipMalloc((void **)&h->d_temp[i], tb);
-    if (e == hipSuccess) { e = hipMemset(h->d_temp[i], 0, tb); }   // temp[i] = 0.0 (ac_intg_dump.h:86-89)
-  }
-  if (e != hipSuccess) { acdsp_intgdump_destroy(h); return fail(ACDSP_EHIP, "intg_dump state allocation failed: %s", hipGetErrorString(e)); }
-  *out = h;
+  if ((rc = h->temp.init(d.n_objects, d.chn, sizeof(int64_t)))) { return rc; }   // temp[i] = 0.0 (ac_intg_dump.h:86-89)
+  *out = h.release();
   return ACDSP_OK;
 }
 
@@ -101,10 +90,8 @@ int32_t acdsp_intgdump_run(acdsp_intgdump_t h, const void *d_in, int64_t in_stri
   hipStream_t s = (hipStream_t)stream;
   if (n_blocks > h->blk_cap) {
     HIP_TRY(hipStreamSynchronize(s));
-    if (h->d_blk) { HIP_TRY(hipFree(h->d_blk)); h->d_blk = nullptr; }
-    if (h->d_chain) { HIP_TRY(hipFree(h->d_chain)); h->d_chain = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_blk, (size_t)3 * n_blocks * sizeof(int64_t)));
-    HIP_TRY(hipMalloc((void **)&h->d_chain, (size_t)n_blocks * sizeof(int32_t)));
+    h->blk_cap = 0;
+    if ((rc = h->d_blk.alloc((size_t)3 * n_blocks * sizeof(int64_t))) || (rc = h->d_chain.alloc((size_t)n_blocks * sizeof(int32_t)))) { return rc; }
     h->blk_cap = n_blocks;
     h->last_ns.clear();   // new device arrays: the table has to be uploaded again
   }
@@ -126,8 +113,8 @@ int32_t acdsp_intgdump_run(acdsp_intgdump_t h, const void *d_in, int64_t in_stri
     h->last_ns.clear();                 // (stays empty if the upload fails)
     // the previous table may still be read by a kernel on another stream: drain the device before overwriting it
     if (h->last_stream != stream) { HIP_TRY(hipDeviceSynchronize()); }
-    HIP_TRY(hipMemcpyAsync(h->d_blk, blk.data(), blk.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_chain, chain.data(), chain.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_blk.get(), blk.data(), blk.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_chain.get(), chain.data(), chain.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));   // blk / chain are stack vectors
     h->tbl_grp = grp; h->tbl_start = start;
     h->tbl_uni_rounds = blk[(size_t)n_blocks];
@@ -149,25 +136,25 @@ int32_t acdsp_intgdump_run(acdsp_intgdump_t h, const void *d_in, int64_t in_stri
   bool sat_free = false;
   if (d.acc.O != ACDSP_WRAP && !h->pending && grp == n_blocks && p.acc.F >= p.in.F && p.acc.F - p.in.F < 64 - d.in.W && (d.acc.S || !d.in.S)) {
     static const bool no_sat_free = getenv("ACDSP_NO_SAT_FREE") != nullptr;   // A/B knob
-    const unsigned __int128 xmax = d.in.S ? ((unsigned __int128)1 << (d.in.W - 1)) : (((unsigned __int128)1 << d.in.W) - 1);
-    const unsigned __int128 top = d.acc.S ? (((unsigned __int128)1 << (d.acc.W - 1)) - 1) : (((unsigned __int128)1 << d.acc.W) - 1);
-    sat_free = !no_sat_free && (((unsigned __int128)h->tbl_max_rounds * xmax) << (p.acc.F - p.in.F)) <= top;   // rounds < 2^63, xmax <= 2^64 - W .. : inside 128 bits
+    sat_free = !no_sat_free && sat_free_bound((unsigned __int128)h->tbl_max_rounds, d.in, d.acc, p.acc.F - p.in.F, 0, 0);
   }
   p.lossless = (d.acc.O == ACDSP_WRAP || sat_free) && p.acc.F >= p.in.F && p.acc.F - p.in.F < 64 - d.in.W;
   p.tile_ok = p.lossless && !h->pending && h->temp_zero && grp == n_blocks;
   if (p.tile_ok) { p.uni_rounds = h->tbl_uni_rounds; }
-  p.x = d_in; p.y = d_out; p.temp = h->d_temp[h->cur];
-  p.blk_off = h->d_blk; p.blk_rounds = h->d_blk + n_blocks; p.blk_out = h->d_blk + 2 * n_blocks; p.blk_chain = h->d_chain;
+  int64_t *const d_blk = h->d_blk.get<int64_t>();
+  p.x = d_in; p.y = d_out; p.temp = static_cast<const int64_t *>(h->temp.cur());
+  p.blk_off = d_blk; p.blk_rounds = d_blk + n_blocks; p.blk_out = d_blk + 2 * n_blocks; p.blk_chain = h->d_chain.get<int32_t>();
   bool temp_written = true;
-  hipError_t e = launch_intg_dump(p, h->d_temp[h->cur ^ 1], s, &temp_written, &h->last_path);
+  const int nxt = h->temp.next(false);
+  hipError_t e = launch_intg_dump(p, static_cast<int64_t *>(h->temp.at(nxt)), s, &temp_written, &h->last_path);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "intg_dump kernel launch failed: %s", hipGetErrorString(e)); }
-  if (temp_written) { h->cur ^= 1; }   // (else: nothing carried in, every block dumped -- the all-zero temp[] of this side stays the state)
+  if (temp_written) { h->temp.commit(nxt); }   // (else: nothing carried in, every block dumped -- the all-zero temp[] of this side stays the state)
   h->pending = start != (int32_t)n_blocks;   // the call ended on blocks that did not dump: their sums sit in temp[]
   if (temp_written) {
     // the general kernel wrote the next temp[]: non-zero while sums are pending; when every chain dumped it is zeroed HERE rather than trusted
     h->temp_zero = false;
     if (!h->pending) {
-      HIP_TRY(hipMemsetAsync(h->d_temp[h->cur], 0, (size_t)d.n_objects * d.chn * sizeof(int64_t), s));
+      HIP_TRY(hipMemsetAsync(h->temp.cur(), 0, h->temp.bytes(), s));
       h->temp_zero = true;
     }
   }
@@ -186,19 +173,8 @@ int32_t acdsp_intgdump_run_host(acdsp_intgdump_t h, const void *h_in, const int6
   if (n_blocks == 0) { return ACDSP_OK; }
   if ((ni > 0 && !h_in) || (no > 0 && (!h_out || out_cap < no))) { return fail(ACDSP_EINVAL, "intg_dump run_host: bad buffers"); }
   if ((rc = check_device(h->d.device))) { return rc; }
-  const int64_t si = ni > 0 ? ni : 1, so = no > 0 ? no : 1;
-  if ((rc = h->st.ensure((size_t)h->d.n_objects * si * h->in_eb, (size_t)h->d.n_objects * so * h->out_eb))) { return rc; }
-  if (ni > 0) {
-    HIP_TRY(hipMemcpy2D(h->st.d_in, (size_t)si * h->in_eb, h_in, (size_t)ni * h->in_eb, (size_t)ni * h->in_eb, (size_t)h->d.n_objects,
-                        hipMemcpyHostToDevice));
-  }
-  if ((rc = acdsp_intgdump_run(h, h->st.d_in, si, n_sample, n_blocks, h->st.d_out, so, nullptr, nullptr))) { return rc; }
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  if (no > 0) {
-    HIP_TRY(hipMemcpy2D(h_out, (size_t)out_cap * h->out_eb, h->st.d_out, (size_t)so * h->out_eb, (size_t)no * h->out_eb,
-                        (size_t)h->d.n_objects, hipMemcpyDeviceToHost));
-  }
-  return ACDSP_OK;
+  const HostRows r = {h->d.n_objects, h_in, ni, ni > 0 ? ni : 1, h->in_eb, h_out, no, no > 0 ? no : 1, out_cap, h->out_eb};
+  return run_host_staged(h->st, r, false, [&](const void *d_in, void *d_out, bool) { return acdsp_intgdump_run(h, d_in, r.si, n_sample, n_blocks, d_out, r.so, nullptr, nullptr); });
 }
 
 int32_t acdsp_intgdump_reset(acdsp_intgdump_t h) {
@@ -206,7 +182,7 @@ int32_t acdsp_intgdump_reset(acdsp_intgdump_t h) {
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < 2; i++) { HIP_TRY(hipMemset(h->d_temp[i], 0, (size_t)h->d.n_objects * h->d.chn * sizeof(int64_t))); }
+  if ((rc = h->temp.zero())) { return rc; }
   h->pending = false;
   h->temp_zero = true;
   return ACDSP_OK;
@@ -221,9 +197,9 @@ struct acdsp_mvavg {
   acdsp_mvavg_desc_t d;
   int in_eb, out_eb;
   bool coeffs_set = false;
-  int64_t *d_coeffs = nullptr;
+  DevBuf d_coeffs;
   std::vector<int64_t> h_coeffs;
-  uint32_t *d_frag = nullptr;   // matrix-core form of the streaming kernel: fragments of the coefficient set (mv_avg_build_frags)
+  DevBuf d_frag;                // matrix-core form of the streaming kernel: fragments of the coefficient set (mv_avg_build_frags)
   int frag_nb = 0;
   int64_t frag_csum = 0;
   int last_path = 0;
@@ -248,26 +224,18 @@ int32_t acdsp_mvavg_create(const acdsp_mvavg_desc_t *desc, acdsp_mvavg_t *out) {
   const int fc = desc->coeff.W - desc->coeff.I;
   if (desc->acc.W + desc->coeff.W + 2 + (fc < 0 ? -fc : 0) > 125) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: type combination needs more than 128-bit intermediates"); }
   if ((rc = check_device(desc->device))) { return rc; }
-  acdsp_mvavg *h = new acdsp_mvavg();
+  std::unique_ptr<acdsp_mvavg> h(new acdsp_mvavg());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   h->in_eb = elem_bytes(desc->in.W);
   h->out_eb = elem_bytes(desc->out.W);
-  if (hipMalloc((void **)&h->d_coeffs, (size_t)desc->taps * sizeof(int64_t)) != hipSuccess ||
-      hipMalloc((void **)&h->d_frag, (size_t)kMvAvgFragWords * sizeof(uint32_t)) != hipSuccess) {
-    if (h->d_coeffs) { (void)hipFree(h->d_coeffs); }
-    delete h;
-    return fail(ACDSP_EHIP, "mv_avg: coefficient allocation failed");
-  }
-  *out = h;
+  if ((rc = h->d_coeffs.alloc((size_t)desc->taps * sizeof(int64_t))) || (rc = h->d_frag.alloc((size_t)kMvAvgFragWords * sizeof(uint32_t)))) { return rc; }
+  *out = h.release();
   return ACDSP_OK;
 }
 
 int32_t acdsp_mvavg_destroy(acdsp_mvavg_t h) {
   if (!h) { return ACDSP_OK; }
   (void)hipSetDevice(h->d.device);
-  if (h->d_coeffs) { (void)hipFree(h->d_coeffs); }
-  if (h->d_frag) { (void)hipFree(h->d_frag); }
-  h->st.destroy();
   delete h;
   return ACDSP_OK;
 }
@@ -281,12 +249,12 @@ int32_t acdsp_mvavg_set_coeffs(acdsp_mvavg_t h, const int64_t *coeffs) {
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_coeffs, coeffs, (size_t)h->d.taps * sizeof(int64_t), hipMemcpyHostToDevice));
+  if ((rc = h->d_coeffs.upload(coeffs, (size_t)h->d.taps * sizeof(int64_t)))) { return rc; }
   h->h_coeffs.assign(coeffs, coeffs + h->d.taps);
   {
     std::vector<uint32_t> fr((size_t)kMvAvgFragWords, 0u);
     h->frag_nb = mv_avg_build_frags(coeffs, h->d.taps, h->d.win_mode, fr.data(), &h->frag_csum);
-    if (h->frag_nb > 0) { HIP_TRY(hipMemcpy(h->d_frag, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice)); }
+    if (h->frag_nb > 0 && (rc = h->d_frag.upload(fr.data(), fr.size() * sizeof(uint32_t)))) { return rc; }
   }
   h->coeffs_set = true;
   return ACDSP_OK;
@@ -327,17 +295,7 @@ int32_t acdsp_mvavg_run(acdsp_mvavg_t h, const void *d_in, int64_t in_stride, in
     static const bool no_sat_free = getenv("ACDSP_NO_SAT_FREE") != nullptr;   // A/B knob
     const int dc = p.acc.F - p.in.F, sh = p.cf.F, i_in = d.in.I + (d.in.S ? 0 : 1);
     if (!no_sat_free && dc >= 0 && dc < 40 && sh >= 0 && sh < 64 && d.acc.I >= i_in) {
-      unsigned __int128 sa = 0;
-      for (int64_t c : h->h_coeffs) { sa += (unsigned __int128)(c < 0 ? -(__int128)c : (__int128)c); }
-      const unsigned __int128 xmax = d.in.S ? ((unsigned __int128)1 << (d.in.W - 1)) : (((unsigned __int128)1 << d.in.W) - 1);
-      const unsigned __int128 top = ((unsigned __int128)1 << (d.acc.W - 1)) - 1;
-      unsigned __int128 b = sa * xmax;                     // sa < 2^74 (1025 taps of 64 bits), xmax <= 2^64: may leave 128 bits
-      if (sa == 0 || b / sa == xmax) {
-        if ((b >> (127 - dc)) == 0) {
-          b = ((b << dc) >> sh) + (unsigned __int128)h->h_coeffs.size() + 1;
-          if (b <= top) { p.acc.O = ACDSP_WRAP; }
-        }
-      }
+      if (sat_free_bound(sum_abs(h->h_coeffs.data(), h->h_coeffs.size()), d.in, d.acc, dc, sh, h->h_coeffs.size() + 1)) { p.acc.O = ACDSP_WRAP; }
     }
   }
   // order-free class: products (ACC_TYPE) w[j] * coeffs[j] inside 2^62.  The cast sample has at most min(W_acc, W_in + max(F_acc - F_in, 0))
@@ -359,8 +317,8 @@ int32_t acdsp_mvavg_run(acdsp_mvavg_t h, const void *d_in, int64_t in_stride, in
   p.fast = !p.force_generic && p.acc.O == ACDSP_WRAP && (d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && p.cf.F >= 0 &&
            p.cf.F < 62 && xbits + cbits <= 62;
   p.n_sample = n_sample; p.n_frames = n_frames; p.out_per_frame = opf; p.in_stride = in_stride; p.out_stride = out_stride;
-  p.x = d_in; p.y = d_out; p.coeffs = h->d_coeffs; p.h_coeffs = h->h_coeffs.data();
-  p.frag = h->frag_nb > 0 ? h->d_frag : nullptr; p.frag_nb = h->frag_nb; p.frag_csum = h->frag_csum;
+  p.x = d_in; p.y = d_out; p.coeffs = h->d_coeffs.get<int64_t>(); p.h_coeffs = h->h_coeffs.data();
+  p.frag = h->frag_nb > 0 ? h->d_frag.get<uint32_t>() : nullptr; p.frag_nb = h->frag_nb; p.frag_csum = h->frag_csum;
   hipError_t e = launch_mv_avg(p, (hipStream_t)stream, &h->last_path);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "mv_avg kernel launch failed: %s", hipGetErrorString(e)); }
   return ACDSP_OK;
@@ -377,15 +335,8 @@ int32_t acdsp_mvavg_run_host(acdsp_mvavg_t h, const void *h_in, int64_t n_sample
   if (!h_in || (no > 0 && (!h_out || out_cap < no))) { return fail(ACDSP_EINVAL, "mv_avg run_host: bad buffers"); }
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
-  const size_t nobj = (size_t)h->d.n_objects;
-  if ((rc = h->st.ensure(nobj * ni * h->in_eb, nobj * (no > 0 ? no : 1) * h->out_eb))) { return rc; }
-  HIP_TRY(hipMemcpy(h->st.d_in, h_in, nobj * ni * h->in_eb, hipMemcpyHostToDevice));
-  if ((rc = acdsp_mvavg_run(h, h->st.d_in, ni, n_sample, n_frames, h->st.d_out, no > 0 ? no : 1, nullptr, nullptr))) { return rc; }
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  if (no > 0) {
-    HIP_TRY(hipMemcpy2D(h_out, (size_t)out_cap * h->out_eb, h->st.d_out, (size_t)no * h->out_eb, (size_t)no * h->out_eb, nobj, hipMemcpyDeviceToHost));
-  }
-  return ACDSP_OK;
+  const HostRows r = {h->d.n_objects, h_in, ni, ni, h->in_eb, h_out, no, no > 0 ? no : 1, out_cap, h->out_eb};   // (rows stay packed on the device)
+  return run_host_staged(h->st, r, false, [&](const void *d_in, void *d_out, bool) { return acdsp_mvavg_run(h, d_in, r.si, n_sample, n_frames, d_out, r.so, nullptr, nullptr); });
 }
 
 }  // extern "C"

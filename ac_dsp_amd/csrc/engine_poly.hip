@@ -12,10 +12,8 @@ struct acdsp_polydec {
   int in_eb, out_eb, hl;
   bool lossless = false, coeffs_set = false, gen_ok = false;
   bool lossless_shape = false, sat_free = false;   // a saturating ACC_TYPE no partial sum of the current set can reach is a wrapping one (cf. acdsp_fir::sat_free)
-  void *d_hist[2] = {nullptr, nullptr};
-  int cur = 0;
-  int64_t *d_coeffs = nullptr;
-  uint32_t *d_gfrag = nullptr;
+  History hist;
+  DevBuf d_coeffs, d_gfrag;
   FirGenPlan gplan;
   int last_path = ACDSP_PATH_GENERIC;
   Staging st;
@@ -41,36 +39,24 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
     return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 128-bit intermediates");
   }
   if ((rc = check_device(desc->device))) { return rc; }
-  acdsp_polydec *h = new acdsp_polydec();
+  std::unique_ptr<acdsp_polydec> h(new acdsp_polydec());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   h->in_eb = elem_bytes(desc->in.W);
   h->out_eb = elem_bytes(desc->out.W);
   h->hl = round_up(desc->n_taps * desc->df + 15, 32);
   h->lossless_shape = fa >= fi + fc && fa - fi - fc < 64;
   h->lossless = h->lossless_shape && desc->acc.O == ACDSP_WRAP;
-  const size_t hb = (size_t)desc->n_channels * h->hl * h->in_eb;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = hipMalloc(&h->d_hist[i], hb);
-    if (e == hipSuccess) { e = hipMemset(h->d_hist[i], 0, hb); }
+  if ((rc = h->hist.init(desc->n_channels, h->hl, h->in_eb)) || (rc = h->d_coeffs.alloc((size_t)desc->n_taps * desc->df * sizeof(int64_t))) ||
+      (rc = h->d_gfrag.alloc(kGenFragWords * sizeof(uint32_t)))) {
+    return rc;
   }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_coeffs, (size_t)desc->n_taps * desc->df * sizeof(int64_t)); }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_gfrag, 3 * 8 * 64 * 4 * sizeof(uint32_t)); }
-  if (e != hipSuccess) {
-    acdsp_polydec_destroy(h);
-    return fail(ACDSP_EHIP, "poly_dec state allocation failed: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  *out = h.release();
   return ACDSP_OK;
 }
 
 int32_t acdsp_polydec_destroy(acdsp_polydec_t h) {
   if (!h) { return ACDSP_OK; }
   (void)hipSetDevice(h->d.device);
-  for (int i = 0; i < 2; i++) { if (h->d_hist[i]) { (void)hipFree(h->d_hist[i]); } }
-  if (h->d_coeffs) { (void)hipFree(h->d_coeffs); }
-  if (h->d_gfrag) { (void)hipFree(h->d_gfrag); }
-  h->st.destroy();
   delete h;
   return ACDSP_OK;
 }
@@ -86,33 +72,25 @@ int32_t acdsp_polydec_set_coeffs(acdsp_polydec_t h, const int64_t *coeffs) {
     if (coeffs[i] < cf.lo || coeffs[i] > cf.hi) { return fail(ACDSP_EINVAL, "coefficient %d = %lld is not a COEFF_TYPE raw word", i, (long long)coeffs[i]); }
   }
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_coeffs, coeffs, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+  if ((rc = h->d_coeffs.upload(coeffs, (size_t)n * sizeof(int64_t)))) { return rc; }
   h->gen_ok = false;
   {
     // |every partial sum of an output| <= sum|c| max|x| over all NTAPS * DF coefficients: inside the symmetric range of a signed saturating
     // ACC_TYPE the saturation never acts (ACDSP_NO_SAT_FREE: A/B knob)
     static const bool no_sat_free = getenv("ACDSP_NO_SAT_FREE") != nullptr;
-    bool sf = !no_sat_free && d.acc.O != ACDSP_WRAP && d.acc.S && h->lossless_shape && d.acc.W >= 2 && d.acc.W <= 64;
-    if (sf) {
-      const int ls = (d.acc.W - d.acc.I) - (d.in.W - d.in.I) - (d.coeff.W - d.coeff.I);
-      unsigned __int128 sa = 0;
-      for (int i = 0; i < n; i++) { sa += (unsigned __int128)(coeffs[i] < 0 ? -(__int128)coeffs[i] : (__int128)coeffs[i]); }
-      const unsigned __int128 xmax = d.in.S ? ((unsigned __int128)1 << (d.in.W - 1)) : (((unsigned __int128)1 << d.in.W) - 1);
-      const unsigned __int128 top = ((unsigned __int128)1 << (d.acc.W - 1)) - 1;
-      unsigned __int128 b = sa * xmax;
-      sf = (sa == 0 || b / sa == xmax) && (ls == 0 || (b >> (127 - ls)) == 0) && (b << ls) <= top;
-    }
+    const bool sf = !no_sat_free && d.acc.O != ACDSP_WRAP && d.acc.S && h->lossless_shape && d.acc.W >= 2 && d.acc.W <= 64 &&
+                    sat_free_bound(sum_abs(coeffs, (size_t)n), d.in, d.acc, (d.acc.W - d.acc.I) - (d.in.W - d.in.I) - (d.coeff.W - d.coeff.I), 0, 0);
     h->sat_free = sf;
     h->lossless = h->lossless_shape && (d.acc.O == ACDSP_WRAP || sf);
   }
   static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
-  if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !no_gen && (d.in.W + (d.in.S ? 0 : 1) + 7) / 8 <= h->in_eb) {
+  if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !no_gen && fits_container(d.in, h->in_eb)) {
     // decimating FIR  y[g] = sum_k hh[k] x[g*DF + DF-1 - k],  hh[df + tp*DF] = c[tp + NTAPS*df]
     std::vector<int64_t> hh((size_t)n, 0);
     for (int df = 0; df < d.df; df++) { for (int tp = 0; tp < d.n_taps; tp++) { hh[df + tp * d.df] = coeffs[tp + d.n_taps * df]; } }
     std::vector<uint32_t> fr;
     if (fir_gen_plan(hh.data(), n, d.df, (d.df - 1) % 16, &h->gplan, &fr)) {
-      HIP_TRY(hipMemcpy(h->d_gfrag, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      if ((rc = h->d_gfrag.upload(fr.data(), fr.size() * sizeof(uint32_t)))) { return rc; }
       h->gen_ok = true;
     }
   }
@@ -142,21 +120,21 @@ int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride
   k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl;
   k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
   k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in;
-  k.x = d_in; k.y = d_out; k.hist = h->d_hist[h->cur]; k.coeffs = h->d_coeffs;
+  k.x = d_in; k.y = d_out; k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>();
   const bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && in_stride >= (n_in + 15) / 16 * 16;
   hipError_t e;
   if (h->gen_ok && aligned) {
     h->last_path = ACDSP_PATH_MFMA_GEN;
-    e = launch_fir_gen(k, h->gplan, h->d_gfrag, 0, 0, d.df - 1, n_out, s);
+    e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, d.df - 1, n_out, s);
   } else {
     h->last_path = ACDSP_PATH_GENERIC;
     e = launch_polydec_generic(k, d.n_taps, d.df, n_out, s);
   }
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "poly_dec kernel launch failed: %s", hipGetErrorString(e)); }
-  const int nxt = hist_next_index(h->cur, k.n >= k.hl);
-  e = launch_fir_hist_update(k, h->d_hist[nxt], s);
+  const int nxt = h->hist.next(k.n >= k.hl);
+  e = launch_fir_hist_update(k, h->hist.at(nxt), s);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "poly_dec state kernel launch failed: %s", hipGetErrorString(e)); }
-  h->cur = nxt;
+  h->hist.commit(nxt);
   return ACDSP_OK;
 }
 
@@ -167,15 +145,8 @@ int32_t acdsp_polydec_run_host(acdsp_polydec_t h, const void *h_in, int64_t n_in
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   const int64_t n_out = n_in / h->d.df;
-  const int64_t si = (n_in + 15) / 16 * 16, so = (n_out + 7) / 8 * 8;
-  if ((rc = h->st.ensure((size_t)h->d.n_channels * si * h->in_eb, (size_t)h->d.n_channels * so * h->out_eb))) { return rc; }
-  HIP_TRY(hipMemcpy2D(h->st.d_in, (size_t)si * h->in_eb, h_in, (size_t)n_in * h->in_eb, (size_t)n_in * h->in_eb,
-                      (size_t)h->d.n_channels, hipMemcpyHostToDevice));
-  if ((rc = acdsp_polydec_run(h, h->st.d_in, si, n_in, h->st.d_out, so, nullptr))) { return rc; }
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  HIP_TRY(hipMemcpy2D(h_out, (size_t)n_out * h->out_eb, h->st.d_out, (size_t)so * h->out_eb, (size_t)n_out * h->out_eb,
-                      (size_t)h->d.n_channels, hipMemcpyDeviceToHost));
-  return ACDSP_OK;
+  const HostRows r = {h->d.n_channels, h_in, n_in, (n_in + 15) / 16 * 16, h->in_eb, h_out, n_out, (n_out + 7) / 8 * 8, n_out, h->out_eb};
+  return run_host_staged(h->st, r, false, [&](const void *d_in, void *d_out, bool) { return acdsp_polydec_run(h, d_in, r.si, n_in, d_out, r.so, nullptr); });
 }
 
 int32_t acdsp_polydec_reset(acdsp_polydec_t h) {
@@ -183,8 +154,7 @@ int32_t acdsp_polydec_reset(acdsp_polydec_t h) {
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < 2; i++) { HIP_TRY(hipMemset(h->d_hist[i], 0, (size_t)h->d.n_channels * h->hl * h->in_eb)); }
-  return ACDSP_OK;
+  return h->hist.zero();
 }
 
 }  // extern "C"
@@ -196,13 +166,12 @@ struct acdsp_polyintr {
   acdsp_polyintr_desc_t d;
   int in_eb, out_eb, hl;
   bool ctrl_set = false;
-  void *d_hist[2] = {nullptr, nullptr};
-  int64_t *d_saved[2] = {nullptr, nullptr};   // sums of the last sample, emitted by the next call (folded cores)
-  SideStream side;                            // head / tail kernels of a call beside its matrix-core kernel (fir_kernels.hpp)
-  int cur = 0;
+  History hist;            // (flips on every call: the saved sums flip with it)
+  DevBuf d_saved[2];       // sums of the last sample, emitted by the next call (folded cores); indexed like the history
+  SideStream side;         // head / tail kernels of a call beside its matrix-core kernel (fir_kernels.hpp)
   int64_t t_total = 0;
-  int64_t *d_coeffs = nullptr;
-  uint8_t *d_sign = nullptr, *d_corr = nullptr;
+  DevBuf d_coeffs, d_sign, d_corr;
+  ~acdsp_polyintr() { side.destroy(); }
   // exact-accumulation class on the matrix cores (fir_up.hip): folded per-phase taps of the current control words
   bool up_ok = false;
   bool acc64_ok = false;        // a 64-bit ACC_TYPE whose sums the current control words keep inside 62 bits: the exact-accumulation class applies
@@ -210,8 +179,7 @@ struct acdsp_polyintr {
   FirUpPlan up_plan;
   uint32_t up_shmask = 0;
   int64_t up_max_abs = -1;      // bound on |z| of the folded taps (enables the 32-bit epilogue)
-  uint32_t *d_upfrag = nullptr;
-  int64_t *d_upcorr = nullptr;
+  DevBuf d_upfrag, d_upcorr;
   int last_path = ACDSP_PATH_GENERIC;
   Staging st;
 };
@@ -272,17 +240,6 @@ extern "C" {
 int32_t acdsp_polyintr_destroy(acdsp_polyintr_t h) {
   if (!h) { return ACDSP_OK; }
   (void)hipSetDevice(h->d.device);
-  for (int i = 0; i < 2; i++) {
-    if (h->d_hist[i]) { (void)hipFree(h->d_hist[i]); }
-    if (h->d_saved[i]) { (void)hipFree(h->d_saved[i]); }
-  }
-  if (h->d_coeffs) { (void)hipFree(h->d_coeffs); }
-  if (h->d_sign) { (void)hipFree(h->d_sign); }
-  if (h->d_corr) { (void)hipFree(h->d_corr); }
-  if (h->d_upfrag) { (void)hipFree(h->d_upfrag); }
-  if (h->d_upcorr) { (void)hipFree(h->d_upcorr); }
-  h->st.destroy();
-  h->side.destroy();
   delete h;
   return ACDSP_OK;
 }
@@ -311,26 +268,16 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
     if (wp + (f - fp) > 125 || d.acc.W + (f - fa) > 125) { return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 128-bit intermediates"); }
   }
   if ((rc = check_device(d.device))) { return rc; }
-  acdsp_polyintr *h = new acdsp_polyintr();
+  std::unique_ptr<acdsp_polyintr> h(new acdsp_polyintr());   // (check_device has made the device current: a failure below frees there)
   h->d = d;
   h->in_eb = elem_bytes(d.in.W); h->out_eb = elem_bytes(d.out.W);
   h->hl = round_up(d.n_taps + 15, 32);
-  hipError_t e = hipSuccess;
-  const size_t hb = (size_t)d.n_channels * h->hl * h->in_eb, sb = (size_t)d.n_channels * d.ifac * sizeof(int64_t);
-  for (int i = 0; i < 2 && e == hipSuccess; i++) {
-    e = hipMalloc(&h->d_hist[i], hb);
-    if (e == hipSuccess) { e = hipMemset(h->d_hist[i], 0, hb); }
-    if (e == hipSuccess) { e = hipMalloc((void **)&h->d_saved[i], sb); }
-    if (e == hipSuccess) { e = hipMemset(h->d_saved[i], 0, sb); }   // acc_a / acc_b start at 0 (ac_poly_intr.h:117-118)
+  if ((rc = h->hist.init(d.n_channels, h->hl, h->in_eb))) { return rc; }
+  for (DevBuf &sv : h->d_saved) {
+    if ((rc = sv.alloc_zeroed((size_t)d.n_channels * d.ifac * sizeof(int64_t)))) { return rc; }   // acc_a / acc_b start at 0 (ac_poly_intr.h:117-118)
   }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_coeffs, (size_t)d.coeff_sz * sizeof(int64_t)); }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_sign, (size_t)d.ifac); }
-  if (e == hipSuccess) { e = hipMalloc((void **)&h->d_corr, (size_t)d.ifac); }
-  if (e != hipSuccess) {
-    acdsp_polyintr_destroy(h);
-    return fail(ACDSP_EHIP, "poly_intr state allocation failed: %s", hipGetErrorString(e));
-  }
-  *out = h;
+  if ((rc = h->d_coeffs.alloc((size_t)d.coeff_sz * sizeof(int64_t))) || (rc = h->d_sign.alloc((size_t)d.ifac)) || (rc = h->d_corr.alloc((size_t)d.ifac))) { return rc; }
+  *out = h.release();
   return ACDSP_OK;
 }
 
@@ -351,9 +298,10 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
     if (d.ftype != ACDSP_POLY_FOLD_ANTI && corr[j] >= d.ifac) { return fail(ACDSP_EINVAL, "corr[%d] = %d indexes outside the IF = %d accumulator banks", j, corr[j], d.ifac); }
   }
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->d_coeffs, coeffs, (size_t)d.coeff_sz * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_sign, sign, (size_t)d.ifac, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_corr, corr, (size_t)d.ifac, hipMemcpyHostToDevice));
+  if ((rc = h->d_coeffs.upload(coeffs, (size_t)d.coeff_sz * sizeof(int64_t))) || (rc = h->d_sign.upload(sign, (size_t)d.ifac)) ||
+      (rc = h->d_corr.upload(corr, (size_t)d.ifac))) {
+    return rc;
+  }
   h->ctrl_set = true;
   // matrix-core path: exact-accumulation class, int16 samples, control words that keep the cores linear, and an
   // accumulator that cannot wrap (the symmetric-pair halving (t1 -/+ t2) >> 1 does not commute with a wrap)
@@ -384,12 +332,7 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
         // |acc| <= sum|taps| * 2^(W_in - 1) << ls must stay inside ACC_TYPE; a pair sum then fits one more bit
         (sa << (d.in.W - 1 + ls)) < ((__int128)1 << ((d.acc.W < 64 ? d.acc.W : 63) - 1)) &&
         fir_up_plan(E.data(), d.ifac, nt, upx, &pl, &frag, &ucorr) && fir_up_shape_ok(h->in_eb, upx, pl.nb, d.ifac, h->out_eb)) {
-      if (h->d_upfrag) { (void)hipFree(h->d_upfrag); h->d_upfrag = nullptr; }
-      if (h->d_upcorr) { (void)hipFree(h->d_upcorr); h->d_upcorr = nullptr; }
-      HIP_TRY(hipMalloc((void **)&h->d_upfrag, frag.size() * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc((void **)&h->d_upcorr, ucorr.size() * sizeof(int64_t)));
-      HIP_TRY(hipMemcpy(h->d_upfrag, frag.data(), frag.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(h->d_upcorr, ucorr.data(), ucorr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+      if ((rc = h->d_upfrag.alloc_upload(frag)) || (rc = h->d_upcorr.alloc_upload(ucorr))) { return rc; }
       h->up_plan = pl; h->up_shmask = shm; h->up_ok = true; h->up_px = upx;
       {  // |z| <= max_j sum_k |E_j[k]| * 2^(W_in - 1)
         __int128 worst = 0;
@@ -442,8 +385,10 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
                  d.acc.I >= d.in.I + 1 && (d.acc.W <= 63 || h->acc64_ok) && (d.in.O == ACDSP_WRAP || d.in.O == ACDSP_SAT || d.in.O == ACDSP_SAT_SYM || d.in.O == ACDSP_SAT_ZERO);
   }
   p.in_stride = in_stride; p.out_stride = out_stride; p.n = n_in; p.n_out = no;
-  p.x = d_in; p.y = d_out; p.hist = h->d_hist[h->cur];
-  p.coeffs = h->d_coeffs; p.sign = h->d_sign; p.corr = h->d_corr; p.saved = h->d_saved[h->cur];
+  const int nxt = h->hist.next(false);   // (always the other buffer: the saved sums flip with it)
+  int64_t *const saved_next = h->d_saved[nxt].get<int64_t>();
+  p.x = d_in; p.y = d_out; p.hist = h->hist.cur();
+  p.coeffs = h->d_coeffs.get<int64_t>(); p.sign = h->d_sign.get<uint8_t>(); p.corr = h->d_corr.get<uint8_t>(); p.saved = h->d_saved[h->hist.index()].get<int64_t>();
   p.o_begin = 0; p.o_end = no;
   hipError_t e = hipSuccess;
   // Complete steps of 32 input slots go to the matrix-core kernel; the head (history, the saved sums of the previous call)
@@ -472,7 +417,7 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
       memset(&k, 0, sizeof k);
       k.n_ch = d.n_channels; k.in = p.in; k.cf = p.cf; k.acc = p.acc; k.out = p.out; k.in_eb = h->in_eb; k.out_eb = h->out_eb;
       k.lossless_shift = p.lossless_shift; k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in; k.x = d_in; k.y = d_out;
-      e = launch_fir_up(k, h->up_plan, h->up_px, h->d_upfrag, h->d_upcorr, 0, 0, 0, h->up_shmask, h->up_max_abs, slot_a, n_steps, out_off, s);
+      e = launch_fir_up(k, h->up_plan, h->up_px, h->d_upfrag.get<uint32_t>(), h->d_upcorr.get<int64_t>(), 0, 0, 0, h->up_shmask, h->up_max_abs, slot_a, n_steps, out_off, s);
       if (e == hipSuccess) {
         o_a = 16 * slot_a * L + out_off; o_b = 16 * (slot_a + 32 * n_steps) * L + out_off;
         h->last_path = ACDSP_PATH_MFMA_GEN;
@@ -486,16 +431,16 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
   if (o_b > o_a) {
     p.o_begin = 0; p.o_end = o_a;
     e = launch_polyintr(p, nullptr, vs);
-    if (e == hipSuccess) { p.o_begin = o_b; p.o_end = no; e = launch_polyintr(p, h->d_saved[h->cur ^ 1], vs); }
+    if (e == hipSuccess) { p.o_begin = o_b; p.o_end = no; e = launch_polyintr(p, saved_next, vs); }
   } else {
-    e = launch_polyintr(p, h->d_saved[h->cur ^ 1], s);
+    e = launch_polyintr(p, saved_next, s);
   }
   hipError_t eh = hipSuccess;
   if (e == hipSuccess) {
     FirParams k;
     memset(&k, 0, sizeof k);
     k.n_ch = d.n_channels; k.in = p.in; k.in_eb = h->in_eb; k.hl = h->hl; k.in_stride = in_stride; k.n = n_in; k.x = d_in; k.hist = p.hist;
-    eh = launch_fir_hist_update(k, h->d_hist[h->cur ^ 1], vs);   // (always the other buffer: the saved sums flip with it -- so it may run beside the main kernel too)
+    eh = launch_fir_hist_update(k, h->hist.at(nxt), vs);   // (never in place -- so it may run beside the main kernel too)
   }
   if (forked) {   // (always joined, used or not: an unjoined fork is an error under stream capture)
     const hipError_t ej = h->side.join(s);
@@ -503,7 +448,7 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
   }
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "poly_intr kernel launch failed: %s", hipGetErrorString(e)); }
   if (eh != hipSuccess) { return fail(ACDSP_EHIP, "poly_intr state kernel launch failed: %s", hipGetErrorString(eh)); }
-  h->cur ^= 1;
+  h->hist.commit(nxt);
   h->t_total += n_in;
   return ACDSP_OK;
 }
@@ -517,18 +462,8 @@ int32_t acdsp_polyintr_run_host(acdsp_polyintr_t h, const void *h_in, int64_t n_
   if (no > 0 && (!h_out || out_cap < no)) { return fail(ACDSP_EINVAL, "poly_intr run_host: output buffer too small"); }
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
-  const int64_t si = (n_in + 15) / 16 * 16, so = (no + 15) / 16 * 16 + 16;
-  if ((rc = h->st.ensure((size_t)h->d.n_channels * si * h->in_eb, (size_t)h->d.n_channels * so * h->out_eb))) { return rc; }
-  HIP_TRY(hipMemcpy2D(h->st.d_in, (size_t)si * h->in_eb, h_in, (size_t)n_in * h->in_eb, (size_t)n_in * h->in_eb,
-                      (size_t)h->d.n_channels, hipMemcpyHostToDevice));
-  int64_t got = 0;
-  if ((rc = acdsp_polyintr_run(h, h->st.d_in, si, n_in, h->st.d_out, so, &got, nullptr))) { return rc; }
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  if (got > 0) {
-    HIP_TRY(hipMemcpy2D(h_out, (size_t)out_cap * h->out_eb, h->st.d_out, (size_t)so * h->out_eb, (size_t)got * h->out_eb,
-                        (size_t)h->d.n_channels, hipMemcpyDeviceToHost));
-  }
-  return ACDSP_OK;
+  const HostRows r = {h->d.n_channels, h_in, n_in, (n_in + 15) / 16 * 16, h->in_eb, h_out, no, (no + 15) / 16 * 16 + 16, out_cap, h->out_eb};
+  return run_host_staged(h->st, r, false, [&](const void *d_in, void *d_out, bool) { return acdsp_polyintr_run(h, d_in, r.si, n_in, d_out, r.so, nullptr, nullptr); });
 }
 
 int32_t acdsp_polyintr_reset(acdsp_polyintr_t h) {
@@ -536,9 +471,9 @@ int32_t acdsp_polyintr_reset(acdsp_polyintr_t h) {
   int rc = check_device(h->d.device);
   if (rc) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(hipMemset(h->d_hist[i], 0, (size_t)h->d.n_channels * h->hl * h->in_eb));
-    HIP_TRY(hipMemset(h->d_saved[i], 0, (size_t)h->d.n_channels * h->d.ifac * sizeof(int64_t)));
+  if ((rc = h->hist.zero())) { return rc; }
+  for (DevBuf &sv : h->d_saved) {
+    if ((rc = sv.zero((size_t)h->d.n_channels * h->d.ifac * sizeof(int64_t)))) { return rc; }
   }
   h->t_total = 0;
   return ACDSP_OK;
