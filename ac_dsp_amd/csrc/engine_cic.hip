@@ -183,6 +183,38 @@ int64_t acdsp_cic_out_count(acdsp_cic_t h, int64_t n_in) {
   return p.q_end > lo ? p.q_end - lo : 0;
 }
 
+}  // extern "C"
+
+// What acdsp_cic_run refuses while its stream is capturing, decided before the call touches the stream or the handle (the two-kernel DDC asks
+// before its own first stream operation): calls whose host-side phase a replay would repeat, and decimator calls whose window phase has no
+// uploaded fir_gen plan yet -- the upload synchronises the stream.
+int acdsp::eng::cic_capture_check(const acdsp_cic *h, const void *d_in, int64_t in_stride, int64_t n_in) {
+  const acdsp_cic_desc_t &d = h->d;
+  if (d.interp) {
+    if (h->t_total == 0) {
+      return fail(ACDSP_ESTATE, "cic_run under graph capture: the interpolator's first call drops its start-up outputs and cannot be replayed; run it before capturing");
+    }
+    return ACDSP_OK;
+  }
+  if (n_in % d.R != 0) {
+    return fail(ACDSP_ESTATE, "cic_run under graph capture: n_in = %lld is not a multiple of R = %d (a replay would repeat the captured decimation phase)",
+                (long long)n_in, d.R);
+  }
+  const bool slots = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && in_stride >= (n_in + 15) / 16 * 16;
+  if (!slots) { return ACDSP_OK; }   // the recurrence kernel: no plan
+  const int fm = (int)(((d.R - h->t_total % d.R) % d.R) % 16);
+  int st = -1;
+  if (h->gen_ok) { st = h->gen.state(fm); }
+  if (st < 0 && h->c2_ok) { st = h->c2.state(fm); }
+  if (st == 0) {
+    return fail(ACDSP_ESTATE, "cic_run under graph capture: the matrix-core plan of window phase %d (t_total %% R = %lld) is not on the device yet and its upload "
+                "synchronises the stream; one eager call at that phase unlocks it (so does the eager call in front of the capture)", fm, (long long)(h->t_total % d.R));
+  }
+  return ACDSP_OK;
+}
+
+extern "C" {
+
 int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride,
                       int64_t *n_out, void *stream) {
   if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
@@ -195,15 +227,8 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   int rc = check_device(d.device);
   if (rc) { return rc; }
   hipStream_t s = (hipStream_t)stream;
-  if (stream_is_capturing(s)) {
-    if (!d.interp && n_in % d.R != 0) {
-      return fail(ACDSP_ESTATE, "cic_run under graph capture: n_in = %lld is not a multiple of R = %d (a replay would repeat the captured decimation phase)",
-                  (long long)n_in, d.R);
-    }
-    if (d.interp && h->t_total == 0) {
-      return fail(ACDSP_ESTATE, "cic_run under graph capture: the interpolator's first call drops its start-up outputs and cannot be replayed; run it before capturing");
-    }
-  }
+  const bool capturing = stream_is_capturing(s);
+  if (capturing && (rc = cic_capture_check(h, d_in, in_stride, n_in))) { return rc; }
   CicParams p;
   cic_window(h, n_in, &p);
   p.q_from = p.q_to = 0;
@@ -228,14 +253,23 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   bool use_gen = h->gen_ok && !d.interp && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
   const uint32_t *gfrag = nullptr, *c2frag = nullptr;
   const FirGenPlan *gpl = nullptr, *c2pl = nullptr;
+  const int fm = (int)(p.first % 16);
+  if (!capturing && (use_gen || (h->c2_ok && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16))) {
+    // plans of this call's window phase, of the next call's and of phase 0: a capture that follows finds them uploaded (cic_capture_check)
+    int fms[3];
+    decimator_phases(d.R, h->t_total, n_in, fms);
+    if (use_gen && (rc = h->gen.prepare(h->h_taps, d.R, fms, 3, s))) { return rc; }
+    const bool gen_all = use_gen && h->gen.state(fms[0]) == 1 && h->gen.state(fms[1]) == 1 && h->gen.state(fms[2]) == 1;
+    if (h->c2_ok && !gen_all && (rc = h->c2.prepare(h->c2_taps, h->c2_R1, fms, 3, s))) { return rc; }
+  }
   if (use_gen) {
-    if ((rc = h->gen.get(h->h_taps, d.R, (int)(p.first % 16), s, &gpl, &gfrag))) { return rc; }
+    h->gen.get(fm, &gpl, &gfrag);
     use_gen = gpl != nullptr;
   }
   // ... or in two stages (R = R1 R2, cic2.hip) where the one-stage window does not fit: complete chunks there, the ragged end on the recurrence kernel
   bool use_c2 = h->c2_ok && !use_gen && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
   if (use_c2) {
-    if ((rc = h->c2.get(h->c2_taps, h->c2_R1, (int)(p.first % 16), s, &c2pl, &c2frag))) { return rc; }
+    h->c2.get(fm, &c2pl, &c2frag);
     use_c2 = c2pl != nullptr;
   }
   const bool use_intr_fir = d.interp && h->d_taps && !h->wide;

@@ -231,33 +231,54 @@ class History {
 constexpr int kGenMaxPlanes = 3, kGenMaxBlocks = 8;
 constexpr size_t kGenFragWords = (size_t)kGenMaxPlanes * kGenMaxBlocks * 64 * 4;
 
-// fir_gen plans of one tap set for each window offset first % 16 (a decimator's calls start at any phase), built and uploaded on the first use
-// of a phase; the fragments share one device slab of 16.
+// fir_gen plans of one tap set for each window offset first % 16 (a decimator's calls start at any phase), built and uploaded by prepare();
+// the fragments share one device slab of 16.  The upload copies from pageable memory and synchronises the stream, which a capturing stream does
+// not allow: an eager call prepares its own phase, the phase of the call that follows it and phase 0 (where reset() leads), so that a capture
+// behind any eager call finds its plan, and get() itself never touches the stream.
 class PhasePlans {
  public:
   int init() { return frag_.alloc(16 * kGenFragWords * sizeof(uint32_t)); }
-  // *plan = the plan of phase `fm` and *frag its device fragments, or *plan = nullptr where the taps have no plan at that phase (the caller
-  // falls back or refuses: not an error here).  A non-zero return is a HIP failure.
-  int get(const std::vector<int64_t> &taps, int R, int fm, hipStream_t s, const FirGenPlan **plan, const uint32_t **frag) {
-    uint32_t *d = frag_.get<uint32_t>() + (size_t)fm * kGenFragWords;
-    *plan = nullptr;
-    if (!((have_ >> fm) & 1)) {
-      std::vector<uint32_t> fr;
-      if (!fir_gen_plan(taps.data(), (int)taps.size(), R, fm, &plan_[fm], &fr) || fr.size() > kGenFragWords) { return ACDSP_OK; }
-      HIP_TRY(hipMemcpyAsync(d, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-      HIP_TRY(hipStreamSynchronize(s));   // fr is a stack vector
-      have_ |= 1u << fm;
+  // 1: the plan of phase `fm` is on the device; -1: the taps have no plan at that phase; 0: not built yet
+  int state(int fm) const { return ((have_ >> fm) & 1) ? 1 : (((none_ >> fm) & 1) ? -1 : 0); }
+  // builds and uploads whichever of the phases fms[0..n) are still missing: copies on `s` and one synchronisation -- never under capture
+  int prepare(const std::vector<int64_t> &taps, int R, const int *fms, int n, hipStream_t s) {
+    std::vector<uint32_t> fr[3];   // (stack vectors: alive until the synchronisation below)
+    int n_up = 0;
+    uint32_t up = 0;
+    for (int i = 0; i < n && n_up < 3; i++) {
+      const int fm = fms[i];
+      if (state(fm) != 0 || ((up >> fm) & 1)) { continue; }
+      if (!fir_gen_plan(taps.data(), (int)taps.size(), R, fm, &plan_[fm], &fr[n_up]) || fr[n_up].size() > kGenFragWords) { none_ |= 1u << fm; continue; }
+      HIP_TRY(hipMemcpyAsync(frag_.get<uint32_t>() + (size_t)fm * kGenFragWords, fr[n_up].data(), fr[n_up].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+      up |= 1u << fm;
+      n_up++;
     }
-    *plan = &plan_[fm];
-    *frag = d;
+    if (up) {
+      HIP_TRY(hipStreamSynchronize(s));
+      have_ |= up;
+    }
     return ACDSP_OK;
+  }
+  // *plan = the prepared plan of phase `fm` and *frag its device fragments, or *plan = nullptr where there is none (state(fm) != 1)
+  void get(int fm, const FirGenPlan **plan, const uint32_t **frag) const {
+    const bool ok = state(fm) == 1;
+    *plan = ok ? &plan_[fm] : nullptr;
+    *frag = ok ? frag_.get<uint32_t>() + (size_t)fm * kGenFragWords : nullptr;
   }
 
  private:
   FirGenPlan plan_[16];
-  uint32_t have_ = 0;
+  uint32_t have_ = 0, none_ = 0;
   DevBuf frag_;   // [16][kGenFragWords]
 };
+
+// Window phases first % 16 an eager decimator call at input count `t_total` of `n_in` samples prepares (PhasePlans::prepare): its own, that of
+// the call behind it -- which may be the first one of a graph capture -- and phase 0
+inline void decimator_phases(int R, int64_t t_total, int64_t n_in, int fms[3]) {
+  fms[0] = (int)(((R - t_total % R) % R) % 16);
+  fms[1] = (int)(((R - (t_total + n_in) % R) % R) % 16);
+  fms[2] = 0;
+}
 
 // Buffers of the host-side calls (run_host_staged)
 struct Staging {
@@ -280,10 +301,16 @@ struct Staging {
     if (!pin_out) { HIP_TRY(hipHostMalloc(&pin_out, kPinBytes, hipHostMallocMapped)); }
     return ACDSP_OK;
   }
+  // acdsp_fir_run has used d_in under graph capture: the graph holds its address, so growing the image later keeps the old one in `retired`
+  // (allocated, unused, until the handle goes) instead of freeing it
+  bool captured = false;
+  std::vector<DevBuf> retired;
   int ensure(size_t bin, size_t bout) {
     int rc;
     if (bin > cap_in) {
       cap_in = 0;
+      if (captured && d_in) { retired.push_back(std::move(d_in)); }
+      captured = false;
       if ((rc = d_in.alloc(bin))) { return rc; }
       cap_in = bin;
     }
@@ -426,6 +453,8 @@ struct acdsp_ddc {
   // two-kernel mode: intermediate stream
   DevBuf d_mid;
   int64_t mid_cap = 0;
+  bool captured = false;         // a call of this handle has been recorded into a graph, which holds d_mid's address: growing the buffer
+  std::vector<DevBuf> retired;   // later (eager) keeps the old one here instead of freeing it
   Timer tm;
 };
 
@@ -433,6 +462,9 @@ namespace acdsp {
 namespace eng {
 // current reg_trans[] buffer of a use_rt handle
 inline int64_t *fir_rt_cur(const acdsp_fir *h) { return h->d_rt[h->rt_hybrid ? h->cur_rt : h->hist.index()].get<int64_t>(); }
+// refusals of acdsp_cic_run / acdsp_fir_run while the stream is capturing (ACDSP_ESTATE with the message set), else ACDSP_OK: no side effects
+int cic_capture_check(const acdsp_cic *h, const void *d_in, int64_t in_stride, int64_t n_in);
+int fir_capture_check(const acdsp_fir *h, const void *d_in, int64_t in_stride, int64_t n);
 // FIR helpers other families use (engine_fir.hip)
 std::vector<int64_t> effective_coeffs(const int64_t *c, int N, int ftype);
 int internal_ftype(int kind, int ftype);

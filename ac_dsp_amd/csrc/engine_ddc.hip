@@ -105,12 +105,24 @@ int32_t acdsp_ddc_run(acdsp_ddc_t h, const void *d_in, int64_t in_stride, int64_
   int rc = check_device(cd.device);
   if (rc) { return rc; }
   hipStream_t s = (hipStream_t)stream;
+  const bool capturing = stream_is_capturing(s);
   if (!h->fused) {
     // two kernels with the INT_TYPE stream in HBM between them
     const int64_t cap = (no + 15) / 16 * 16 + 16;
+    if (capturing) {
+      // everything either stage would refuse, and a buffer that had to grow, before the first stream operation of the call
+      if (cap > h->mid_cap) {
+        return fail(ACDSP_ESTATE, "ddc_run under graph capture: the intermediate buffer holds %lld samples per channel and this call needs %lld; "
+                    "run one eager call of at least this length before capturing", (long long)h->mid_cap, (long long)cap);
+      }
+      if ((rc = cic_capture_check(h->cic, d_in, in_stride, n_in)) || (rc = fir_capture_check(h->fir, h->d_mid.get(), h->mid_cap, no))) { return rc; }
+      h->captured = true;
+    }
     if (cap > h->mid_cap) {
       HIP_TRY(hipStreamSynchronize(s));
       h->mid_cap = 0;
+      // a captured graph has the old buffer's address in its kernel arguments: it stays allocated, unused, until the handle goes
+      if (h->captured && h->d_mid) { h->retired.push_back(std::move(h->d_mid)); }
       if ((rc = h->d_mid.alloc((size_t)cd.n_channels * cap * h->cic->out_eb))) { return rc; }
       h->mid_cap = cap;
     }
@@ -128,14 +140,24 @@ int32_t acdsp_ddc_run(acdsp_ddc_t h, const void *d_in, int64_t in_stride, int64_
     return fail(ACDSP_EUNSUPPORTED, "ddc_run (fused): rows must be 16-byte aligned and readable up to a multiple of 16 samples");
   }
   const int R = cd.R;
-  if (stream_is_capturing((hipStream_t)stream) && n_in % R != 0) {
+  if (capturing && n_in % R != 0) {
     return fail(ACDSP_ESTATE, "ddc_run under graph capture: n_in = %lld is not a multiple of R = %d (a replay would repeat the captured decimation phase)",
                 (long long)n_in, R);
   }
   const int64_t first = (R - h->t_total % R) % R;
+  const int fm = (int)(first % 16);
+  if (capturing && h->plansA.state(fm) == 0) {
+    return fail(ACDSP_ESTATE, "ddc_run under graph capture: the stage-A plan of window phase %d (t_total %% R = %lld) is not on the device yet and its upload "
+                "synchronises the stream; one eager call at that phase unlocks it (so does the eager call in front of the capture)", fm, (long long)(h->t_total % R));
+  }
+  if (!capturing) {
+    int fms[3];
+    decimator_phases(R, h->t_total, n_in, fms);
+    if ((rc = h->plansA.prepare(h->cic->h_taps, R, fms, 3, s))) { return rc; }
+  }
   const FirGenPlan *planA = nullptr;
   const uint32_t *fragA = nullptr;
-  if ((rc = h->plansA.get(h->cic->h_taps, R, (int)(first % 16), s, &planA, &fragA))) { return rc; }
+  h->plansA.get(fm, &planA, &fragA);
   if (!planA) { return fail(ACDSP_EUNSUPPORTED, "ddc_run (fused): decimator shape outside the fused kernel"); }
   FirParams pa, pb;
   memset(&pa, 0, sizeof pa); memset(&pb, 0, sizeof pb);

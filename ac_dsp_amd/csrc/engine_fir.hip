@@ -422,6 +422,40 @@ int32_t acdsp_fir_clone(acdsp_fir_t h, acdsp_fir_t *out) {
 int32_t acdsp_fir_path(acdsp_fir_t h) { return h ? h->path : -1; }
 int32_t acdsp_fir_kernel_class(acdsp_fir_t h) { return (h && h->coeffs_set) ? h->kclass : -1; }
 
+}  // extern "C"
+
+// Do the matrix-core kernels take the caller's rows as they are (acdsp_fir_run: else fir_gen reads an aligned staging image of them)?
+static bool fir_rows_aligned(const acdsp_fir *h, const void *d_in, int64_t in_stride, int64_t n) {
+  static const bool aligned_only = getenv("ACDSP_ALIGNED_ONLY") != nullptr;   // A/B knob: the round-2 behaviour
+  const int path = h->path;
+  bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) &&
+                 (path == ACDSP_PATH_MFMA_I8 || in_stride >= (n + 15) / 16 * 16);
+  if (!aligned && !aligned_only && path == ACDSP_PATH_MFMA_I8 && in_stride >= (n + 7) / 8 * 8) { aligned = true; }
+  return aligned;
+}
+
+// What acdsp_fir_run refuses while its stream is capturing, decided before the call touches the stream or the handle
+int acdsp::eng::fir_capture_check(const acdsp_fir *h, const void *d_in, int64_t in_stride, int64_t n) {
+  if (h->rt_hybrid) {
+    const int64_t m_rt = (int64_t)h->d.n_taps - 1 - h->rt_since;
+    if (m_rt > 0 && n > 0) {
+      return fail(ACDSP_ESTATE, "fir_run under graph capture: a TRANSPOSED filter within n_taps - 1 samples of a coefficient change keeps host-side state; run %lld more samples before capturing", (long long)m_rt);
+    }
+  }
+  const int path = h->path;
+  if (!h->wide && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) && !fir_rows_aligned(h, d_in, in_stride, n)) {
+    // rows the matrix-core kernels do not take as they are go through the aligned staging image, which is allocated on growth
+    const size_t need = (size_t)h->d.n_channels * ((n + 15) / 16 * 16) * h->in_eb;
+    if (need > h->st.cap_in) {
+      return fail(ACDSP_ESTATE, "fir_run under graph capture: these rows need the aligned staging image (%zu bytes, %zu allocated) and a captured call "
+                  "cannot allocate; run one eager call of this shape before capturing, or lay the rows out on 16-byte boundaries", need, h->st.cap_in);
+    }
+  }
+  return ACDSP_OK;
+}
+
+extern "C" {
+
 int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_t n, void *d_out, int64_t out_stride,
                       void *stream) {
   if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
@@ -434,6 +468,8 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   int rc = check_device(d.device);
   if (rc) { return rc; }
   hipStream_t s = (hipStream_t)stream;
+  const bool capturing = stream_is_capturing(s);
+  if (capturing && (rc = fir_capture_check(h, d_in, in_stride, n))) { return rc; }
   FirParams k;
   k.hist_next = nullptr; k.t_begin = 0; k.in_flip = 0;
   k.n_taps = d.n_taps; k.ftype = internal_ftype(d.kind, d.ftype); k.n_ch = d.n_channels; k.coeffs_per_channel = d.coeffs_per_channel;
@@ -451,9 +487,6 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   if (hyb) {
     m_rt = (int64_t)d.n_taps - 1 - h->rt_since;
     m_rt = m_rt < 0 ? 0 : (m_rt > n ? n : m_rt);
-    if (m_rt > 0 && stream_is_capturing(s)) {
-      return fail(ACDSP_ESTATE, "fir_run under graph capture: a TRANSPOSED filter within n_taps - 1 samples of a coefficient change keeps host-side state; run %lld more samples before capturing", (long long)m_rt);
-    }
   }
 
   int path = h->path;
@@ -486,13 +519,11 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     // samples costs +12 %, profiles/r3_unaligned.txt; the staging copy below -- hipMemcpy2DAsync of misaligned rows -- cost 6.4 ms
     // per 2 GB, 7 x the filter itself) as long as a row is readable up to the next multiple of 8 samples.  fir_gen still wants
     // whole aligned slots: rows that are not laid out that way are first copied, on the device, into an aligned staging image.
-    static const bool aligned_only = getenv("ACDSP_ALIGNED_ONLY") != nullptr;   // A/B knob: the round-2 behaviour
-    bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) &&
-                   (path == ACDSP_PATH_MFMA_I8 || in_stride >= (n + 15) / 16 * 16);
-    if (!aligned && !aligned_only && path == ACDSP_PATH_MFMA_I8 && in_stride >= (n + 7) / 8 * 8) { aligned = true; }
+    const bool aligned = fir_rows_aligned(h, d_in, in_stride, n);
     if (!aligned) {
       const int64_t si = (n + 15) / 16 * 16;
-      if ((rc = h->st.ensure((size_t)d.n_channels * si * h->in_eb, 0))) { return rc; }
+      if ((rc = h->st.ensure((size_t)d.n_channels * si * h->in_eb, 0))) { return rc; }   // (under capture: large enough already, fir_capture_check)
+      if (capturing) { h->st.captured = true; }
       HIP_TRY(hipMemcpy2DAsync(h->st.d_in.get(), (size_t)si * h->in_eb, d_in, (size_t)in_stride * h->in_eb, (size_t)n * h->in_eb,
                                (size_t)d.n_channels, hipMemcpyDeviceToDevice, s));
       k.x = h->st.d_in.get(); k.in_stride = si;

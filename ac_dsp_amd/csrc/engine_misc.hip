@@ -14,6 +14,8 @@ struct acdsp_intgdump {
   DevBuf d_blk;                 // int64 [3][cap] off / rounds / out
   DevBuf d_chain;               // int32 [cap]
   int64_t blk_cap = 0;
+  bool captured = false;        // a call of this handle has been recorded into a graph, which holds d_blk / d_chain: a later (eager) call with
+  std::vector<DevBuf> retired;  // another table keeps the old arrays here instead of freeing or overwriting them
   bool pending = false;         // the last call ended on a block that did not dump: temp[] is non-zero
   bool temp_zero = true;        // temp.cur() is known to be all zero (create / reset / zeroed behind a general-kernel call that dumped everything):
                                 // what the tile / stream kernels rely on when they leave temp[] alone (advisor, round 5)
@@ -88,15 +90,38 @@ int32_t acdsp_intgdump_run(acdsp_intgdump_t h, const void *d_in, int64_t in_stri
   const acdsp_intgdump_desc_t &d = h->d;
   if ((rc = check_device(d.device))) { return rc; }
   hipStream_t s = (hipStream_t)stream;
-  if (n_blocks > h->blk_cap) {
+  if (stream_is_capturing(s)) {
+    // A captured call only enqueues kernels: its block table is the one the preceding eager call on this stream uploaded, and it neither finds
+    // nor leaves sums in temp[] (pending / temp_zero and the temp[] ping-pong are host-side state that a replay would not repeat)
+    const bool same = n_blocks <= h->blk_cap && h->last_stream == stream && (int64_t)h->last_ns.size() == n_blocks &&
+                      memcmp(h->last_ns.data(), n_sample, (size_t)n_blocks * sizeof(int64_t)) == 0;
+    if (!same) {
+      return fail(ACDSP_ESTATE, "intg_dump run under graph capture: the n_sample table differs from that of the last call on this stream and its upload "
+                  "synchronises the stream; run one eager call with this table on the capture stream first");
+    }
+    if (h->pending) {
+      return fail(ACDSP_ESTATE, "intg_dump run under graph capture: sums of blocks that did not dump are pending in temp[], host-side state a replay "
+                  "would not repeat; capture from a call boundary behind a dump");
+    }
+    if (h->tbl_grp != n_blocks) {
+      return fail(ACDSP_ESTATE, "intg_dump run under graph capture: the call holds blocks that do not dump, whose sums a replay would not carry "
+                  "(host-side state); every block of a captured call must dump");
+    }
+    h->captured = true;
+  }
+  const bool same_table = n_blocks <= h->blk_cap && h->last_stream == stream && (int64_t)h->last_ns.size() == n_blocks &&
+                          memcmp(h->last_ns.data(), n_sample, (size_t)n_blocks * sizeof(int64_t)) == 0;
+  // A captured graph has the tables' addresses in its kernel arguments and replays with their contents: once a call of the handle has been
+  // captured, an (eager) call with another table gets device arrays of its own and the old ones stay allocated, untouched, until the handle goes
+  if (n_blocks > h->blk_cap || (h->captured && !same_table)) {
     HIP_TRY(hipStreamSynchronize(s));
     h->blk_cap = 0;
+    if (h->captured && h->d_blk) { h->retired.push_back(std::move(h->d_blk)); h->retired.push_back(std::move(h->d_chain)); }
+    h->captured = false;
     if ((rc = h->d_blk.alloc((size_t)3 * n_blocks * sizeof(int64_t))) || (rc = h->d_chain.alloc((size_t)n_blocks * sizeof(int32_t)))) { return rc; }
     h->blk_cap = n_blocks;
     h->last_ns.clear();   // new device arrays: the table has to be uploaded again
   }
-  const bool same_table = h->last_stream == stream && (int64_t)h->last_ns.size() == n_blocks &&
-                          memcmp(h->last_ns.data(), n_sample, (size_t)n_blocks * sizeof(int64_t)) == 0;
   if (!same_table) {
     std::vector<int64_t> blk((size_t)3 * n_blocks);
     std::vector<int32_t> chain((size_t)n_blocks);

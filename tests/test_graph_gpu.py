@@ -1,8 +1,11 @@
 """GPU tests: run() calls captured into a HIP graph (torch.cuda.CUDAGraph) and replayed.
 
 Small chunks are launch-bound (a 255-tap step over 256 ch x 4096 samples is ~10 us of GPU work behind two launches), so a
-streaming deployment captures a fixed schedule of run() calls once and replays it.  run() performs no
-allocation, synchronisation or host copy in steady state, so it is capturable; the handle's host-side bookkeeping must be
+streaming deployment captures a fixed schedule of run() calls once and replays it.  These tests compare the replays of four
+handles with an eager run of the same library; tests/test_graph_paths_gpu.py compares every family and kernel path with the CPU oracle and
+asserts what is refused.  While its stream is capturing, run() either only enqueues kernels or refuses the call (ACDSP_ESTATE, "graph
+capture") before it touches the stream or the handle: one-time uploads (matrix-core fragments per decimation phase, the integrate-and-dump
+block table) and buffer growth happen in eager calls in front of the capture.  The handle's host-side bookkeeping must be
 the same after the captured sequence as before it: calls of at least `hl` samples (the handle's history length: N_TAPS - 1
 rounded up to a multiple of 32, the window of the class for CIC / DDC) update the history in place, so any number of them
 qualifies; every captured decimator call must consume a multiple of the rate change (acdsp_cic_run / acdsp_ddc_run refuse other
