@@ -395,6 +395,10 @@ struct acdsp_fir {
   FirMfmaPlan plan;             // worst case over the coefficient sets (bounds for the epilogue choice)
   bool mfma_ok = false;
   int mfma_cshift = 0;          // the fragments hold the coefficients scaled by 2^mfma_cshift (narrow types: engine_fir.hip, set_coeffs)
+  // 1026 .. 16384 taps (fir_long.hip): long_shape = the descriptor is long-eligible (create), long_ok = the current set runs there; d_frag /
+  // d_corr hold its fragments
+  bool long_shape = false, long_ok = false;
+  FirLongPlan lplan;
   DevBuf d_gfrag;               // fragments of the generalised (wide-input) MFMA kernel
   FirGenPlan gplan;
   bool gen_ok = false;

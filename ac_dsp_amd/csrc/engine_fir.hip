@@ -66,6 +66,34 @@ namespace {
 
 inline bool is_fold_odd(int ift) { return ift == ACDSP_FOLD_ODD || ift == kRsFoldOdd || ift == kRsFoldOddAnti; }
 
+// the exact-sum shape of a descriptor, the overflow mode of ACC_TYPE left out: `sum << (fa - fi - fc)` in 64 bits, so the shift must be
+// 0..63 (formats with I outside [0, W] can ask for more: those stay on the per-tap path)
+bool fir_exact_shape(const acdsp_fir_desc_t &d) {
+  const int fi = d.in.W - d.in.I, fc = d.coeff.W - d.coeff.I, fa = d.acc.W - d.acc.I;
+  bool ok = fa >= fi + fc && fa - fi - fc < 64;
+  const int ift = internal_ftype(d.kind, d.ftype);
+  if (is_fold_odd(ift)) {
+    // the ACC_TYPE `fold` must also keep every fraction bit of the pre-add (fc < 0 would let fa >= fi + fc pass with fa < fi)
+    ok = ok && fa >= fi;
+    // the ACC_TYPE `fold` variable must hold x[i] +/- x[N-1-i] without wrapping (a difference needs a signed type)
+    const int need_i = d.in.I + 1 + ((d.acc.S && !d.in.S) ? 1 : 0);
+    ok = ok && d.acc.I >= need_i && (d.acc.S || (!d.in.S && ift != kRsFoldOddAnti));
+  }
+  return ok;
+}
+
+// Long filters (kFirLongMinTaps .. kFirLongMaxTaps, fir_long.hip): the condition a descriptor fails, or nullptr when it is long-eligible
+const char *fir_long_refusal(const acdsp_fir_desc_t &d) {
+  if (d.coeffs_per_channel) { return "one coefficient set per channel"; }
+  if (d.flags & ACDSP_FLAG_FORCE_GENERIC) { return "ACDSP_FLAG_FORCE_GENERIC (the exact-order kernels end at 2048 taps)"; }
+  if (d.in.W > 16) { return "IN_TYPE wider than 16 bits"; }
+  if (d.coeff.S ? d.coeff.W > 16 : d.coeff.W > 15) { return "COEFF_TYPE wider than 16 bits signed / 15 bits unsigned"; }
+  if (d.acc.W > 64 || d.out.W > 64) { return "ACC_TYPE or OUT_TYPE wider than 64 bits"; }
+  if (d.ftype == ACDSP_TRANSPOSED && d.kind != ACDSP_FIR_CONST) { return "TRANSPOSED with loadable coefficients (carried reg_trans partial sums)"; }
+  if (!fir_exact_shape(d)) { return "ACC_TYPE is not an exact-sum accumulator (F_acc >= F_in + F_coeff, shift below 64; FOLD_ODD: the pre-add must fit too)"; }
+  return nullptr;
+}
+
 int fir_validate(const acdsp_fir_desc_t &d) {
   if (d.kind < ACDSP_FIR_CONST || d.kind > ACDSP_FIR_REG_SHARE) { return fail(ACDSP_EINVAL, "bad FIR class %d", d.kind); }
   if (d.ftype < 0 || d.ftype > ACDSP_FOLD_ODD_ANTI) { return fail(ACDSP_EINVAL, "bad ftype %d", d.ftype); }
@@ -74,7 +102,7 @@ int fir_validate(const acdsp_fir_desc_t &d) {
                     ? "ac_fir_reg_share::run() has no branch for this FTYPE (output would be an unassigned value)"
                     : "FOLD_*_ANTI: the reference run() has no branch for these (output is an unassigned value)");
   }
-  if (d.n_taps < 1 || d.n_taps > 2048) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d outside 1..2048", d.n_taps); }
+  if (d.n_taps < 1 || d.n_taps > kFirLongMaxTaps) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d outside 1..%d", d.n_taps, kFirLongMaxTaps); }
   if (d.n_channels < 1) { return fail(ACDSP_EINVAL, "n_channels=%d must be positive", d.n_channels); }
   if (d.n_channels > 65535) { return fail(ACDSP_EUNSUPPORTED, "n_channels=%d outside 1..65535", d.n_channels); }
   int rc;
@@ -97,6 +125,10 @@ int fir_validate(const acdsp_fir_desc_t &d) {
     return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 256-bit intermediates");
   }
   if (wide && d.kind == ACDSP_FIR_REG_SHARE) { return fail(ACDSP_EUNSUPPORTED, "ac_fir_reg_share: ACC / OUT wider than 64 bits not supported"); }
+  // more than 2048 taps: the long matrix-core kernel or nothing
+  if (d.n_taps > 2048) {
+    if (const char *why = fir_long_refusal(d)) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: more than 2048 taps run on the long matrix-core kernel only, which does not take %s", d.n_taps, why); }
+  }
   return ACDSP_OK;
 }
 
@@ -129,16 +161,11 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   static const bool no_hybrid = getenv("ACDSP_NO_RT_HYBRID") != nullptr;   // A/B knob: reg_trans on the exact-order kernel for every sample
   h->rt_hybrid = h->use_rt && !no_hybrid && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) && (desc->in.S || desc->in.W <= 15) && desc->acc.O == ACDSP_WRAP && fa >= fi + fc && fa - fi - fc < 64 && !h->wide;
   h->rt_since = desc->n_taps - 1;   // an all-zero state carries no coefficients
-  bool lossless = fa >= fi + fc && fa - fi - fc < 64 && (!h->use_rt || h->rt_hybrid) && !h->wide;   // (the overflow mode: below)
-  const int ift = internal_ftype(desc->kind, desc->ftype);
-  if (is_fold_odd(ift)) {
-    // the ACC_TYPE `fold` must also keep every fraction bit of the pre-add (fc < 0 would let fa >= fi + fc pass with fa < fi)
-    lossless = lossless && fa >= fi;
-    // the ACC_TYPE `fold` variable must hold x[i] +/- x[N-1-i] without wrapping (a difference needs a signed type)
-    int need_i = desc->in.I + 1 + ((desc->acc.S && !desc->in.S) ? 1 : 0);
-    lossless = lossless && desc->acc.I >= need_i && (desc->acc.S || (!desc->in.S && ift != kRsFoldOddAnti));
-  }
+  const bool lossless = fir_exact_shape(*desc) && (!h->use_rt || h->rt_hybrid) && !h->wide;   // (the overflow mode: below)
   h->lossless_shape = lossless;
+  h->long_shape = desc->n_taps >= kFirLongMinTaps && fir_long_refusal(*desc) == nullptr;
+  // the long kernel's first step reaches 32 (NB - 1) samples back, NB = ceil((n_taps - 1) / 32) + 1
+  if (h->long_shape && h->hl < 32 * ((desc->n_taps - 1 + 31) / 32)) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
   h->sat_free = false;
   h->lossless = lossless && desc->acc.O == ACDSP_WRAP;
   h->coeffs_set = false;
@@ -249,7 +276,7 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
     h->lossless = h->lossless_shape && (d.acc.O == ACDSP_WRAP || sf);
   }
   static const bool no_flip = getenv("ACDSP_NO_UNSIGNED16") != nullptr;   // A/B knob: unsigned 16-bit samples stay on the exact-sum VALU kernel
-  const bool flip = !d.in.S && d.in.W == 16 && !no_flip && !h->use_rt;
+  const bool flip = !d.in.S && d.in.W == 16 && (!no_flip || h->long_shape) && !h->use_rt;   // (the long kernel has no other way to take them)
   const bool i16_in = d.in.W <= 15 || (d.in.W == 16 && (d.in.S || flip));
   const bool i16_cf = d.coeff.S ? d.coeff.W <= 16 : d.coeff.W <= 15;
   if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && i16_in && i16_cf && h->in_eb == 2 &&
@@ -317,10 +344,37 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
       h->in_flip = flip;
     }
   }
+  // 1026 .. 16384 taps: the same split on the long kernel (fir_long.hip), whatever the epilogue class.  Above 2048 taps nothing else exists:
+  // a set that cannot go there is refused, and the handle stays without a set.
+  h->long_ok = false;
+  if (h->long_shape) {
+    if (!h->lossless) {
+      if (d.n_taps > 2048) {
+        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", d.n_taps);
+      }
+    } else {
+      const std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
+      std::vector<uint32_t> frag;
+      FirLongPlan lp;
+      if (fir_long_plan(eff.data(), d.n_taps, &lp, &frag)) {
+        if (flip) {   // + 32768 * sum(c): the samples go through the kernel as x - 32768
+          int64_t sc = 0;
+          for (int64_t v : eff) { sc += v; }
+          lp.corr += 32768 * sc;
+        }
+        if ((rc = h->d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = h->d_corr.upload(&lp.corr, sizeof(int64_t)))) { return rc; }
+        h->lplan = lp;
+        h->long_ok = true;
+        h->in_flip = flip;
+      } else if (d.n_taps > 2048) {
+        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: a coefficient of 32640 or more cannot be split into two signed bytes, and more than 2048 taps run on the matrix cores only", d.n_taps);
+      }
+    }
+  }
   // wide inputs (more than 16 bits) / other misses of the int16 kernel: generalised multi-plane MFMA kernel
   h->gen_ok = false;
   static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
-  if (!h->mfma_ok && h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel && !no_gen &&
+  if (!h->mfma_ok && !h->long_ok && h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel && !no_gen &&
       fits_container(d.in, h->in_eb)) {
     std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
     std::vector<uint32_t> gfrag;
@@ -387,6 +441,7 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
     }
   }
   h->path = h->wide ? ACDSP_PATH_WIDE
+            : h->long_ok ? ACDSP_PATH_MFMA_LONG
             : h->mfma_ok ? ACDSP_PATH_MFMA_I8
             : h->gen_ok ? ACDSP_PATH_MFMA_GEN
             : h->lz_ok ? ACDSP_PATH_MFMA_LOSSY
@@ -429,8 +484,8 @@ static bool fir_rows_aligned(const acdsp_fir *h, const void *d_in, int64_t in_st
   static const bool aligned_only = getenv("ACDSP_ALIGNED_ONLY") != nullptr;   // A/B knob: the round-2 behaviour
   const int path = h->path;
   bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) &&
-                 (path == ACDSP_PATH_MFMA_I8 || in_stride >= (n + 15) / 16 * 16);
-  if (!aligned && !aligned_only && path == ACDSP_PATH_MFMA_I8 && in_stride >= (n + 7) / 8 * 8) { aligned = true; }
+                 (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || in_stride >= (n + 15) / 16 * 16);
+  if (!aligned && !aligned_only && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG) && in_stride >= (n + 7) / 8 * 8) { aligned = true; }
   return aligned;
 }
 
@@ -443,7 +498,7 @@ int acdsp::eng::fir_capture_check(const acdsp_fir *h, const void *d_in, int64_t 
     }
   }
   const int path = h->path;
-  if (!h->wide && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) && !fir_rows_aligned(h, d_in, in_stride, n)) {
+  if (!h->wide && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) && !fir_rows_aligned(h, d_in, in_stride, n)) {
     // rows the matrix-core kernels do not take as they are go through the aligned staging image, which is allocated on growth
     const size_t need = (size_t)h->d.n_channels * ((n + 15) / 16 * 16) * h->in_eb;
     if (need > h->st.cap_in) {
@@ -505,7 +560,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     return ACDSP_OK;
   }
   FirParams kraw = k;   // the state kernels always see the caller's samples
-  const bool flipped = h->in_flip && path == ACDSP_PATH_MFMA_I8;
+  const bool flipped = h->in_flip && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG);
   if (flipped) {
     // unsigned 16-bit samples: the kernel flips the top bit of every sample as it splits the rows and the history into byte planes
     // (FirParams::in_flip; round 4 and the first half of round 5 wrote a flipped image of both first: a second pass over the call's input,
@@ -513,7 +568,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     k.in_flip = 1;
     k.in.S = 1; k.in.lo = -32768; k.in.hi = 32767;
   }
-  if (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) {
+  if (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) {
     // The matrix-core kernels read rows with 16-byte vector loads (fir_gen: in whole 16-sample slots).  gfx950 serves a vector
     // access at any ELEMENT-aligned address, so the int8 kernel takes unaligned rows as they are (round 3: a row stride of 2^20 + 3
     // samples costs +12 %, profiles/r3_unaligned.txt; the staging copy below -- hipMemcpy2DAsync of misaligned rows -- cost 6.4 ms
@@ -543,6 +598,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     km.cf.F += h->mfma_cshift; km.lossless_shift -= h->mfma_cshift;
     e = launch_fir_mfma(km, h->plan, d.coeffs_per_channel, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s);
   }
+  else if (path == ACDSP_PATH_MFMA_LONG) { e = launch_fir_long(k, h->lplan, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s); }
   else if (path == ACDSP_PATH_MFMA_GEN) { e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, 0, n, s); }
   else if (path == ACDSP_PATH_MFMA_LOSSY) {
     // complete chunks on the matrix cores, the ragged rest (and calls shorter than a chunk) on the exact-order kernel
@@ -641,6 +697,8 @@ int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples) {
   *per_1024_samples = 0;
   if (h->path == ACDSP_PATH_MFMA_I8) {
     *per_1024_samples = fir_mfma_issued_per_step(fir_class_params(h, h->mfma_cshift), h->plan);
+  } else if (h->path == ACDSP_PATH_MFMA_LONG) {
+    *per_1024_samples = fir_long_issued_per_step(h->lplan);
   }
   return ACDSP_OK;
 }

@@ -52,6 +52,8 @@ struct FirMfmaPlan {
 // Builds the per-lane A fragments (host side) into frag[2][nb][64][4] dwords; returns false if the
 // coefficient set cannot be split into two signed bytes per tap.
 bool fir_mfma_build_fragments(const int64_t *coeffs, int n_taps, FirMfmaPlan *plan, uint32_t *frag /* host */);
+// ... for a plan of nb K-blocks of any count (fir_long.hip; hi_mask / lo_mask cover the first 64 blocks only)
+bool fir_mfma_build_fragments_nb(const int64_t *coeffs, int n_taps, int nb, FirMfmaPlan *plan, uint32_t *frag /* host */);
 int fir_mfma_plan_blocks_padded(int n_taps);   // the same with the padding applied regardless of the ACDSP_NO_MID knob (state geometry)
 int fir_mfma_plan_blocks(int n_taps);   // K-blocks of the plan (258 - 513 taps: padded to an odd count, fir_mfma.hip)
 int fir_mfma_max_blocks();       // K-blocks the MFMA path can take at all (A fragments in LDS): 33 -> 1025 taps
@@ -63,6 +65,18 @@ int fir_mfma_epilogue_class(const FirParams &p, const FirMfmaPlan &plan);   // 0
 bool fir_mfma_register_resident(const FirParams &p, const FirMfmaPlan &plan);   // fragments in registers: per-channel coefficient sets allowed
 hipError_t launch_fir_mfma(const FirParams &p, const FirMfmaPlan &plan, int frag_per_channel, const uint32_t *d_frag,
                            const int64_t *d_corr, hipStream_t s);
+
+// Long filters (1026 .. 16384 taps) of the same int8-split formulation (fir_long.hip): 34 .. 513 K-blocks, walked in LDS segments
+constexpr int kFirLongMinTaps = 1026, kFirLongMaxTaps = 16384;
+struct FirLongPlan {
+  int32_t nb;                  // K-blocks = ceil((n_taps-1)/32) + 1, never padded
+  int32_t hb0, hb1;            // K-blocks [hb0, hb1] hold every non-zero high coefficient byte (hb0 > hb1: the set has none)
+  int64_t corr;                // 128 * sum(c)
+};
+// host: fragments frag[2][nb][64][4] and the plan; false if a coefficient cannot be split into two signed bytes
+bool fir_long_plan(const int64_t *coeffs, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag);
+int fir_long_issued_per_step(const FirLongPlan &plan);   // two low-plane products per K-block + two per K-block of [hb0, hb1]
+hipError_t launch_fir_long(const FirParams &p, const FirLongPlan &plan, const uint32_t *d_frag, const int64_t *d_corr, hipStream_t s);
 
 // Generalised exact FIR on the matrix cores (fir_gen.hip): wide inputs / coefficients, decimation.
 // FirParams::ftype values of the ac_fir_reg_share cores (ascending MAC order, anti-symmetric folds:

@@ -94,6 +94,10 @@ int fir_mfma_plan_blocks(int n_taps) {
 bool fir_mfma_build_fragments(const int64_t *c, int n_taps, FirMfmaPlan *plan, uint32_t *frag) {
   const int nb = fir_mfma_plan_blocks(n_taps);
   if (nb > kMaxNB) { return false; }
+  return fir_mfma_build_fragments_nb(c, n_taps, nb, plan, frag);
+}
+
+bool fir_mfma_build_fragments_nb(const int64_t *c, int n_taps, int nb, FirMfmaPlan *plan, uint32_t *frag) {
   std::vector<int8_t> chi(n_taps), clo(n_taps);
   int64_t sum = 0, sa = 0, sah = 0, sal = 0;
   for (int k = 0; k < n_taps; k++) {
@@ -128,7 +132,7 @@ bool fir_mfma_build_fragments(const int64_t *c, int n_taps, FirMfmaPlan *plan, u
           frag[(((size_t)pl * nb + b) * 64 + lane) * 4 + dw] = word;
         }
       }
-      if (any) { (pl == 0 ? plan->hi_mask : plan->lo_mask) |= uint64_t(1) << b; }
+      if (any && b < 64) { (pl == 0 ? plan->hi_mask : plan->lo_mask) |= uint64_t(1) << b; }
     }
   }
   return true;

@@ -250,7 +250,7 @@ class Fir:
         return a.value, m.value
 
     def mfma_issued(self):
-        """32x32x32 int8 MFMAs the selected kernel issues per 1024 samples of one channel (0 off the int8 matrix-core path)."""
+        """32x32x32 int8 MFMAs the selected kernel issues per 1024 samples of one channel (0 off the "mfma_i8" and "mfma_long" paths)."""
         v = C.c_int32()
         check(lib.acdsp_fir_mfma_issued(self._h, C.byref(v)))
         return v.value

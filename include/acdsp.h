@@ -66,7 +66,9 @@ enum {
 enum { ACDSP_PATH_GENERIC = 0, ACDSP_PATH_LOSSLESS64 = 1, ACDSP_PATH_MFMA_I8 = 2, ACDSP_PATH_MFMA_GEN = 3,
        ACDSP_PATH_WIDE = 4 /* a format wider than 64 bits: exact-order kernels on 128-bit words, 256-bit intermediates */,
        ACDSP_PATH_MFMA_LOSSY = 5 /* lossy wrapping accumulator (per-tap AC_TRN / AC_RND): exact sum on the matrix cores minus the dropped bits */,
-       ACDSP_PATH_CIC_2STAGE = 6 /* ac_cic_dec_full with R = R1 R2: FIR identity of rate R1 on the matrix cores, integrators / combs of rate R2 behind it, one launch */ };
+       ACDSP_PATH_CIC_2STAGE = 6 /* ac_cic_dec_full with R = R1 R2: FIR identity of rate R1 on the matrix cores, integrators / combs of rate R2 behind it, one launch */,
+       ACDSP_PATH_MFMA_LONG = 8 /* 1026 .. 16384 taps of the exact-sum class on 16-bit types: the int8 split of ACDSP_PATH_MFMA_I8 with the coefficient
+                                  * fragments walked in LDS segments (7 is ACDSP_KCLASS_SATACC16 in the value space of acdsp_fir_kernel_class) */ };
 /* finer: the kernel family inside ACDSP_PATH_GENERIC (acdsp_fir_kernel_class; the other values equal the path) */
 enum { ACDSP_KCLASS_LOSSY16 = 6 /* fir_lossy_kernel: class B on 16-bit types, int32 VALU */,
        ACDSP_KCLASS_SATACC16 = 7 /* fir_satacc_kernel: saturating accumulator of <= 32 bits on 16-bit types, reference tap order */ };
@@ -74,7 +76,9 @@ enum { ACDSP_KCLASS_LOSSY16 = 6 /* fir_lossy_kernel: class B on 16-bit types, in
 typedef struct {
   int32_t kind;               /* ACDSP_FIR_*: which reference class this mirrors (informational) */
   int32_t ftype;              /* ACDSP_SHIFT_REG ... */
-  int32_t n_taps;
+  int32_t n_taps;             /* 1 .. 2048 for every class; 2049 .. 16384 only for descriptors the long matrix-core kernel takes (one shared
+                               * coefficient set, 16-bit samples and coefficients, exact-sum ACC_TYPE of <= 64 bits, no carried reg_trans:
+                               * INTEGRATION.md "Long filters"), else acdsp_fir_create fails with ACDSP_EUNSUPPORTED */
   int32_t n_channels;
   int32_t coeffs_per_channel; /* 0: one coefficient set shared by all channels, 1: one set per channel */
   acdsp_fmt_t in, coeff, acc, out;
@@ -220,7 +224,9 @@ int32_t acdsp_fir_clone(acdsp_fir_t h, acdsp_fir_t *out);
 /* Raw coefficient words from host memory: [n_taps] or [n_channels][n_taps].
  * const_coeffs: call once (the reference borrows the pointer for the object's
  * life); load_coeffs: the coefficient-load phase of run(); prog_coeffs: before
- * every run().  Takes effect for samples processed by later run() calls. */
+ * every run().  Takes effect for samples processed by later run() calls.
+ * More than 2048 taps have no fallback kernel: ACDSP_EUNSUPPORTED when a coefficient is >= 32640 (not two signed
+ * bytes) or when a saturating ACC_TYPE cannot be proven saturation-free for the set; the handle is then without a set. */
 int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs);
 /* Filter n_samples per channel.  d_in / d_out are device pointers to IN / OUT
  * containers, strides in elements.  Asynchronous on `stream` (a hipStream_t, or
@@ -244,7 +250,7 @@ int32_t acdsp_fir_last_kernel_ms(acdsp_fir_t h, float *ms);
 /* Average / minimum main-kernel duration over the last `last_k` (<= 64) run() calls. */
 int32_t acdsp_fir_kernel_stats(acdsp_fir_t h, int32_t last_k, float *avg_ms, float *min_ms);
 /* 32x32x32 int8 MFMA instructions the selected kernel issues per 1024 samples of one channel (0 when the current
- * coefficients do not run on the int8 matrix-core path): the numerator of an MFMA-utilisation figure.  All-zero
+ * coefficients run on neither ACDSP_PATH_MFMA_I8 nor ACDSP_PATH_MFMA_LONG): the numerator of an MFMA-utilisation figure.  All-zero
  * high-byte blocks of the coefficient set are not issued, so this is <= 4 * (ceil((n_taps - 1) / 32) + 1). */
 int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples);
 

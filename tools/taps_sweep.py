@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/taps_sweep.py [dense] -- the int8 MFMA FIR over the tap count (1024 ch x 2^20 samples, <16,2> types, OUT <16,2,RND,SAT>): ms per
-launch, the kernel path the plan chose and the MFMAs issued per 1024 outputs; looks for cliffs between the compiled shapes."""
+launch, the kernel path the plan chose and the MFMAs issued per 1024 outputs; looks for cliffs between the compiled shapes.
+TAPS=1023,1027,4095,16383 in the environment replaces the default list (1026 taps and more: the long kernel, path mfma_long)."""
 import sys
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
