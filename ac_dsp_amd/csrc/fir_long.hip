@@ -1,6 +1,6 @@
 // fir_long.hip -- long 16-bit FIRs (1026 .. 16384 taps) on the gfx950 matrix cores, exact integer arithmetic.
 //
-// The formulation is that of fir_mfma.hip (header comment there): one step is 1024 consecutive outputs of one channel, the 32 MFMA columns
+// The formulation is that of fir_mfma_kernels.hpp (header comment there): one step is 1024 consecutive outputs of one channel, the 32 MFMA columns
 // are 32 consecutive output blocks, K-block b of the [32 x 32 NB] Toeplitz matrix meets "input chunk n + b", both operands are split into
 // two signed bytes and the four int32 plane sums are recombined in 64 bits.  |plane sum| <= 32 NB 2^14: 2^28 at NB = 513 (2^29 with the
 // re-biased low sample byte), so the accumulators of a step stay live across the WHOLE coefficient set and the recombination, the wrap to
@@ -37,7 +37,7 @@ constexpr int kLongSB = 16;                          // K-blocks per LDS segment
 constexpr int kLongNC = 32 + kLongSB - 1;            // chunks (32 samples) of a segment's sample window
 constexpr int kLongNP = 4 * kLongNC;                 // 16-byte loads of the window
 constexpr int kLongJN = (kLongNP + 63) / 64;         // ... per lane
-// one staged [plane][half] array of kLongNC 16-byte chunks (fir_mfma.hip, staged_array_bytes: size = 64 mod 128 keeps the halves 16 banks apart)
+// one staged [plane][half] array of kLongNC 16-byte chunks (fir_mfma_kernels.hpp, staged_array_bytes: size = 64 mod 128 keeps the halves 16 banks apart)
 constexpr int kLongARR = ((kLongNC * 16 + 63) / 128) * 128 + 64;
 constexpr int kLongAWords = 2 * kLongSB * 64;        // v4i words of one A segment: [plane][block][lane]
 constexpr int kLongAPerThread = kLongAWords / 512;   // = 4
@@ -52,7 +52,7 @@ struct LongArgs {
   int64_t n_steps;          // ceil(n / 1024)
   int64_t n8;               // n rounded up to a multiple of 8 (rows are readable that far)
   int32_t nb, hb0, hb1;     // K-blocks; the high-plane products of blocks [hb0, hb1] only are issued
-  uint32_t hi_xor;          // unsigned 16-bit samples: 0x80808080 flips the top bit of every high byte (fir_mfma.hip, MfmaArgs::hi_xor)
+  uint32_t hi_xor;          // unsigned 16-bit samples: 0x80808080 flips the top bit of every high byte (fir_mfma_kernels.hpp, MfmaArgs::hi_xor)
   const int64_t *corr;      // [1] 128 * sum(c) (+ 32768 * sum(c) with hi_xor)
 };
 

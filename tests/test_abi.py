@@ -151,3 +151,18 @@ def test_no_kernel_uses_scratch():
     # the allow-list must not outlive its entries
     present = {dn.replace("acdsp::", "") for k, dn in zip(ks, names) if k["scratch"] > 0}
     assert set(SCRATCH_ALLOWED) <= present, "stale SCRATCH_ALLOWED entries: %s" % (set(SCRATCH_ALLOWED) - present)
+
+
+def test_every_kernel_is_compiled_once():
+    """The kernel templates of fir_mfma_kernels.hpp, fir_up_kernels.hpp and cic2_kernels.hpp are instantiated by whichever translation unit
+    names them: a shape named in two units would compile twice (same work, a second copy in the library) without any error.  No kernel
+    name may occur in more than one code object of the shipped library."""
+    import collections
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import codeobj_notes as N
+    import ac_dsp_amd._lib as L
+    ks = N.kernels(L.LIB_PATH)
+    assert len(ks) >= 300, "expected the engine's kernels in %s, found %d" % (L.LIB_PATH, len(ks))
+    twice = sorted(name for name, count in collections.Counter(k["name"] for k in ks).items() if count > 1)
+    assert not twice, "kernels compiled in more than one translation unit:\n  " + "\n  ".join(N.demangle(twice))

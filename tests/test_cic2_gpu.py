@@ -49,7 +49,7 @@ def int_fmt(R, M, N, fin):
 
 
 CASES = [
-    # W, I, R, M, N      (stage-1 rates compiled: 16 / 10 / 8 / 15 / 5 / 12 / 6 / 7 / 4 / 3 on 16-bit samples, 10 / 8 / 5 / 4 / 3 / 6 / 7 on 32-bit samples: cic2.hip ACDSP_CIC2_SHAPES)
+    # W, I, R, M, N      (stage-1 rates compiled: 16 / 10 / 8 / 15 / 5 / 12 / 6 / 7 / 4 / 3 on 16-bit samples, 10 / 8 / 5 / 4 / 3 / 6 / 7 on 32-bit samples: cic2_kernels.hpp ACDSP_CIC2_SHAPES)
     (16, 1, 32, 1, 4), (16, 1, 64, 1, 3), (16, 1, 128, 2, 3), (16, 1, 256, 1, 3), (16, 1, 32, 1, 6), (16, 1, 48, 2, 3), (16, 1, 40, 1, 5),
     (16, 1, 64, 1, 5), (12, 4, 96, 1, 3), (16, 1, 100, 1, 3), (16, 1, 250, 1, 3), (16, 1, 255, 2, 3), (16, 1, 35, 1, 4), (16, 1, 45, 1, 5),
     (16, 1, 56, 1, 2), (16, 1, 200, 1, 1),

@@ -34,6 +34,10 @@ def main():
     rounds = sorted({os.path.basename(f).split("_")[0] for f in files}, key=lambda r: -int(r[1:]))
     out = ["# profiles/ -- evidence index (regenerate with `python tools/profiles_index.py`)", "",
            "Every number DESIGN.md / BASELINE.md quote comes from one of these files; `gpurun_out/` is scratch.  Newest round first.", ""]
+    other = sorted(f for f in glob.glob(os.path.join(ROOT, "*")) if f not in files and not f.endswith("README.md"))
+    if other:   # evidence of a restructuring rather than of a tuning round
+        out += ["## not tied to a round", "", "| file | what it holds |", "|---|---|"]
+        out += ["| `%s` | %s |" % (os.path.basename(f), describe(f).replace("|", "/")) for f in other] + [""]
     for r in rounds:
         out += ["## round %s" % r[1:], "", "| file | what it holds |", "|---|---|"]
         for f in files:
