@@ -179,6 +179,8 @@ SYMBOLS = {
     "acdsp_polydec_run_host": (_i32, [_vp, _vp, _i64, _vp]),
     "acdsp_polydec_reset": (_i32, [_vp]),
     "acdsp_polydec_path": (_i32, [_vp]),
+    "acdsp_polydec_set_scratch_cap": (_i32, [_vp, C.c_uint64]),
+    "acdsp_polydec_long_geometry": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(C.c_uint64)]),
     "acdsp_polyintr_create": (_i32, [C.POINTER(PolyIntrDesc), C.POINTER(_vp)]),
     "acdsp_polyintr_destroy": (_i32, [_vp]),
     "acdsp_polyintr_set_ctrl": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),

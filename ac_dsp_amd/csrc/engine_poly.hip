@@ -15,16 +15,53 @@ struct acdsp_polydec {
   History hist;
   DevBuf d_coeffs, d_gfrag;
   FirGenPlan gplan;
+  // long prototypes (polydec_long.hip): long_shape = the descriptor is long-eligible and the ring kernel has no plan for its shape (create);
+  // long_ok = the current set runs there.  The scratch of the phase streams is sized at create / set_scratch_cap, never in run()
+  bool long_shape = false, long_ok = false, in_flip = false;
+  PolyDecLongPlan lplan;
+  PolyDecLongGeom lgeo = {0, 0, 0};
+  uint64_t scratch_cap = (uint64_t)128 << 20;
+  DevBuf d_lfrag, d_lcorr, d_scratch;
   int last_path = ACDSP_PATH_GENERIC;
   Staging st;
 };
+
+namespace {
+
+// Long prototypes (polydec_long.hip): the condition a descriptor fails, or nullptr when it is long-eligible
+const char *polydec_long_refusal(const acdsp_polydec_desc_t &d) {
+  if (d.df < 1 || d.df > kPolyDecLongMaxDf) { return "DF outside 1..256"; }
+  if (d.n_taps < 1 || (int64_t)d.n_taps * d.df > kPolyDecLongMaxTaps) { return "NTAPS*DF above 16384"; }
+  if (d.flags & ACDSP_FLAG_FORCE_GENERIC) { return "ACDSP_FLAG_FORCE_GENERIC (the exact-order kernel ends at NTAPS*DF = 2048)"; }
+  if (d.in.W > 16) { return "IN_TYPE wider than 16 bits"; }
+  if (d.coeff.S ? d.coeff.W > 16 : d.coeff.W > 15) { return "COEFF_TYPE wider than 16 bits signed / 15 bits unsigned"; }
+  // (ACC_TYPE / OUT_TYPE of more than 64 bits never get here: check_fmt refuses them for every ac_poly_dec shape)
+  const int fi = d.in.W - d.in.I, fc = d.coeff.W - d.coeff.I, fa = d.acc.W - d.acc.I;
+  if (fa < fi + fc || fa - fi - fc >= 64) { return "ACC_TYPE is not an exact-sum accumulator (F_acc >= F_in + F_coeff, shift below 64)"; }
+  return nullptr;
+}
+
+// scratch of a long handle under `cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a
+// failure leaves cap, geometry and scratch as they were
+int polydec_size_scratch(acdsp_polydec *h, uint64_t cap) {
+  const PolyDecLongGeom geo = polydec_long_geometry(h->d.n_taps, h->d.df, h->d.n_channels, cap);
+  DevBuf fresh;
+  const int rc = fresh.alloc(geo.bytes);
+  if (rc) { return rc; }
+  h->d_scratch = std::move(fresh);   // (the old buffer goes with `fresh`)
+  h->lgeo = geo;
+  h->scratch_cap = cap;
+  return ACDSP_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
 int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *out) {
   if (!desc || !out) { return fail(ACDSP_EINVAL, "null argument"); }
-  if (desc->n_taps < 1 || desc->df < 1 || (int64_t)desc->n_taps * desc->df > 2048) {
-    return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %lld outside 1..2048", (long long)desc->n_taps * desc->df);
+  if (desc->n_taps < 1 || desc->df < 1 || (int64_t)desc->n_taps * desc->df > kPolyDecLongMaxTaps) {
+    return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %lld outside 1..%d", (long long)desc->n_taps * desc->df, kPolyDecLongMaxTaps);
   }
   if (desc->n_channels < 1) { return fail(ACDSP_EINVAL, "n_channels=%d must be positive", desc->n_channels); }
   if (desc->n_channels > 65535) { return fail(ACDSP_EUNSUPPORTED, "n_channels=%d outside 1..65535", desc->n_channels); }
@@ -38,6 +75,12 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
   if (desc->in.W + desc->coeff.W + 2 + (f - fi - fc) > 125 || desc->acc.W + (f - fa) > 125) {
     return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 128-bit intermediates");
   }
+  // NTAPS*DF above 2048: the long matrix-core kernel or nothing
+  const char *const long_why = polydec_long_refusal(*desc);
+  if ((int64_t)desc->n_taps * desc->df > 2048 && long_why) {
+    return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %lld: more than 2048 taps run on the long matrix-core kernel only, which does not take %s",
+                (long long)desc->n_taps * desc->df, long_why);
+  }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_polydec> h(new acdsp_polydec());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
@@ -49,6 +92,16 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
   if ((rc = h->hist.init(desc->n_channels, h->hl, h->in_eb)) || (rc = h->d_coeffs.alloc((size_t)desc->n_taps * desc->df * sizeof(int64_t))) ||
       (rc = h->d_gfrag.alloc(kGenFragWords * sizeof(uint32_t)))) {
     return rc;
+  }
+  // the long kernel takes the eligible shapes the ring kernel has no plan for (DF > 64, more than 8 K blocks): a test of the shape alone
+  int g_off, g_nb;
+  h->long_shape = !long_why && !fir_gen_window(desc->n_taps * desc->df, desc->df, (desc->df - 1) % 16, &g_off, &g_nb);
+  if (h->long_shape) {
+    h->in_flip = !desc->in.S && desc->in.W == 16;   // unsigned 16-bit samples: read as x - 32768, 32768 * sum(c) rides in the correction constant
+    if ((rc = h->d_lfrag.alloc((size_t)2 * desc->df * polydec_long_blocks(desc->n_taps) * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc(sizeof(int64_t))) ||
+        (rc = polydec_size_scratch(h.get(), h->scratch_cap))) {
+      return rc;
+    }
   }
   *out = h.release();
   return ACDSP_OK;
@@ -94,11 +147,51 @@ int32_t acdsp_polydec_set_coeffs(acdsp_polydec_t h, const int64_t *coeffs) {
       h->gen_ok = true;
     }
   }
+  // Long shapes: the int8 split of polydec_long.hip.  Above 2048 taps nothing else exists: a set that cannot go there is refused, and the
+  // handle stays without a set.
+  h->long_ok = false;
+  if (h->long_shape) {
+    std::vector<uint32_t> fr;
+    if (!h->lossless) {
+      if (n > 2048) {
+        h->coeffs_set = false;
+        return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", n);
+      }
+    } else if (polydec_long_plan(coeffs, d.n_taps, d.df, &h->lplan, &fr)) {
+      if (h->in_flip) {
+        int64_t sc = 0;
+        for (int i = 0; i < n; i++) { sc += coeffs[i]; }
+        h->lplan.corr += 32768 * sc;
+      }
+      if ((rc = h->d_lfrag.upload(fr.data(), fr.size() * sizeof(uint32_t))) || (rc = h->d_lcorr.upload(&h->lplan.corr, sizeof(int64_t)))) { return rc; }
+      h->long_ok = true;
+    } else if (n > 2048) {
+      h->coeffs_set = false;
+      return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %d: a coefficient of 32640 or more cannot be split into two signed bytes, and more than 2048 taps run on the matrix cores only", n);
+    }
+  }
   h->coeffs_set = true;
   return ACDSP_OK;
 }
 
 int32_t acdsp_polydec_path(acdsp_polydec_t h) { return h ? h->last_path : -1; }
+
+int32_t acdsp_polydec_set_scratch_cap(acdsp_polydec_t h, uint64_t bytes) {
+  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
+  if (!h->long_shape) { return ACDSP_OK; }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  return polydec_size_scratch(h, bytes);
+}
+
+int32_t acdsp_polydec_long_geometry(acdsp_polydec_t h, int64_t *slab_outputs, int32_t *group_channels, uint64_t *scratch_bytes) {
+  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
+  if (slab_outputs) { *slab_outputs = h->long_shape ? h->lgeo.slab : 0; }
+  if (group_channels) { *group_channels = h->long_shape ? h->lgeo.group : 0; }
+  if (scratch_bytes) { *scratch_bytes = h->long_shape ? h->lgeo.bytes : 0; }
+  return ACDSP_OK;
+}
 
 int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride,
                           void *stream) {
@@ -123,7 +216,11 @@ int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride
   k.x = d_in; k.y = d_out; k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>();
   const bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && in_stride >= (n_in + 15) / 16 * 16;
   hipError_t e;
-  if (h->gen_ok && aligned) {
+  if (h->long_ok) {   // every call, whatever its length or alignment
+    h->last_path = ACDSP_PATH_MFMA_LONG;
+    k.in_flip = h->in_flip;
+    e = launch_polydec_long(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_scratch.get(), n_out, s);
+  } else if (h->gen_ok && aligned) {
     h->last_path = ACDSP_PATH_MFMA_GEN;
     e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, d.df - 1, n_out, s);
   } else {

@@ -52,6 +52,15 @@ constexpr int kGenMaxPX = 8, kGenMaxPC = 3, kGenMaxNB = 8;  // A fragments: [b][
 // ---------------------------------------------------------------------------------------------
 // host: coefficient planes and A fragments
 // ---------------------------------------------------------------------------------------------
+// window geometry: T_n mod 16 == first mod 16; window start is the 16-aligned floor of T_n - (taps-1)
+bool fir_gen_window(int n_taps, int R, int first_mod16, int *off, int *nb) {
+  if (n_taps < 1 || R < 1 || R > 64) { return false; }
+  const int a = ((first_mod16 - (n_taps - 1)) % 16 + 16) % 16;
+  *off = (n_taps - 1) + a;
+  *nb = (*off + 15 * R + 1 + 63) / 64;
+  return *nb <= kGenMaxNB;
+}
+
 bool fir_gen_plan(const int64_t *h, int n_taps, int R, int first_mod16, FirGenPlan *pl, std::vector<uint32_t> *frag) {
   // balanced base-256 digits of every tap
   int pc = 1;
@@ -68,11 +77,8 @@ bool fir_gen_plan(const int64_t *h, int n_taps, int R, int first_mod16, FirGenPl
     }
     if (v != 0) { return false; }  // needs more than kGenMaxPC digits (dig[][] has exactly kGenMaxPC rows)
   }
-  // window geometry: T_n mod 16 == first mod 16; window start is the 16-aligned floor of T_n - (taps-1)
-  const int a = ((first_mod16 - (n_taps - 1)) % 16 + 16) % 16;
-  const int off = (n_taps - 1) + a;
-  const int nb = (off + 15 * R + 1 + 63) / 64;
-  if (nb > kGenMaxNB) { return false; }
+  int off, nb;
+  if (!fir_gen_window(n_taps, R, first_mod16, &off, &nb)) { return false; }
   pl->pc = pc; pl->nb = nb; pl->off = off; pl->R = R;
   __int128 sum = 0, sum_abs = 0;
   for (int k = 0; k < n_taps; k++) { sum += (__int128)h[k]; sum_abs += h[k] < 0 ? -(__int128)h[k] : (__int128)h[k]; }

@@ -92,6 +92,8 @@ struct FirGenPlan {
 // y[m] = sum_k h[k] x[first + m R - k] mod 2^64.  Builds the A fragments for first % 16 == first_mod16;
 // false if the taps need more than 3 byte planes or more than 8 K blocks.
 bool fir_gen_plan(const int64_t *h, int n_taps, int R, int first_mod16, FirGenPlan *pl, std::vector<uint32_t> *frag);
+// the shape half of that answer: window offset and K blocks of (n_taps, R, first % 16); false where the ring kernel has no plan (R > 64, more than 8 K blocks)
+bool fir_gen_window(int n_taps, int R, int first_mod16, int *off, int *nb);
 // out_mode 0: FIR class A epilogue (p.lossless_shift, p.acc wrap, requant to p.out);
 // out_mode 1: CIC epilogue (wrap to w_int, requant from p.in.F to p.out).  p.n = inputs, p.hist holds >= off samples.
 // Class B on the ring kernel (lossy accumulator, AC_TRN / AC_RND into AC_WRAP; fir_gen.hip: LZ instantiations).  pl / d_frag are the
@@ -246,5 +248,29 @@ hipError_t launch_diag_envelope_copygeom(const uint32_t *d_frag, const void *x, 
 
 // Polyphase decimator, exact per-MAC order (polydec.hip); p.coeffs = STR_COEFF_TYPE array [ntaps*df], p.n = inputs used
 hipError_t launch_polydec_generic(const FirParams &p, int ntaps, int df, int64_t n_out, hipStream_t s);
+
+// Long polyphase decimators (polydec_long.hip): NTAPS * DF up to 16384, DF up to 256, as DF Toeplitz products of fir_long.hip's int8 split on
+// the phase streams z_d[m] = x[m DF + DF-1 - d], which a first kernel writes into a scratch of the handle
+constexpr int kPolyDecLongMaxTaps = 16384, kPolyDecLongMaxDf = 256;
+struct PolyDecLongPlan {
+  int32_t ntaps, df, nb;       // nb = K-blocks per phase = max(2, ceil((ntaps-1)/32) + 1); the phase rows reach 32 (nb - 1) samples back
+  int64_t corr;                // 128 * sum(c) over all phases
+};
+int polydec_long_blocks(int ntaps);
+// host: fragments frag[2][df * nb][64][4] of c[tp + ntaps * d] and the plan; false if a coefficient cannot be split into two signed bytes
+bool polydec_long_plan(const int64_t *coeffs, int ntaps, int df, PolyDecLongPlan *plan, std::vector<uint32_t> *frag);
+// A call is walked as channel groups x time slabs.  With b(G) = df * (32 (nb - 1) + G) * 2 bytes per channel: group = n_ch if n_ch * b(1024)
+// <= cap, else the largest multiple of 8 that fits (at least 8); slab = the largest multiple of 1024 with group * b(slab) <= cap, inside
+// 1024 .. 65536; bytes = group * b(slab), the scratch the launches need
+struct PolyDecLongGeom {
+  int64_t slab;
+  int32_t group;
+  uint64_t bytes;
+};
+PolyDecLongGeom polydec_long_geometry(int ntaps, int df, int n_ch, uint64_t cap);
+// p.n = inputs, p.x / p.hist / p.y as for the other kernels (2-byte IN containers, rows at any element-aligned address); two launches per
+// slab of a group, no allocation and no synchronisation
+hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, const PolyDecLongGeom &geo, const uint32_t *d_frag,
+                               const int64_t *d_corr, void *d_scratch, int64_t n_out, hipStream_t s);
 
 }  // namespace acdsp

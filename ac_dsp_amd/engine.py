@@ -371,6 +371,16 @@ class PolyDec:
                                     out.stride(0), _stream_ptr(x)))
         return out[:, :n_out]
 
+    def set_scratch_cap(self, n_bytes):
+        """long prototypes: bound the scratch of the phase streams (re-derives the slab / group geometry, reallocates, synchronises)"""
+        check(lib.acdsp_polydec_set_scratch_cap(self._h, int(n_bytes)))
+
+    def long_geometry(self):
+        """(outputs per slab, channels per group, scratch bytes) of a long handle; (0, 0, 0) otherwise"""
+        slab, group, nbytes = C.c_int64(), C.c_int32(), C.c_uint64()
+        check(lib.acdsp_polydec_long_geometry(self._h, C.byref(slab), C.byref(group), C.byref(nbytes)))
+        return slab.value, group.value, nbytes.value
+
     def reset(self):
         check(lib.acdsp_polydec_reset(self._h))
 

@@ -278,7 +278,15 @@ int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride
                           int64_t out_stride, void *stream);
 int32_t acdsp_polydec_run_host(acdsp_polydec_t h, const void *h_in, int64_t n_in, void *h_out);
 int32_t acdsp_polydec_reset(acdsp_polydec_t h);
-int32_t acdsp_polydec_path(acdsp_polydec_t h);  /* ACDSP_PATH_GENERIC or ACDSP_PATH_MFMA_GEN */
+int32_t acdsp_polydec_path(acdsp_polydec_t h);  /* last run(): ACDSP_PATH_GENERIC, ACDSP_PATH_MFMA_GEN (ring kernel) or ACDSP_PATH_MFMA_LONG (long prototypes) */
+/* Long prototypes (NTAPS*DF up to 16384, DF up to 256; exact-sum types of up to 16 bits whose shape the ring kernel cannot plan) run as DF
+ * matrix-core FIRs on the phase streams, which a first kernel writes into a scratch buffer owned by the handle.  A call is walked as channel
+ * groups x time slabs sized so that the scratch stays within a cap (default 128 MiB; at least 8 channels x 1024 outputs).  set_scratch_cap
+ * re-derives the geometry and reallocates (it synchronises the device; graphs captured before it hold the old buffer and must be re-captured);
+ * on a handle that is not long it does nothing; if the new buffer cannot be allocated the call fails and cap, geometry and buffer stay as they were.  long_geometry reports outputs per slab, channels per group and the scratch bytes, all zero
+ * for a handle that is not long. */
+int32_t acdsp_polydec_set_scratch_cap(acdsp_polydec_t h, uint64_t bytes);
+int32_t acdsp_polydec_long_geometry(acdsp_polydec_t h, int64_t *slab_outputs, int32_t *group_channels, uint64_t *scratch_bytes);
 
 /* ---- DDC cascade: ac_cic_dec_full -> FIR on the decimator's lossless INT_TYPE words ----
  * Replaces the pair of run() calls `cic.run(in, mid); fir.run(mid, out);` on many channels (the reference couples the
