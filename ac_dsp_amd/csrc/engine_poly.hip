@@ -277,17 +277,60 @@ struct acdsp_polyintr {
   uint32_t up_shmask = 0;
   int64_t up_max_abs = -1;      // bound on |z| of the folded taps (enables the 32-bit epilogue)
   DevBuf d_upfrag, d_upcorr;
+  // long sub-filters (polyintr_long.hip): long_shape = the descriptor is long-capable (create); long_ok = the current control words run
+  // there.  The scratch of the phase rows is sized at create / set_scratch_cap, never in run()
+  bool long_shape = false, long_ok = false;
+  PolyIntrLongPlan lplan;
+  PolyIntrLongGeom lgeo = {0, 0, 0};
+  uint64_t scratch_cap = (uint64_t)128 << 20;
+  DevBuf d_lfrag, d_lcorr, d_lhalve, d_scratch;
   int last_path = ACDSP_PATH_GENERIC;
   Staging st;
 };
 
 namespace {
 
+inline int polyintr_lag(const acdsp_polyintr_desc_t &d) { return d.ftype == ACDSP_POLY_FOLD_ANTI ? 0 : 1; }
+
+// the exact-accumulation class of ac_poly_intr as far as the descriptor decides it (a 64-bit ACC_TYPE needs the bound of the control words too)
+inline bool polyintr_lossless_desc(const acdsp_polyintr_desc_t &d) {
+  const int fi = d.in.W - d.in.I, fc = d.coeff.W - d.coeff.I, fa = d.acc.W - d.acc.I, ls = fa - fi - fc;
+  return d.in.S && d.acc.S && d.acc.O == ACDSP_WRAP && ls >= 0 && ls < 64 && fa >= fi && d.acc.I >= d.in.I + 1 && d.acc.W <= 64;
+}
+
+// Long sub-filters (polyintr_long.hip): the condition a descriptor fails, or nullptr when it is long-capable
+const char *polyintr_long_refusal(const acdsp_polyintr_desc_t &d) {
+  const int nt = d.n_taps + polyintr_lag(d);
+  if (nt < kPolyIntrLongMinTaps) { return "fewer than 65 taps per phase"; }
+  if (nt > kPolyIntrLongMaxTaps) { return "more than 16384 taps per phase"; }
+  if (d.flags & ACDSP_FLAG_FORCE_GENERIC) { return "ACDSP_FLAG_FORCE_GENERIC (the exact-order kernels end at NTAPS = 2048)"; }
+  if (!d.in.S || d.in.W > 16) { return "an IN_TYPE that is unsigned or wider than 16 bits"; }
+  if (d.coeff.S ? d.coeff.W > 16 : d.coeff.W > 15) { return "a COEFF_TYPE wider than 16 bits signed / 15 bits unsigned"; }
+  if (!polyintr_lossless_desc(d)) {
+    return "an ACC_TYPE that is not an exact accumulator (signed AC_WRAP, F_acc >= F_in + F_coeff, I_acc >= I_in + 1, W_acc <= 64)";
+  }
+  if ((int64_t)d.ifac * polyintr_long_blocks(nt) > kPolyIntrLongMaxBlocks) { return "IF * K-blocks per phase above the K-block budget of 1024"; }
+  return nullptr;
+}
+
+// scratch of a long handle under `cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a
+// failure leaves cap, geometry and scratch as they were
+int polyintr_size_scratch(acdsp_polyintr *h, uint64_t cap) {
+  const PolyIntrLongGeom geo = polyintr_long_geometry(h->d.ifac, h->out_eb, h->d.n_channels, cap);
+  DevBuf fresh;
+  const int rc = fresh.alloc(geo.bytes);
+  if (rc) { return rc; }
+  h->d_scratch = std::move(fresh);   // (the old buffer goes with `fresh`)
+  h->lgeo = geo;
+  h->scratch_cap = cap;
+  return ACDSP_OK;
+}
+
 // Per-phase taps of ac_poly_intr as one linear filter of the input (host side; see fir_up.hip).  E[j][k] multiplies
 // x[n - k] in the output group of input sample n.  Returns false when the control words make the cores non-linear in the
 // input (a phase with sign[j] = 0 negates samples in IN_TYPE: -min(IN_TYPE) is not representable).
 bool polyintr_linear_taps(const acdsp_polyintr_desc_t &d, const int64_t *coeffs, const uint8_t *sign, const uint8_t *corr,
-                          std::vector<int64_t> *E, int *nt, uint32_t *sh_mask, __int128 *max_abs_sum) {
+                          std::vector<int64_t> *E, int *nt, uint32_t *sh_mask, __int128 *max_abs_sum, std::vector<uint8_t> *halve = nullptr) {
   const int N = d.n_taps, L = d.ifac;
   std::vector<std::vector<__int128>> sub((size_t)L, std::vector<__int128>((size_t)N, 0));   // sub-filter sums acc_n[j] = sum_k sub[j][k] x[n-k]
   for (int j = 0; j < L; j++) {
@@ -313,9 +356,10 @@ bool polyintr_linear_taps(const acdsp_polyintr_desc_t &d, const int64_t *coeffs,
     for (int k = 0; k < N; k++) { sa += sub[j][k] < 0 ? -sub[j][k] : sub[j][k]; }
     if (sa > *max_abs_sum) { *max_abs_sum = sa; }
   }
-  const int lag = d.ftype == ACDSP_POLY_FOLD_ANTI ? 0 : 1;   // banks: the sums of sample n-1 leave with sample n (:153-175)
+  const int lag = polyintr_lag(d);   // banks: the sums of sample n-1 leave with sample n (:153-175)
   *nt = N + lag;
-  *sh_mask = 0;
+  *sh_mask = 0;   // (phases 0 .. 31, all fir_up.hip takes; `halve` holds every phase)
+  if (halve) { halve->assign((size_t)L, 0); }
   E->assign((size_t)L * (size_t)*nt, 0);
   for (int j = 0; j < L; j++) {
     const int cj = d.ftype == ACDSP_POLY_FOLD_ANTI ? j : corr[j];
@@ -325,7 +369,10 @@ bool polyintr_linear_taps(const acdsp_polyintr_desc_t &d, const int64_t *coeffs,
       if (g < INT64_MIN / 4 || g > INT64_MAX / 4) { return false; }
       (*E)[(size_t)j * *nt + k + lag] = (int64_t)g;
     }
-    if (cj != j) { *sh_mask |= 1u << j; }
+    if (cj != j) {
+      if (j < 32) { *sh_mask |= 1u << j; }
+      if (halve) { (*halve)[(size_t)j] = 1; }
+    }
   }
   return true;
 }
@@ -347,7 +394,9 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
   if (!desc || !out) { return fail(ACDSP_EINVAL, "null argument"); }
   const acdsp_polyintr_desc_t &d = *desc;
   if (d.ftype < ACDSP_POLY_FOLD_EVEN || d.ftype > ACDSP_POLY_FOLD_ANTI) { return fail(ACDSP_EINVAL, "bad poly_intr ftype %d", d.ftype); }
-  if (d.n_taps < 1 || d.n_taps > 2048) { return fail(ACDSP_EUNSUPPORTED, "NTAPS=%d outside 1..2048", d.n_taps); }
+  if (d.n_taps < 1 || d.n_taps > kPolyIntrLongMaxTaps - polyintr_lag(d)) {
+    return fail(ACDSP_EUNSUPPORTED, "NTAPS=%d outside 1..%d", d.n_taps, kPolyIntrLongMaxTaps - polyintr_lag(d));
+  }
   if (d.ifac < 1 || d.ifac > 255) { return fail(ACDSP_EUNSUPPORTED, "IF=%d outside 1..255 (corr[] is ac_int<8,false>)", d.ifac); }
   if (d.coeff_sz < 1 || d.coeff_sz > (1 << 20)) { return fail(ACDSP_EUNSUPPORTED, "COEFFSZ=%d outside 1..2^20", d.coeff_sz); }
   if (d.n_channels < 1) { return fail(ACDSP_EINVAL, "n_channels=%d must be positive", d.n_channels); }
@@ -364,6 +413,11 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
     const int f = fp > fa ? fp : fa;
     if (wp + (f - fp) > 125 || d.acc.W + (f - fa) > 125) { return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 128-bit intermediates"); }
   }
+  // NTAPS above 2048: the long matrix-core kernels or nothing
+  const char *const long_why = polyintr_long_refusal(d);
+  if (d.n_taps > 2048 && long_why) {
+    return fail(ACDSP_EUNSUPPORTED, "poly_intr: NTAPS=%d: more than 2048 taps run on the long matrix-core kernels only, which do not take %s", d.n_taps, long_why);
+  }
   if ((rc = check_device(d.device))) { return rc; }
   std::unique_ptr<acdsp_polyintr> h(new acdsp_polyintr());   // (check_device has made the device current: a failure below frees there)
   h->d = d;
@@ -374,6 +428,21 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
     if ((rc = sv.alloc_zeroed((size_t)d.n_channels * d.ifac * sizeof(int64_t)))) { return rc; }   // acc_a / acc_b start at 0 (ac_poly_intr.h:117-118)
   }
   if ((rc = h->d_coeffs.alloc((size_t)d.coeff_sz * sizeof(int64_t))) || (rc = h->d_sign.alloc((size_t)d.ifac)) || (rc = h->d_corr.alloc((size_t)d.ifac))) { return rc; }
+  h->long_shape = long_why == nullptr;
+  if (h->long_shape) {
+    const int nb = polyintr_long_blocks(d.n_taps + polyintr_lag(d));
+    // a step reaches 32 (nb - 1) samples back: inside the history as far as real taps go (nt - 1 <= NTAPS), beyond it over zero-padded taps only
+    if (h->hl < d.n_taps || h->hl % 32 || 32 * (nb - 1) > h->hl) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
+    if ((rc = h->d_lfrag.alloc((size_t)2 * d.ifac * nb * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc((size_t)d.ifac * sizeof(int64_t))) ||
+        (rc = h->d_lhalve.alloc((size_t)d.ifac)) || (rc = polyintr_size_scratch(h.get(), h->scratch_cap))) {
+      if (d.n_taps > 2048) { return rc; }
+      // up to 2048 taps the handle existed without these buffers: it stays what it was, on the exact kernels
+      h->long_shape = false;
+      h->d_lfrag = DevBuf(); h->d_lcorr = DevBuf(); h->d_lhalve = DevBuf(); h->d_scratch = DevBuf();
+      h->lgeo = {0, 0, 0};
+      (void)hipGetLastError();
+    }
+  }
   *out = h.release();
   return ACDSP_OK;
 }
@@ -394,41 +463,65 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
   for (int j = 0; j < d.ifac; j++) {
     if (d.ftype != ACDSP_POLY_FOLD_ANTI && corr[j] >= d.ifac) { return fail(ACDSP_EINVAL, "corr[%d] = %d indexes outside the IF = %d accumulator banks", j, corr[j], d.ifac); }
   }
+  // The cores as IF linear filters of the input, folded once for every decision below (an O(IF * NTAPS) fold: exact-accumulation descriptors only)
+  const int fi = d.in.W - d.in.I, fc = d.coeff.W - d.coeff.I, fa = d.acc.W - d.acc.I, ls = fa - fi - fc;
+  const bool lossless = polyintr_lossless_desc(d);
+  std::vector<int64_t> E;
+  std::vector<uint8_t> hv;
+  int nt = 0;
+  uint32_t shm = 0;
+  __int128 sa = 0;
+  const bool linear = lossless && polyintr_linear_taps(d, coeffs, sign, corr, &E, &nt, &shm, &sa, &hv);
+  // |acc| <= sum|taps| * 2^(W_in - 1) << ls must stay inside ACC_TYPE (62 bits of a 64-bit one); a pair sum then fits one more bit
+  const bool no_wrap = linear && d.in.W - 1 + ls < 100 && (sa << (d.in.W - 1 + ls)) < ((__int128)1 << ((d.acc.W < 64 ? d.acc.W : 63) - 1));
+  // Long sub-filters (polyintr_long.hip): decided on the host before anything is uploaded.  The control words must keep the cores linear
+  // (every sign[j] set on the folded cores), no sum may wrap ACC_TYPE (the pair halving does not commute with a wrap) and every folded tap
+  // must split into two signed bytes.  Above 2048 taps nothing else exists: a set that cannot go there is refused and the handle keeps
+  // the state it had.
+  bool long_ok = false;
+  std::vector<uint32_t> lfrag;
+  std::vector<int64_t> lcorr;
+  std::vector<uint8_t> lhalve;
+  PolyIntrLongPlan lpl;
+  if (h->long_shape) {
+    const char *why = nullptr;
+    if (!linear) { why = "a phase with sign[j] = 0 (it negates samples in IN_TYPE)"; }
+    else if (!no_wrap) { why = "sub-filter sums that may wrap ACC_TYPE"; }
+    else if (!polyintr_long_plan(E.data(), d.ifac, nt, hv.data(), &lpl, &lfrag, &lcorr, &lhalve)) { why = "a folded tap outside -32768..32639 (it cannot be split into two signed bytes)"; }
+    long_ok = why == nullptr;
+    if (!long_ok && d.n_taps > 2048) {
+      return fail(ACDSP_EUNSUPPORTED, "poly_intr: NTAPS=%d: more than 2048 taps run on the long matrix-core kernels only, which do not take %s", d.n_taps, why);
+    }
+  }
   HIP_TRY(hipDeviceSynchronize());
   if ((rc = h->d_coeffs.upload(coeffs, (size_t)d.coeff_sz * sizeof(int64_t))) || (rc = h->d_sign.upload(sign, (size_t)d.ifac)) ||
       (rc = h->d_corr.upload(corr, (size_t)d.ifac))) {
     return rc;
   }
   h->ctrl_set = true;
+  h->long_ok = false;
+  if (long_ok) {
+    if ((rc = h->d_lfrag.upload(lfrag.data(), lfrag.size() * sizeof(uint32_t))) || (rc = h->d_lcorr.upload(lcorr.data(), lcorr.size() * sizeof(int64_t))) ||
+        (rc = h->d_lhalve.upload(lhalve.data(), lhalve.size()))) {
+      return rc;
+    }
+    h->lplan = lpl;
+    h->long_ok = true;
+  }
   // matrix-core path: exact-accumulation class, int16 samples, control words that keep the cores linear, and an
   // accumulator that cannot wrap (the symmetric-pair halving (t1 -/+ t2) >> 1 does not commute with a wrap)
   h->up_ok = false;
   static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
-  const int fi = d.in.W - d.in.I, fc = d.coeff.W - d.coeff.I, fa = d.acc.W - d.acc.I, ls = fa - fi - fc;
   // (a 64-bit ACC_TYPE -- the header's own usage example, ac_poly_intr.h:45-48: <32,16> samples and coefficients into <64,32> -- belongs to
   // the class when the control words bound every sub-filter sum to 62 bits: nothing can wrap and the pair sum t1 -/+ t2 stays inside int64)
-  const bool lossless = d.in.S && d.acc.S && d.acc.O == ACDSP_WRAP && ls >= 0 && ls < 64 && fa >= fi && d.acc.I >= d.in.I + 1 && d.acc.W <= 64;
-  h->acc64_ok = false;
-  if (lossless && d.acc.W == 64) {
-    std::vector<int64_t> E;
-    int nt = 0;
-    uint32_t shm = 0;
-    __int128 sa = 0;
-    h->acc64_ok = polyintr_linear_taps(d, coeffs, sign, corr, &E, &nt, &shm, &sa) && d.in.W - 1 + ls < 100 && (sa << (d.in.W - 1 + ls)) < ((__int128)1 << 62);
-  }
+  h->acc64_ok = lossless && d.acc.W == 64 && no_wrap;
   const int upx = h->in_eb;
-  if (lossless && (d.acc.W <= 63 || h->acc64_ok) && !no_gen && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && (h->in_eb == 2 || h->in_eb == 4) && d.ifac <= 32) {
-    std::vector<int64_t> E;
-    int nt = 0;
-    uint32_t shm = 0;
-    __int128 sa = 0;
+  // (a long-capable handle has nt >= 65 taps per phase: fir_up_plan has no plan there)
+  if (!h->long_shape && no_wrap && !no_gen && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && (h->in_eb == 2 || h->in_eb == 4) && d.ifac <= 32) {
     std::vector<uint32_t> frag;
     std::vector<int64_t> ucorr;
     FirUpPlan pl;
-    if (polyintr_linear_taps(d, coeffs, sign, corr, &E, &nt, &shm, &sa) &&
-        // |acc| <= sum|taps| * 2^(W_in - 1) << ls must stay inside ACC_TYPE; a pair sum then fits one more bit
-        (sa << (d.in.W - 1 + ls)) < ((__int128)1 << ((d.acc.W < 64 ? d.acc.W : 63) - 1)) &&
-        fir_up_plan(E.data(), d.ifac, nt, upx, &pl, &frag, &ucorr) && fir_up_shape_ok(h->in_eb, upx, pl.nb, d.ifac, h->out_eb)) {
+    if (fir_up_plan(E.data(), d.ifac, nt, upx, &pl, &frag, &ucorr) && fir_up_shape_ok(h->in_eb, upx, pl.nb, d.ifac, h->out_eb)) {
       if ((rc = h->d_upfrag.alloc_upload(frag)) || (rc = h->d_upcorr.alloc_upload(ucorr))) { return rc; }
       h->up_plan = pl; h->up_shmask = shm; h->up_ok = true; h->up_px = upx;
       {  // |z| <= max_j sum_k |E_j[k]| * 2^(W_in - 1)
@@ -443,6 +536,23 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
       }
     }
   }
+  return ACDSP_OK;
+}
+
+int32_t acdsp_polyintr_set_scratch_cap(acdsp_polyintr_t h, uint64_t bytes) {
+  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
+  if (!h->long_shape) { return ACDSP_OK; }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  return polyintr_size_scratch(h, bytes);
+}
+
+int32_t acdsp_polyintr_long_geometry(acdsp_polyintr_t h, int64_t *slab_inputs, int32_t *group_channels, uint64_t *scratch_bytes) {
+  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
+  if (slab_inputs) { *slab_inputs = h->long_shape ? h->lgeo.slab : 0; }
+  if (group_channels) { *group_channels = h->long_shape ? h->lgeo.group : 0; }
+  if (scratch_bytes) { *scratch_bytes = h->long_shape ? h->lgeo.bytes : 0; }
   return ACDSP_OK;
 }
 
@@ -493,7 +603,30 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
   int64_t o_a = 0, o_b = 0;   // outputs [o_a, o_b) are produced by fir_up
   bool forked = false;
   h->last_path = p.lossless ? ACDSP_PATH_LOSSLESS64 : ACDSP_PATH_GENERIC;
-  if (h->up_ok && p.lossless) {
+  if (h->long_ok) {
+    // Long sub-filters, every call whatever its length and alignment.  Two things stay on the exact kernels below, beside the long kernels on
+    // the side stream: the first group of a call on the folded cores (it carries the sums saved by the previous call, formed with the
+    // coefficients of their own time) and the sums of the call's last sample -- so the stream continues bit for bit on the exact kernels
+    // when later control words leave the long path.
+    h->last_path = ACDSP_PATH_MFMA_LONG;
+    const int64_t o_lo = (d.ftype != ACDSP_POLY_FOLD_ANTI && h->t_total > 0) ? d.ifac : 0;
+    if (SideStream::enabled()) {
+      const hipError_t ef = h->side.fork(s);
+      if (ef != hipSuccess) { return fail(ACDSP_EHIP, "poly_intr side stream: %s", hipGetErrorString(ef)); }
+      forked = true;
+    }
+    FirParams k;
+    memset(&k, 0, sizeof k);
+    k.n_ch = d.n_channels; k.in = p.in; k.cf = p.cf; k.acc = p.acc; k.out = p.out; k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl;
+    k.lossless_shift = p.lossless_shift; k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in; k.x = d_in; k.y = d_out; k.hist = p.hist;
+    e = launch_polyintr_long(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_lhalve.get<uint8_t>(), h->d_scratch.get(),
+                             p.skip, o_lo, no, s);
+    if (e != hipSuccess) {
+      if (forked) { (void)h->side.join(s); }
+      return fail(ACDSP_EHIP, "poly_intr long kernel launch failed: %s", hipGetErrorString(e));
+    }
+    o_a = o_lo; o_b = no;   // (a call that ends with its first group runs that group and the save kernel in one launch below)
+  } else if (h->up_ok && p.lossless) {
     const int L = d.ifac;
     const int64_t out_off = -(int64_t)p.skip * L, slot_a = h->up_plan.hs;
     const int64_t n_steps = (n_in / 16 - slot_a) / 32;
@@ -527,7 +660,8 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
   hipStream_t vs = (forked && o_b > o_a) ? h->side.s : s;
   if (o_b > o_a) {
     p.o_begin = 0; p.o_end = o_a;
-    e = launch_polyintr(p, nullptr, vs);
+    // (the head of a long call is the one group that reads `saved`: no window or coefficient table to stage)
+    e = h->long_ok ? launch_polyintr_saved_group(p, vs) : launch_polyintr(p, nullptr, vs);
     if (e == hipSuccess) { p.o_begin = o_b; p.o_end = no; e = launch_polyintr(p, saved_next, vs); }
   } else {
     e = launch_polyintr(p, saved_next, s);

@@ -191,6 +191,8 @@ struct PolyIntrParams {
   const int64_t *saved;       // [n_ch][ifac] sums of the previous call's last sample (folded cores)
 };
 hipError_t launch_polyintr(const PolyIntrParams &p, int64_t *saved_next, hipStream_t s);
+// outputs [0, o_end <= ifac) of a folded core's call that continues a stream: the group that carries p.saved, on the thread-per-output kernel
+hipError_t launch_polyintr_saved_group(const PolyIntrParams &p, hipStream_t s);
 
 // Integrate-and-dump (intg_dump.hip).  Block b covers rounds [blk_off[b], blk_off[b] + blk_rounds[b]) of the interleaved
 // stream; blk_out[b] = index of its output group or -1 (no dump); blk_chain[b] = first block of its carry chain.
@@ -272,5 +274,36 @@ PolyDecLongGeom polydec_long_geometry(int ntaps, int df, int n_ch, uint64_t cap)
 // slab of a group, no allocation and no synchronisation
 hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, const PolyDecLongGeom &geo, const uint32_t *d_frag,
                                const int64_t *d_corr, void *d_scratch, int64_t n_out, hipStream_t s);
+
+// Long polyphase interpolators (polyintr_long.hip): 65 .. 16384 taps per phase, IF up to 255, as IF Toeplitz products of fir_long.hip's int8
+// split on ONE input stream; the phase rows go to a scratch of the handle and a second kernel interleaves them into the caller's rows
+constexpr int kPolyIntrLongMinTaps = 65, kPolyIntrLongMaxTaps = 16384;   // taps per phase of the linear filters (nt = NTAPS + lag)
+// IF * K-blocks per phase: 2 KB of A fragments each, 2 MiB in all -- a guess at what stays in one XCD's L2 beside the sample windows, not
+// measured.  Admits every 16384-tap prototype from 16383 x 1 to 64 x 255
+constexpr int kPolyIntrLongMaxBlocks = 1024;
+struct PolyIntrLongPlan {
+  int32_t nt, ifac, nb;        // nb = K-blocks per phase = max(2, ceil((nt-1)/32) + 1); a step reaches 32 (nb - 1) samples back
+};
+int polyintr_long_blocks(int nt);
+// host: E = [ifac][nt] taps, halve = [ifac] flags -> fragments frag[2][ifac * nb][64][4], the per-phase corrections 128 * sum(E_j) and the
+// flags as uploaded; false if a tap cannot be split into two signed bytes or the shape is outside the limits above
+bool polyintr_long_plan(const int64_t *E, int ifac, int nt, const uint8_t *halve, PolyIntrLongPlan *plan, std::vector<uint32_t> *frag,
+                        std::vector<int64_t> *corr, std::vector<uint8_t> *flags);
+// A call is walked as channel groups x time slabs.  With b(G) = ifac * G * out_eb bytes per channel: group = n_ch if n_ch * b(1024) <= cap,
+// else the largest multiple of 8 that fits (at least 8); slab = the largest multiple of 1024 input samples with group * b(slab) <= cap,
+// inside 1024 .. 65536; bytes = group * b(slab), the scratch the launches need.  (group <= n_ch <= 65535, which create enforces: the merge
+// kernel's grid has one row per group channel)
+struct PolyIntrLongGeom {
+  int64_t slab;
+  int32_t group;
+  uint64_t bytes;
+};
+PolyIntrLongGeom polyintr_long_geometry(int ifac, int out_eb, int n_ch, uint64_t cap);
+// p.n = inputs, p.x / p.hist / p.y as for the other kernels (2-byte IN containers, rows at any element-aligned address and stride).  Output
+// (input n, phase j) = (n - skip) ifac + j; the outputs [o_lo, n_out) of the call are written.  Two launches per slab of a group, no
+// allocation and no synchronisation
+hipError_t launch_polyintr_long(const FirParams &p, const PolyIntrLongPlan &plan, const PolyIntrLongGeom &geo, const uint32_t *d_frag,
+                                const int64_t *d_corr, const uint8_t *d_halve, void *d_scratch, int skip, int64_t o_lo, int64_t n_out,
+                                hipStream_t s);
 
 }  // namespace acdsp

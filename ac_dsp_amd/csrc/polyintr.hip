@@ -210,6 +210,15 @@ __global__ void polyintr_save_kernel(PolyIntrParams p, int64_t *saved_next) {
   saved_next[(int64_t)ch * p.ifac + j] = p.lossless ? polyintr_acc_fast(p, ch, p.n - 1, j) : polyintr_acc(p, ch, p.n - 1, j);
 }
 
+hipError_t launch_polyintr_saved_group(const PolyIntrParams &p, hipStream_t s) {
+  const int64_t span = p.o_end - p.o_begin;
+  if (span <= 0) { return hipSuccess; }
+  if (p.ftype == 2 || p.skip != 0 || p.o_begin != 0 || p.o_end > p.ifac) { return hipErrorInvalidValue; }   // group 0 of a folded core only
+  dim3 grid((unsigned)((span + 255) / 256), (unsigned)p.n_ch);
+  hipLaunchKernelGGL(polyintr_kernel, grid, dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
 hipError_t launch_polyintr(const PolyIntrParams &p, int64_t *saved_next, hipStream_t s) {
   const int64_t span = p.o_end - p.o_begin;
   if (span > 0) {

@@ -466,10 +466,10 @@ POLY_FTYPES = {"FOLD_EVEN": 0, "FOLD_ODD": 1, "FOLD_ANTI": 2}   # the enum of ac
 class PolyIntr:
     """n_channels independent ac_poly_intr objects (C ABI acdsp_polyintr_*): IF outputs per input sample."""
 
-    def __init__(self, n_taps, coeff_sz, ifac, ftype, fin, fcoeff, facc, fout, n_channels=1, device=0):
+    def __init__(self, n_taps, coeff_sz, ifac, ftype, fin, fcoeff, facc, fout, n_channels=1, device=0, force_generic=False):
         self.fin, self.fout, self.n_channels, self.coeff_sz, self.ifac = fin, fout, n_channels, coeff_sz, ifac
         d = PolyIntrDesc(n_taps, coeff_sz, ifac, POLY_FTYPES[ftype] if isinstance(ftype, str) else ftype, n_channels, fin, fcoeff,
-                         facc, fout, device, 0)
+                         facc, fout, device, _lib.FLAG_FORCE_GENERIC if force_generic else 0)
         self._h = C.c_void_p()
         check(lib.acdsp_polyintr_create(C.byref(d), C.byref(self._h)))
 
@@ -484,11 +484,13 @@ class PolyIntr:
     def out_count(self, n_in):
         return lib.acdsp_polyintr_out_count(self._h, n_in)
 
-    def run(self, x):
+    def run(self, x, out=None):
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_channels and x.stride(1) == 1
         assert x.dtype == torch_dtype_for(self.fin), (x.dtype, self.fin)
         no = self.out_count(x.shape[1])
-        out = torch.empty((self.n_channels, max(no, 1)), dtype=torch_dtype_for(self.fout), device=x.device)
+        if out is None:
+            out = torch.empty((self.n_channels, max(no, 1)), dtype=torch_dtype_for(self.fout), device=x.device)
+        assert out.shape[0] == self.n_channels and out.shape[1] >= no and out.stride(1) == 1 and out.dtype == torch_dtype_for(self.fout)
         n_out = C.c_int64()
         check(lib.acdsp_polyintr_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), x.shape[1], C.c_void_p(out.data_ptr()),
                                      out.stride(0), C.byref(n_out), _stream_ptr(x)))
@@ -496,8 +498,19 @@ class PolyIntr:
 
     @property
     def path(self):
-        """kernel family of the last run(): "generic", "lossless64" (tiled int64 VALU kernel) or "mfma_gen" (fir_up.hip)"""
+        """kernel family of the last run(): "generic", "lossless64" (tiled int64 VALU kernel), "mfma_gen" (fir_up.hip) or "mfma_long"
+        (polyintr_long.hip: 65 taps per phase and more)"""
         return PATHS[lib.acdsp_polyintr_path(self._h)]
+
+    def set_scratch_cap(self, n_bytes):
+        """long sub-filters: bound the scratch of the phase rows (re-derives the slab / group geometry, reallocates, synchronises)"""
+        check(lib.acdsp_polyintr_set_scratch_cap(self._h, int(n_bytes)))
+
+    def long_geometry(self):
+        """(input samples per slab, channels per group, scratch bytes) of a long handle; (0, 0, 0) otherwise"""
+        slab, group, nbytes = C.c_int64(), C.c_int32(), C.c_uint64()
+        check(lib.acdsp_polyintr_long_geometry(self._h, C.byref(slab), C.byref(group), C.byref(nbytes)))
+        return slab.value, group.value, nbytes.value
 
     def reset(self):
         check(lib.acdsp_polyintr_reset(self._h))

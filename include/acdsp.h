@@ -109,7 +109,10 @@ typedef struct {
  * ftype is THAT header's enum (ac_poly_intr.h:71), not the FIR FTYPE. */
 enum { ACDSP_POLY_FOLD_EVEN = 0, ACDSP_POLY_FOLD_ODD = 1, ACDSP_POLY_FOLD_ANTI = 2 };
 typedef struct {
-  int32_t n_taps;             /* NTAPS: length of the shift register */
+  int32_t n_taps;             /* NTAPS: length of the shift register.  1 .. 2048 for every class; up to 16384 (16383 on the folded cores, whose sums
+                               * leave one sample late) only for descriptors the long matrix-core kernels take (signed samples of up to 16 bits,
+                               * coefficients of up to 16 bits signed / 15 bits unsigned, exact wrapping ACC_TYPE of <= 64 bits, IF * K-blocks per phase <= 1024: INTEGRATION.md
+                               * "Long interpolators"), else acdsp_polyintr_create fails with ACDSP_EUNSUPPORTED */
   int32_t coeff_sz;           /* COEFFSZ: words in the coefficient struct */
   int32_t ifac;               /* IF: interpolation factor = outputs per input sample */
   int32_t ftype;              /* ACDSP_POLY_* */
@@ -317,7 +320,17 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
                            int64_t *n_out, void *stream);
 int32_t acdsp_polyintr_run_host(acdsp_polyintr_t h, const void *h_in, int64_t n_in, void *h_out, int64_t out_cap, int64_t *n_out);
 int32_t acdsp_polyintr_reset(acdsp_polyintr_t h);
-int32_t acdsp_polyintr_path(acdsp_polyintr_t h);   /* kernel family of the last run(): ACDSP_PATH_GENERIC, _LOSSLESS64 or _MFMA_GEN */
+int32_t acdsp_polyintr_path(acdsp_polyintr_t h);   /* kernel family of the last run(): ACDSP_PATH_GENERIC, _LOSSLESS64, _MFMA_GEN or _MFMA_LONG */
+/* Long sub-filters (NTAPS + lag >= 65 taps per phase, lag = 1 on the folded cores; up to 16384) of the exact-accumulation class on 16-bit
+ * types run as IF matrix-core FIRs on the input stream.  Their phase rows go to a scratch buffer owned by the handle, and a second kernel
+ * interleaves them into the caller's rows.  A call is walked as channel groups x time slabs so that the scratch stays under a cap (default
+ * 128 MiB).  set_scratch_cap re-derives the geometry and reallocates (it synchronises the device; not for a capturing stream); on a handle
+ * that is not long it does nothing; if the new buffer cannot be allocated the call fails and cap, geometry and buffer stay as they were.
+ * long_geometry reports input samples per slab, channels per group and the scratch bytes, all zero for a handle that is not long.
+ * Above 2048 taps acdsp_polyintr_set_ctrl refuses (ACDSP_EUNSUPPORTED, the handle keeps its state) control words the long kernels cannot
+ * take: a phase with sign[j] = 0 on the folded cores, sums that may wrap ACC_TYPE, a folded tap outside -32768 .. 32639. */
+int32_t acdsp_polyintr_set_scratch_cap(acdsp_polyintr_t h, uint64_t bytes);
+int32_t acdsp_polyintr_long_geometry(acdsp_polyintr_t h, int64_t *slab_inputs, int32_t *group_channels, uint64_t *scratch_bytes);
 
 /* ---- integrate and dump (reference ac_intg_dump.h:93-147) ----
  * Rows = objects; a row is the interleaved stream the reference reads from data_in (round-major, channel-minor).
