@@ -86,8 +86,10 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
     // two-stage kernel takes over there as well instead of the recurrence kernel)
     const bool one_stage = h->gen_ok && desc->R < 32;
     static const bool no_c2 = getenv("ACDSP_NO_CIC2") != nullptr;         // A/B knob: recurrence kernel as before
+    // (ACDSP_NO_GEN: the two-stage kernel is a multi-plane matrix-core kernel too -- without the check a handle whose one-stage identity the knob
+    // switched off came here instead of to the recurrence kernel, with the longer history of this kernel)
     static const bool c2_all = getenv("ACDSP_CIC2_ALL") != nullptr;       // A/B knob: also where the one-stage FIR identity fits (R < 32)
-    if (!desc->interp && !h->wide && !no_c2 && (desc->R >= 32 || c2_all || !one_stage) && fits_container(desc->in, h->in_eb) && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) &&
+    if (!desc->interp && !h->wide && !no_c2 && !no_gen && (desc->R >= 32 || c2_all || !one_stage) && fits_container(desc->in, h->in_eb) && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) &&
         cic2_factor(h->in_eb, desc->R, h->me, desc->N, &h->c2_R1, &h->c2_R2, &h->c2_wu)) {
       cic2_stage1_taps(h->c2_R1, desc->N, &h->c2_taps);
       h->c2_ok = fir_gen_plan(h->c2_taps.data(), (int)h->c2_taps.size(), h->c2_R1, 15, &probe, &fr) &&
@@ -95,6 +97,7 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
       if (h->c2_ok) {
         const int need = round_up(cic2_hist_len(h->in_eb, h->c2_R1, desc->N, h->c2_wu), kCicTile);
         if (need > h->hl) { h->hl = need; }
+        h->c2_first = c2_all && one_stage;   // (acdsp_cic_run gives the one-stage kernel the first refusal otherwise: the knob chose nothing)
       }
     }
   }
@@ -204,7 +207,7 @@ int acdsp::eng::cic_capture_check(const acdsp_cic *h, const void *d_in, int64_t 
   if (!slots) { return ACDSP_OK; }   // the recurrence kernel: no plan
   const int fm = (int)(((d.R - h->t_total % d.R) % d.R) % 16);
   int st = -1;
-  if (h->gen_ok) { st = h->gen.state(fm); }
+  if (h->gen_ok && !h->c2_first) { st = h->gen.state(fm); }
   if (st < 0 && h->c2_ok) { st = h->c2.state(fm); }
   if (st == 0) {
     return fail(ACDSP_ESTATE, "cic_run under graph capture: the matrix-core plan of window phase %d (t_total %% R = %lld) is not on the device yet and its upload "
@@ -250,7 +253,7 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   if (chunk < floor_chunk) { chunk = floor_chunk; }
   p.chunk = (chunk + kCicTile - 1) / kCicTile * kCicTile;
   // decimator on the matrix cores when the FIR identity fits and the rows are slot-aligned
-  bool use_gen = h->gen_ok && !d.interp && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
+  bool use_gen = h->gen_ok && !h->c2_first && !d.interp && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
   const uint32_t *gfrag = nullptr, *c2frag = nullptr;
   const FirGenPlan *gpl = nullptr, *c2pl = nullptr;
   const int fm = (int)(p.first % 16);

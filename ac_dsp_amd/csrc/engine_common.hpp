@@ -423,6 +423,7 @@ struct acdsp_cic {
   PhasePlans gen;
   // decimator in two stages (cic2.hip): R = c2_R1 * c2_R2, stage-1 taps z^-(N-1) boxcar(R1)^N with their per (first mod 16) plans / fragments
   bool c2_ok = false;
+  bool c2_first = false;   // ACDSP_CIC2_ALL: the two-stage kernel goes first where the one-stage identity (gen_ok) would serve the handle too
   int c2_R1 = 0, c2_R2 = 0, c2_wu = 0;
   std::vector<int64_t> c2_taps;
   PhasePlans c2;

@@ -75,7 +75,7 @@ def test_fused_cascade_state_carries_across_calls_and_decimation_phases():
     assert np.array_equal(run_ddc(ddc, x[:, :16 * 1024]), yo[:, :1024])
 
 
-def test_other_shapes_take_the_two_kernels_and_match(monkeypatch):
+def test_other_shapes_take_the_two_kernels_and_match():
     # 8-bit narrower decimator (R = 8 on <32,16>): int32 input containers -> not the fused shape class
     cin, fc, fa, fo = A.Fmt(32, 16), A.Fmt(16, 1), A.Fmt(64, 31), A.Fmt(32, 16, True, "RND", "SAT")
     rng = np.random.default_rng(19)
@@ -87,14 +87,16 @@ def test_other_shapes_take_the_two_kernels_and_match(monkeypatch):
     y = run_ddc(ddc, x, [8 * 1000])
     yo = oracle_cascade(8, 1, 5, cin, ddc.int_type, 63, "SHIFT_REG", fc, fa, fo, c, x, [8 * 1000])
     assert np.array_equal(y, yo)
-    # the config-5 shape forced onto the two kernels gives the same stream as the fused kernel
-    monkeypatch.setenv("ACDSP_NO_FUSE", "1")
+    # the config-5 shape on the same stream lengths: the fused kernel again (a second fused case).  ACDSP_NO_FUSE cannot force it onto the two
+    # kernels from inside this process -- the library read the variable at the first acdsp_ddc_create -- so that leg runs in a process of its
+    # own: tests/test_knobs_gpu.py, row ACDSP_NO_FUSE of tests/knob_legs.py (path "two_kernels" there against "fused" here)
     g = CFG5
     fo5 = A.Fmt(24, 9, True, "RND", "SAT")
     x5 = rng.integers(-32768, 32768, size=(2, 16 * 3000))
     c5 = windowed_sinc(127, 0.2, g["fc"])
     d2 = A.Ddc(16, 1, 5, g["cin"], 127, "SHIFT_REG", g["fc"], g["fa"], fo5, n_channels=2)
     d2.set_coeffs(c5)
+    assert d2.path == "fused"
     yo5 = oracle_cascade(16, 1, 5, g["cin"], d2.int_type, 127, "SHIFT_REG", g["fc"], g["fa"], fo5, c5, x5)
     assert np.array_equal(run_ddc(d2, x5), yo5)
 
