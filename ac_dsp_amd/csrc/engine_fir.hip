@@ -164,8 +164,8 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   const bool lossless = fir_exact_shape(*desc) && (!h->use_rt || h->rt_hybrid) && !h->wide;   // (the overflow mode: below)
   h->lossless_shape = lossless;
   h->long_shape = desc->n_taps >= kFirLongMinTaps && fir_long_refusal(*desc) == nullptr;
-  // the long kernel's first step reaches 32 (NB - 1) samples back, NB = ceil((n_taps - 1) / 32) + 1
-  if (h->long_shape && h->hl < 32 * ((desc->n_taps - 1 + 31) / 32)) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
+  // the long kernel's first step reaches 32 (NB - 1) samples back
+  if (h->long_shape && h->hl < 32 * (long_blocks(desc->n_taps) - 1)) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
   h->sat_free = false;
   h->lossless = lossless && desc->acc.O == ACDSP_WRAP;
   h->coeffs_set = false;

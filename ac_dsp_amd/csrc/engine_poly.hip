@@ -19,7 +19,7 @@ struct acdsp_polydec {
   // long_ok = the current set runs there.  The scratch of the phase streams is sized at create / set_scratch_cap, never in run()
   bool long_shape = false, long_ok = false, in_flip = false;
   PolyDecLongPlan lplan;
-  PolyDecLongGeom lgeo = {0, 0, 0};
+  LongGeom lgeo = {0, 0, 0};
   uint64_t scratch_cap = (uint64_t)128 << 20;
   DevBuf d_lfrag, d_lcorr, d_scratch;
   int last_path = ACDSP_PATH_GENERIC;
@@ -44,7 +44,8 @@ const char *polydec_long_refusal(const acdsp_polydec_desc_t &d) {
 // scratch of a long handle under `cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a
 // failure leaves cap, geometry and scratch as they were
 int polydec_size_scratch(acdsp_polydec *h, uint64_t cap) {
-  const PolyDecLongGeom geo = polydec_long_geometry(h->d.n_taps, h->d.df, h->d.n_channels, cap);
+  // phase rows of int16: df * 2 bytes per slab output, in front of them the reach of 32 (nb - 1) samples
+  const LongGeom geo = long_geometry((uint64_t)h->d.df * 2, 32 * (uint64_t)(long_blocks(h->d.n_taps) - 1), h->d.n_channels, cap);
   DevBuf fresh;
   const int rc = fresh.alloc(geo.bytes);
   if (rc) { return rc; }
@@ -98,7 +99,7 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
   h->long_shape = !long_why && !fir_gen_window(desc->n_taps * desc->df, desc->df, (desc->df - 1) % 16, &g_off, &g_nb);
   if (h->long_shape) {
     h->in_flip = !desc->in.S && desc->in.W == 16;   // unsigned 16-bit samples: read as x - 32768, 32768 * sum(c) rides in the correction constant
-    if ((rc = h->d_lfrag.alloc((size_t)2 * desc->df * polydec_long_blocks(desc->n_taps) * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc(sizeof(int64_t))) ||
+    if ((rc = h->d_lfrag.alloc((size_t)2 * desc->df * long_blocks(desc->n_taps) * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc(sizeof(int64_t))) ||
         (rc = polydec_size_scratch(h.get(), h->scratch_cap))) {
       return rc;
     }
@@ -281,7 +282,7 @@ struct acdsp_polyintr {
   // there.  The scratch of the phase rows is sized at create / set_scratch_cap, never in run()
   bool long_shape = false, long_ok = false;
   PolyIntrLongPlan lplan;
-  PolyIntrLongGeom lgeo = {0, 0, 0};
+  LongGeom lgeo = {0, 0, 0};
   uint64_t scratch_cap = (uint64_t)128 << 20;
   DevBuf d_lfrag, d_lcorr, d_lhalve, d_scratch;
   int last_path = ACDSP_PATH_GENERIC;
@@ -309,14 +310,15 @@ const char *polyintr_long_refusal(const acdsp_polyintr_desc_t &d) {
   if (!polyintr_lossless_desc(d)) {
     return "an ACC_TYPE that is not an exact accumulator (signed AC_WRAP, F_acc >= F_in + F_coeff, I_acc >= I_in + 1, W_acc <= 64)";
   }
-  if ((int64_t)d.ifac * polyintr_long_blocks(nt) > kPolyIntrLongMaxBlocks) { return "IF * K-blocks per phase above the K-block budget of 1024"; }
+  if ((int64_t)d.ifac * long_blocks(nt) > kPolyIntrLongMaxBlocks) { return "IF * K-blocks per phase above the K-block budget of 1024"; }
   return nullptr;
 }
 
 // scratch of a long handle under `cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a
 // failure leaves cap, geometry and scratch as they were
 int polyintr_size_scratch(acdsp_polyintr *h, uint64_t cap) {
-  const PolyIntrLongGeom geo = polyintr_long_geometry(h->d.ifac, h->out_eb, h->d.n_channels, cap);
+  // phase rows of OUT containers: ifac * out_eb bytes per slab input sample, no head
+  const LongGeom geo = long_geometry((uint64_t)h->d.ifac * h->out_eb, 0, h->d.n_channels, cap);
   DevBuf fresh;
   const int rc = fresh.alloc(geo.bytes);
   if (rc) { return rc; }
@@ -430,7 +432,7 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
   if ((rc = h->d_coeffs.alloc((size_t)d.coeff_sz * sizeof(int64_t))) || (rc = h->d_sign.alloc((size_t)d.ifac)) || (rc = h->d_corr.alloc((size_t)d.ifac))) { return rc; }
   h->long_shape = long_why == nullptr;
   if (h->long_shape) {
-    const int nb = polyintr_long_blocks(d.n_taps + polyintr_lag(d));
+    const int nb = long_blocks(d.n_taps + polyintr_lag(d));
     // a step reaches 32 (nb - 1) samples back: inside the history as far as real taps go (nt - 1 <= NTAPS), beyond it over zero-padded taps only
     if (h->hl < d.n_taps || h->hl % 32 || 32 * (nb - 1) > h->hl) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
     if ((rc = h->d_lfrag.alloc((size_t)2 * d.ifac * nb * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc((size_t)d.ifac * sizeof(int64_t))) ||

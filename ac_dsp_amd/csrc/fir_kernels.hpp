@@ -68,8 +68,9 @@ hipError_t launch_fir_mfma(const FirParams &p, const FirMfmaPlan &plan, int frag
 
 // Long filters (1026 .. 16384 taps) of the same int8-split formulation (fir_long.hip): 34 .. 513 K-blocks, walked in LDS segments
 constexpr int kFirLongMinTaps = 1026, kFirLongMaxTaps = 16384;
+int long_blocks(int taps);   // K-blocks of `taps` taps in the long kernels: max(2, ceil((taps-1)/32) + 1), never padded; the reach is 32 (nb - 1) samples
 struct FirLongPlan {
-  int32_t nb;                  // K-blocks = ceil((n_taps-1)/32) + 1, never padded
+  int32_t nb;                  // long_blocks(n_taps)
   int32_t hb0, hb1;            // K-blocks [hb0, hb1] hold every non-zero high coefficient byte (hb0 > hb1: the set has none)
   int64_t corr;                // 128 * sum(c)
 };
@@ -77,6 +78,25 @@ struct FirLongPlan {
 bool fir_long_plan(const int64_t *coeffs, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag);
 int fir_long_issued_per_step(const FirLongPlan &plan);   // two low-plane products per K-block + two per K-block of [hb0, hb1]
 hipError_t launch_fir_long(const FirParams &p, const FirLongPlan &plan, const uint32_t *d_frag, const int64_t *d_corr, hipStream_t s);
+// The polyphase long kernels (polydec_long.hip, polyintr_long.hip) walk `phases` filters of nt taps each per step.  host: c = [phases][nt]
+// taps -> fragments frag[2][phases * long_blocks(nt)][64][4] and the per-phase corrections 128 * sum(c_d); false if a tap cannot be split
+// into two signed bytes
+bool long_phase_fragments(const int64_t *c, int phases, int nt, std::vector<uint32_t> *frag, std::vector<int64_t> *corr);
+// A polyphase call is walked as channel groups x time slabs under a scratch cap.  With b(G) = sample_bytes * (head + G) bytes of phase rows
+// per channel: group = n_ch if n_ch * b(1024) <= cap, else the largest multiple of 8 that fits (at least 8); slab = the largest multiple of
+// 1024 with group * b(slab) <= cap, inside 1024 .. 65536; bytes = group * b(slab), the scratch the launches need
+struct LongGeom {
+  int64_t slab;
+  int32_t group;
+  uint64_t bytes;
+};
+LongGeom long_geometry(uint64_t sample_bytes, uint64_t head, int n_ch, uint64_t cap);
+// Grid of a long kernel over n_steps steps of `rows` rows: eight rows x steps_per_wave steps per workgroup, steps_per_wave >= min_steps
+struct LongGrid {
+  int64_t steps_per_wave;
+  unsigned gx, gy;
+};
+LongGrid long_grid(int64_t n_steps, int rows, int64_t min_steps);
 
 // Generalised exact FIR on the matrix cores (fir_gen.hip): wide inputs / coefficients, decimation.
 // FirParams::ftype values of the ac_fir_reg_share cores (ascending MAC order, anti-symmetric folds:
@@ -255,24 +275,14 @@ hipError_t launch_polydec_generic(const FirParams &p, int ntaps, int df, int64_t
 // the phase streams z_d[m] = x[m DF + DF-1 - d], which a first kernel writes into a scratch of the handle
 constexpr int kPolyDecLongMaxTaps = 16384, kPolyDecLongMaxDf = 256;
 struct PolyDecLongPlan {
-  int32_t ntaps, df, nb;       // nb = K-blocks per phase = max(2, ceil((ntaps-1)/32) + 1); the phase rows reach 32 (nb - 1) samples back
+  int32_t ntaps, df, nb;       // nb = K-blocks per phase = long_blocks(ntaps); the phase rows reach 32 (nb - 1) samples back
   int64_t corr;                // 128 * sum(c) over all phases
 };
-int polydec_long_blocks(int ntaps);
 // host: fragments frag[2][df * nb][64][4] of c[tp + ntaps * d] and the plan; false if a coefficient cannot be split into two signed bytes
 bool polydec_long_plan(const int64_t *coeffs, int ntaps, int df, PolyDecLongPlan *plan, std::vector<uint32_t> *frag);
-// A call is walked as channel groups x time slabs.  With b(G) = df * (32 (nb - 1) + G) * 2 bytes per channel: group = n_ch if n_ch * b(1024)
-// <= cap, else the largest multiple of 8 that fits (at least 8); slab = the largest multiple of 1024 with group * b(slab) <= cap, inside
-// 1024 .. 65536; bytes = group * b(slab), the scratch the launches need
-struct PolyDecLongGeom {
-  int64_t slab;
-  int32_t group;
-  uint64_t bytes;
-};
-PolyDecLongGeom polydec_long_geometry(int ntaps, int df, int n_ch, uint64_t cap);
-// p.n = inputs, p.x / p.hist / p.y as for the other kernels (2-byte IN containers, rows at any element-aligned address); two launches per
-// slab of a group, no allocation and no synchronisation
-hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, const PolyDecLongGeom &geo, const uint32_t *d_frag,
+// p.n = inputs, p.x / p.hist / p.y as for the other kernels (2-byte IN containers, rows at any element-aligned address); geo = long_geometry
+// with df * 2 bytes per slab output and a head of 32 (nb - 1) samples; two launches per slab of a group, no allocation and no synchronisation
+hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, const LongGeom &geo, const uint32_t *d_frag,
                                const int64_t *d_corr, void *d_scratch, int64_t n_out, hipStream_t s);
 
 // Long polyphase interpolators (polyintr_long.hip): 65 .. 16384 taps per phase, IF up to 255, as IF Toeplitz products of fir_long.hip's int8
@@ -282,27 +292,17 @@ constexpr int kPolyIntrLongMinTaps = 65, kPolyIntrLongMaxTaps = 16384;   // taps
 // measured.  Admits every 16384-tap prototype from 16383 x 1 to 64 x 255
 constexpr int kPolyIntrLongMaxBlocks = 1024;
 struct PolyIntrLongPlan {
-  int32_t nt, ifac, nb;        // nb = K-blocks per phase = max(2, ceil((nt-1)/32) + 1); a step reaches 32 (nb - 1) samples back
+  int32_t nt, ifac, nb;        // nb = K-blocks per phase = long_blocks(nt); a step reaches 32 (nb - 1) samples back
 };
-int polyintr_long_blocks(int nt);
 // host: E = [ifac][nt] taps, halve = [ifac] flags -> fragments frag[2][ifac * nb][64][4], the per-phase corrections 128 * sum(E_j) and the
 // flags as uploaded; false if a tap cannot be split into two signed bytes or the shape is outside the limits above
 bool polyintr_long_plan(const int64_t *E, int ifac, int nt, const uint8_t *halve, PolyIntrLongPlan *plan, std::vector<uint32_t> *frag,
                         std::vector<int64_t> *corr, std::vector<uint8_t> *flags);
-// A call is walked as channel groups x time slabs.  With b(G) = ifac * G * out_eb bytes per channel: group = n_ch if n_ch * b(1024) <= cap,
-// else the largest multiple of 8 that fits (at least 8); slab = the largest multiple of 1024 input samples with group * b(slab) <= cap,
-// inside 1024 .. 65536; bytes = group * b(slab), the scratch the launches need.  (group <= n_ch <= 65535, which create enforces: the merge
-// kernel's grid has one row per group channel)
-struct PolyIntrLongGeom {
-  int64_t slab;
-  int32_t group;
-  uint64_t bytes;
-};
-PolyIntrLongGeom polyintr_long_geometry(int ifac, int out_eb, int n_ch, uint64_t cap);
 // p.n = inputs, p.x / p.hist / p.y as for the other kernels (2-byte IN containers, rows at any element-aligned address and stride).  Output
-// (input n, phase j) = (n - skip) ifac + j; the outputs [o_lo, n_out) of the call are written.  Two launches per slab of a group, no
-// allocation and no synchronisation
-hipError_t launch_polyintr_long(const FirParams &p, const PolyIntrLongPlan &plan, const PolyIntrLongGeom &geo, const uint32_t *d_frag,
+// (input n, phase j) = (n - skip) ifac + j; the outputs [o_lo, n_out) of the call are written.  geo = long_geometry with ifac * out_eb bytes
+// per slab input sample and no head (group <= n_ch <= 65535, which create enforces: the merge kernel's grid has one row per group channel).
+// Two launches per slab of a group, no allocation and no synchronisation
+hipError_t launch_polyintr_long(const FirParams &p, const PolyIntrLongPlan &plan, const LongGeom &geo, const uint32_t *d_frag,
                                 const int64_t *d_corr, const uint8_t *d_halve, void *d_scratch, int skip, int64_t o_lo, int64_t n_out,
                                 hipStream_t s);
 

@@ -1,4 +1,5 @@
-// fir_long.hip -- long 16-bit FIRs (1026 .. 16384 taps) on the gfx950 matrix cores, exact integer arithmetic.
+// fir_long.hip -- long 16-bit FIRs (1026 .. 16384 taps) on the gfx950 matrix cores, exact integer arithmetic; and the host helpers the three
+// long units share (long_blocks, long_phase_fragments, long_geometry, long_grid).  The segment geometry kLong* is in fir_long_kernels.hpp.
 //
 // The formulation is that of fir_mfma_kernels.hpp (header comment there): one step is 1024 consecutive outputs of one channel, the 32 MFMA columns
 // are 32 consecutive output blocks, K-block b of the [32 x 32 NB] Toeplitz matrix meets "input chunk n + b", both operands are split into
@@ -26,26 +27,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "fir_kernels.hpp"
+#include "fir_long_kernels.hpp"
 
 namespace acdsp {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-constexpr int kLongSB = 16;                          // K-blocks per LDS segment
-constexpr int kLongNC = 32 + kLongSB - 1;            // chunks (32 samples) of a segment's sample window
-constexpr int kLongNP = 4 * kLongNC;                 // 16-byte loads of the window
-constexpr int kLongJN = (kLongNP + 63) / 64;         // ... per lane
-// one staged [plane][half] array of kLongNC 16-byte chunks (fir_mfma_kernels.hpp, staged_array_bytes: size = 64 mod 128 keeps the halves 16 banks apart)
-constexpr int kLongARR = ((kLongNC * 16 + 63) / 128) * 128 + 64;
-constexpr int kLongAWords = 2 * kLongSB * 64;        // v4i words of one A segment: [plane][block][lane]
-constexpr int kLongAPerThread = kLongAWords / 512;   // = 4
-constexpr int kLongXBytes = 4 * kLongARR;            // one staged window of a wave
-constexpr size_t kLongLdsBytes = (size_t)2 * kLongAWords * 16 + (size_t)8 * 2 * kLongXBytes;
-static_assert(kLongAWords % 512 == 0, "an A segment is copied by 512 threads in whole passes");
-static_assert(kLongARR >= kLongNC * 16, "staged array holds the window");
-static_assert(kLongLdsBytes <= 160 * 1024, "LDS of one gfx950 CU");
 
 struct LongArgs {
   int64_t steps_per_wave;   // 1024-sample steps per workgroup row
@@ -173,9 +157,55 @@ fir_long_kernel(FirParams p, const v4i *__restrict__ frag, LongArgs a) {
   }
 }
 
+int long_blocks(int taps) {
+  const int nb = (taps - 1 + 31) / 32 + 1;
+  return nb < 2 ? 2 : nb;
+}
+
+bool long_phase_fragments(const int64_t *c, int phases, int nt, std::vector<uint32_t> *frag, std::vector<int64_t> *corr) {
+  const int nb = long_blocks(nt);
+  const size_t blk = (size_t)64 * 4, plane = (size_t)phases * nb * blk;
+  frag->assign(2 * plane, 0u);
+  corr->assign((size_t)phases, 0);
+  std::vector<uint32_t> one((size_t)2 * nb * blk);
+  for (int d = 0; d < phases; d++) {
+    FirMfmaPlan mp;
+    if (!fir_mfma_build_fragments_nb(c + (size_t)nt * d, nt, nb, &mp, one.data())) { return false; }
+    (*corr)[(size_t)d] = mp.corr;
+    for (int pl = 0; pl < 2; pl++) {   // [plane][nb] of the phase -> [plane][d][nb] of the set
+      std::copy(one.begin() + (size_t)pl * nb * blk, one.begin() + (size_t)(pl + 1) * nb * blk, frag->begin() + pl * plane + (size_t)d * nb * blk);
+    }
+  }
+  return true;
+}
+
+LongGeom long_geometry(uint64_t sample_bytes, uint64_t head, int n_ch, uint64_t cap) {
+  auto b = [&](uint64_t G) { return sample_bytes * (head + G); };   // bytes of one channel's phase rows
+  uint64_t C = (uint64_t)n_ch;
+  if (C * b(1024) > cap) {
+    C = cap / b(1024) / 8 * 8;
+    if (C < 8) { C = 8; }
+    if (C > (uint64_t)n_ch) { C = (uint64_t)n_ch; }
+  }
+  // largest multiple of 1024 with C * b(G) <= cap, inside 1024 .. 65536
+  const uint64_t fit = cap / (C * sample_bytes);   // slab samples + head that fit
+  uint64_t G = fit > head ? (fit - head) / 1024 * 1024 : 0;
+  if (G < 1024) { G = 1024; }
+  if (G > 65536) { G = 65536; }
+  return {(int64_t)G, (int32_t)C, C * b(G)};
+}
+
+LongGrid long_grid(int64_t n_steps, int rows, int64_t min_steps) {
+  // a workgroup is eight rows x steps_per_wave steps; >= 2048 workgroups (8 per CU) when the problem allows it
+  const int64_t wg_rows = ((int64_t)rows + 7) / 8;
+  int64_t spw = (n_steps * wg_rows + 2047) / 2048;
+  if (spw < min_steps) { spw = min_steps; }
+  return {spw, (unsigned)((n_steps + spw - 1) / spw), (unsigned)wg_rows};
+}
+
 bool fir_long_plan(const int64_t *c, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag) {
   if (n_taps < kFirLongMinTaps || n_taps > kFirLongMaxTaps) { return false; }
-  const int nb = (n_taps - 1 + 31) / 32 + 1;
+  const int nb = long_blocks(n_taps);
   frag->assign((size_t)2 * nb * 64 * 4, 0u);
   FirMfmaPlan mp;
   if (!fir_mfma_build_fragments_nb(c, n_taps, nb, &mp, frag->data())) { return false; }
@@ -209,18 +239,14 @@ hipError_t launch_fir_long(const FirParams &p, const FirLongPlan &plan, const ui
   LongArgs a;
   a.n_steps = (p.n + 1023) / 1024;
   a.n8 = (p.n + 7) / 8 * 8;
-  // a workgroup is eight channels x steps_per_wave steps; >= 2048 workgroups (8 per CU) when the problem allows it, at least 8 steps each
-  const int64_t rows = ((int64_t)p.n_ch + 7) / 8;
-  int64_t spw = (a.n_steps * rows + 2047) / 2048;
-  if (spw < 8) { spw = 8; }
-  a.steps_per_wave = spw;
+  const LongGrid lg = long_grid(a.n_steps, p.n_ch, 8);   // at least 8 steps each
+  a.steps_per_wave = lg.steps_per_wave;
   a.nb = plan.nb; a.hb0 = plan.hb0; a.hb1 = plan.hb1;
   a.hi_xor = p.in_flip ? 0x80808080u : 0u;
   a.corr = d_corr;
-  const dim3 grid((unsigned)((a.n_steps + spw - 1) / spw), (unsigned)rows);
   hipError_t e = hipFuncSetAttribute((const void *)fir_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes);
   if (e != hipSuccess) { return e; }
-  hipLaunchKernelGGL(fir_long_kernel, grid, dim3(512), kLongLdsBytes, s, p, (const v4i *)d_frag, a);
+  hipLaunchKernelGGL(fir_long_kernel, dim3(lg.gx, lg.gy), dim3(512), kLongLdsBytes, s, p, (const v4i *)d_frag, a);
   return hipGetLastError();
 }
 

@@ -27,28 +27,12 @@
 // Barrier uniformity, as in fir_long.hip: the loop that contains the barrier runs nsteps * DF * NSEG times; DF and NSEG are launch
 // arguments, nsteps follows from launch arguments and blockIdx.  A wave's channel is clamped to the group's last one, never exited.
 #include <cstdlib>
+#include <numeric>
 #include <vector>
 
-#include "fir_kernels.hpp"
+#include "fir_long_kernels.hpp"
 
 namespace acdsp {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-// the segment geometry of fir_long.hip (kLongSB .. kLongLdsBytes there)
-constexpr int kDecSB = 16;                         // K-blocks per LDS segment
-constexpr int kDecNC = 32 + kDecSB - 1;            // chunks (32 samples) of a segment's sample window
-constexpr int kDecNP = 4 * kDecNC;                 // 16-byte loads of the window
-constexpr int kDecJN = (kDecNP + 63) / 64;         // ... per lane
-constexpr int kDecARR = ((kDecNC * 16 + 63) / 128) * 128 + 64;   // one staged [plane][half] array (size = 64 mod 128: the halves sit 16 banks apart)
-constexpr int kDecAWords = 2 * kDecSB * 64;        // v4i words of one A segment: [plane][block][lane]
-constexpr int kDecAPerThread = kDecAWords / 512;   // = 4
-constexpr int kDecXBytes = 4 * kDecARR;            // one staged window of a wave
-constexpr size_t kDecLdsBytes = (size_t)2 * kDecAWords * 16 + (size_t)8 * 2 * kDecXBytes;
-static_assert(kDecAWords % 512 == 0, "an A segment is copied by 512 threads in whole passes");
-static_assert(kDecARR >= kDecNC * 16, "staged array holds the window");
-static_assert(kDecLdsBytes <= 160 * 1024, "LDS of one gfx950 CU");
 
 // ---------------------------------------------------------------------------------------------
 // kernel 1: phase split
@@ -122,7 +106,7 @@ struct LongDecArgs {
 __global__ void __launch_bounds__(512, 1)
 fir_long_dec_kernel(FirParams p, const v4i *__restrict__ frag, LongDecArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-  const int NB = a.nb, NSEG = (NB + kDecSB - 1) / kDecSB, DF = a.df;
+  const int NB = a.nb, NSEG = (NB + kLongSB - 1) / kLongSB, DF = a.df;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n_col = lane & 31, h = lane >> 5;
   int chl = blockIdx.y * 8 + wave;
@@ -130,7 +114,7 @@ fir_long_dec_kernel(FirParams p, const v4i *__restrict__ frag, LongDecArgs a) {
   const int ch = a.ch0 + chl;
   // LDS: [2 A segments: 2 planes x 16 blocks x 1 KB][per wave: 2 staged windows of 4 arrays]
   v4i *ldsA = (v4i *)lds_all;
-  unsigned char *ldsX = lds_all + (size_t)2 * kDecAWords * 16 + (size_t)wave * 2 * kDecXBytes;
+  unsigned char *ldsX = lds_all + (size_t)2 * kLongAWords * 16 + (size_t)wave * 2 * kLongXBytes;
 
   const int16_t *zch = a.z + (int64_t)chl * DF * a.L;
   // loop bounds: launch arguments and blockIdx only (see "Barrier uniformity" above)
@@ -140,45 +124,45 @@ fir_long_dec_kernel(FirParams p, const v4i *__restrict__ frag, LongDecArgs a) {
   const int total = nsteps * DF * NSEG;
   const size_t plane_words = (size_t)DF * NB * 64;
 
-  v4i RA[kDecAPerThread], RX[kDecJN];
+  v4i RA[kLongAPerThread], RX[kLongJN];
   // global loads of iteration (step s, phase d, segment g): this thread's share of the A segment, this lane's share of the wave's window
   auto issue_loads = [&](int s, int d, int g) {
 #pragma unroll
-    for (int q = 0; q < kDecAPerThread; q++) {
-      const int idx = threadIdx.x + 512 * q, pl = idx / (kDecSB * 64), bl = (idx >> 6) % kDecSB, ln = idx & 63;
-      int bg = g * kDecSB + bl;
+    for (int q = 0; q < kLongAPerThread; q++) {
+      const int idx = threadIdx.x + 512 * q, pl = idx / (kLongSB * 64), bl = (idx >> 6) % kLongSB, ln = idx & 63;
+      int bg = g * kLongSB + bl;
       if (bg >= NB) { bg = NB - 1; }   // blocks past the phase in its last segment: never multiplied, any in-bounds fragment will do
       RA[q] = frag[(size_t)pl * plane_words + ((size_t)d * NB + bg) * 64 + ln];
     }
     // the window of segment g starts 32 * 16 g elements behind the step's first one; the chunks a product reads end at H + 1024 (s0 + s + 1)
     // <= L, the others are clamped to the row's start.  e and L are multiples of 8: a load never straddles the end of the row
     const int16_t *zrow = zch + (int64_t)d * a.L;
-    const int64_t base = (s0 + s) * 1024 + 32 * kDecSB * (int64_t)g;
+    const int64_t base = (s0 + s) * 1024 + 32 * kLongSB * (int64_t)g;
 #pragma unroll
-    for (int j = 0; j < kDecJN; j++) {
-      const int pc = (lane + 64 * j < kDecNP) ? lane + 64 * j : kDecNP - 1;
+    for (int j = 0; j < kLongJN; j++) {
+      const int pc = (lane + 64 * j < kLongNP) ? lane + 64 * j : kLongNP - 1;
       const int64_t e = base + 8 * pc;
       RX[j] = *(const v4i *)(zrow + ((e < a.L) ? e : 0));
     }
   };
   // registers -> LDS: the A segment (all waves, read after the barrier) and the wave's byte planes
   auto commit = [&](int buf) {
-    v4i *dstA = ldsA + buf * kDecAWords;
+    v4i *dstA = ldsA + buf * kLongAWords;
 #pragma unroll
-    for (int q = 0; q < kDecAPerThread; q++) { dstA[threadIdx.x + 512 * q] = RA[q]; }
-    unsigned char *xb = ldsX + buf * kDecXBytes;
+    for (int q = 0; q < kLongAPerThread; q++) { dstA[threadIdx.x + 512 * q] = RA[q]; }
+    unsigned char *xb = ldsX + buf * kLongXBytes;
 #pragma unroll
-    for (int j = 0; j < kDecJN; j++) {
+    for (int j = 0; j < kLongJN; j++) {
       const int pc = lane + 64 * j;
-      if (pc < kDecNP) {
+      if (pc < kLongNP) {
         const int c = pc >> 2, hh_ = (pc >> 1) & 1, sub = pc & 1;
         const unsigned hi0 = __builtin_amdgcn_perm((unsigned)RX[j].y, (unsigned)RX[j].x, 0x07050301u) ^ a.hi_xor;
         const unsigned hi1 = __builtin_amdgcn_perm((unsigned)RX[j].w, (unsigned)RX[j].z, 0x07050301u) ^ a.hi_xor;
         const unsigned lo0 = __builtin_amdgcn_perm((unsigned)RX[j].y, (unsigned)RX[j].x, 0x06040200u) ^ 0x80808080u;
         const unsigned lo1 = __builtin_amdgcn_perm((unsigned)RX[j].w, (unsigned)RX[j].z, 0x06040200u) ^ 0x80808080u;
         typedef unsigned v2u __attribute__((ext_vector_type(2)));
-        *(v2u *)(xb + (0 * 2 + hh_) * kDecARR + c * 16 + sub * 8) = (v2u){hi0, hi1};
-        *(v2u *)(xb + (1 * 2 + hh_) * kDecARR + c * 16 + sub * 8) = (v2u){lo0, lo1};
+        *(v2u *)(xb + (0 * 2 + hh_) * kLongARR + c * 16 + sub * 8) = (v2u){hi0, hi1};
+        *(v2u *)(xb + (1 * 2 + hh_) * kLongARR + c * 16 + sub * 8) = (v2u){lo0, lo1};
       }
     }
   };
@@ -198,11 +182,11 @@ fir_long_dec_kernel(FirParams p, const v4i *__restrict__ frag, LongDecArgs a) {
     __syncthreads();
 
     if (d == 0 && g == 0) { hh = (v16i){0}; mid = (v16i){0}; ll = (v16i){0}; }
-    const int b0 = g * kDecSB, nbs = (NB - b0 < kDecSB) ? NB - b0 : kDecSB;
-    const v4i *ah = ldsA + buf * kDecAWords + lane, *al = ah + kDecSB * 64;
-    const unsigned char *xb = ldsX + buf * kDecXBytes;
-    const unsigned char *fh = xb + (0 * 2 + h) * kDecARR + n_col * 16;   // chunk n_col + bl <= 46
-    const unsigned char *fl = xb + (1 * 2 + h) * kDecARR + n_col * 16;
+    const int b0 = g * kLongSB, nbs = (NB - b0 < kLongSB) ? NB - b0 : kLongSB;
+    const v4i *ah = ldsA + buf * kLongAWords + lane, *al = ah + kLongSB * 64;
+    const unsigned char *xb = ldsX + buf * kLongXBytes;
+    const unsigned char *fh = xb + (0 * 2 + h) * kLongARR + n_col * 16;   // chunk n_col + bl <= 46
+    const unsigned char *fl = xb + (1 * 2 + h) * kLongARR + n_col * 16;
     v4i Ahc = ah[0], Alc = al[0], Bhc = *(const v4i *)fh, Blc = *(const v4i *)fl;
     for (int bl = 0; bl < nbs; bl++) {
       v4i Ahn = Ahc, Aln = Alc, Bhn = Bhc, Bln = Blc;
@@ -240,55 +224,21 @@ fir_long_dec_kernel(FirParams p, const v4i *__restrict__ frag, LongDecArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-int polydec_long_blocks(int ntaps) {
-  const int nb = (ntaps - 1 + 31) / 32 + 1;
-  return nb < 2 ? 2 : nb;
-}
-
 bool polydec_long_plan(const int64_t *c, int ntaps, int df, PolyDecLongPlan *plan, std::vector<uint32_t> *frag) {
   if (ntaps < 1 || df < 1 || df > kPolyDecLongMaxDf || (int64_t)ntaps * df > kPolyDecLongMaxTaps) { return false; }
-  const int nb = polydec_long_blocks(ntaps);
-  const size_t blk = (size_t)64 * 4, plane = (size_t)df * nb * blk;
-  frag->assign(2 * plane, 0u);
-  std::vector<uint32_t> one((size_t)2 * nb * blk);
-  int64_t corr = 0;
-  for (int d = 0; d < df; d++) {
-    FirMfmaPlan mp;
-    if (!fir_mfma_build_fragments_nb(c + (size_t)ntaps * d, ntaps, nb, &mp, one.data())) { return false; }
-    corr += mp.corr;
-    for (int pl = 0; pl < 2; pl++) {   // [plane][nb] of the phase -> [plane][d][nb] of the set
-      std::copy(one.begin() + (size_t)pl * nb * blk, one.begin() + (size_t)(pl + 1) * nb * blk, frag->begin() + pl * plane + (size_t)d * nb * blk);
-    }
-  }
-  plan->ntaps = ntaps; plan->df = df; plan->nb = nb; plan->corr = corr;
+  std::vector<int64_t> corr;
+  if (!long_phase_fragments(c, df, ntaps, frag, &corr)) { return false; }
+  plan->ntaps = ntaps; plan->df = df; plan->nb = long_blocks(ntaps);
+  plan->corr = std::accumulate(corr.begin(), corr.end(), (int64_t)0);   // one accumulator over all phases: one constant
   return true;
 }
 
-PolyDecLongGeom polydec_long_geometry(int ntaps, int df, int n_ch, uint64_t cap) {
-  const uint64_t H = 32 * (uint64_t)(polydec_long_blocks(ntaps) - 1);
-  auto b = [&](uint64_t G) { return (uint64_t)df * (H + G) * 2; };   // bytes of one channel's phase rows
-  PolyDecLongGeom g;
-  uint64_t C = (uint64_t)n_ch;
-  if (C * b(1024) > cap) {
-    C = cap / b(1024) / 8 * 8;
-    if (C < 8) { C = 8; }
-    if (C > (uint64_t)n_ch) { C = (uint64_t)n_ch; }
-  }
-  // largest multiple of 1024 with C * b(G) <= cap, inside 1024 .. 65536
-  uint64_t G = 1024;
-  if (cap / C / ((uint64_t)df * 2) > H) { G = (cap / C / ((uint64_t)df * 2) - H) / 1024 * 1024; }
-  if (G < 1024) { G = 1024; }
-  if (G > 65536) { G = 65536; }
-  g.slab = (int64_t)G; g.group = (int32_t)C; g.bytes = C * b(G);
-  return g;
-}
-
-hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, const PolyDecLongGeom &geo, const uint32_t *d_frag,
+hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, const LongGeom &geo, const uint32_t *d_frag,
                                const int64_t *d_corr, void *d_scratch, int64_t n_out, hipStream_t s) {
   if (n_out <= 0) { return hipSuccess; }
   if (p.in_eb != 2 || plan.nb < 2 || geo.slab < 1024 || geo.slab % 1024 || geo.group < 1 || !d_scratch) { return hipErrorInvalidValue; }
   const int64_t H = 32 * (int64_t)(plan.nb - 1), L = H + geo.slab;
-  hipError_t e = hipFuncSetAttribute((const void *)fir_long_dec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDecLdsBytes);
+  hipError_t e = hipFuncSetAttribute((const void *)fir_long_dec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes);
   if (e != hipSuccess) { return e; }
   int J = 1024;
   while (J > 64 && J * plan.df > kSplitTileElems) { J >>= 1; }
@@ -309,13 +259,9 @@ hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, 
       a.nb = plan.nb; a.df = plan.df; a.ch0 = ch0; a.n_grp = n_grp;
       a.hi_xor = p.in_flip ? 0x80808080u : 0u;
       a.corr = d_corr; a.z = (const int16_t *)d_scratch;
-      // a workgroup is eight channels x steps_per_wave steps; >= 2048 workgroups (8 per CU) when the slab allows it
-      const int64_t rows = ((int64_t)n_grp + 7) / 8;
-      int64_t spw = (n_steps * rows + 2047) / 2048;
-      if (spw < 1) { spw = 1; }
-      a.steps_per_wave = spw;
-      const dim3 grid((unsigned)((n_steps + spw - 1) / spw), (unsigned)rows);
-      hipLaunchKernelGGL(fir_long_dec_kernel, grid, dim3(512), kDecLdsBytes, s, p, (const v4i *)d_frag, a);
+      const LongGrid lg = long_grid(n_steps, n_grp, 1);
+      a.steps_per_wave = lg.steps_per_wave;
+      hipLaunchKernelGGL(fir_long_dec_kernel, dim3(lg.gx, lg.gy), dim3(512), kLongLdsBytes, s, p, (const v4i *)d_frag, a);
       if ((e = hipGetLastError()) != hipSuccess) { return e; }
     }
   }

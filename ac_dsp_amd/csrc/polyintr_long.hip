@@ -28,26 +28,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "fir_kernels.hpp"
+#include "fir_long_kernels.hpp"
 
 namespace acdsp {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-// the segment geometry of fir_long.hip (kLongSB .. kLongLdsBytes there)
-constexpr int kIntrSB = 16;                          // K-blocks per LDS segment
-constexpr int kIntrNC = 32 + kIntrSB - 1;            // chunks (32 samples) of a segment's sample window
-constexpr int kIntrNP = 4 * kIntrNC;                 // 16-byte loads of the window
-constexpr int kIntrJN = (kIntrNP + 63) / 64;         // ... per lane
-constexpr int kIntrARR = ((kIntrNC * 16 + 63) / 128) * 128 + 64;   // one staged [plane][half] array (size = 64 mod 128: the halves sit 16 banks apart)
-constexpr int kIntrAWords = 2 * kIntrSB * 64;        // v4i words of one A segment: [plane][block][lane]
-constexpr int kIntrAPerThread = kIntrAWords / 512;   // = 4
-constexpr int kIntrXBytes = 4 * kIntrARR;            // one staged window of a wave
-constexpr size_t kIntrLdsBytes = (size_t)2 * kIntrAWords * 16 + (size_t)8 * 2 * kIntrXBytes;
-static_assert(kIntrAWords % 512 == 0, "an A segment is copied by 512 threads in whole passes");
-static_assert(kIntrARR >= kIntrNC * 16, "staged array holds the window");
-static_assert(kIntrLdsBytes <= 160 * 1024, "LDS of one gfx950 CU");
 
 // ---------------------------------------------------------------------------------------------
 // kernel 1: the Toeplitz products over (step, phase, segment)
@@ -67,7 +50,7 @@ struct LongIntrArgs {
 __global__ void __launch_bounds__(512, 1)
 fir_long_intr_kernel(FirParams p, const v4i *__restrict__ frag, LongIntrArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
-  const int NB = a.nb, NSEG = (NB + kIntrSB - 1) / kIntrSB, IF = a.ifac;
+  const int NB = a.nb, NSEG = (NB + kLongSB - 1) / kLongSB, IF = a.ifac;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n_col = lane & 31, h = lane >> 5;
   int chl = blockIdx.y * 8 + wave;
@@ -75,7 +58,7 @@ fir_long_intr_kernel(FirParams p, const v4i *__restrict__ frag, LongIntrArgs a) 
   const int ch = a.ch0 + chl;
   // LDS: [2 A segments: 2 planes x 16 blocks x 1 KB][per wave: 2 staged windows of 4 arrays]
   v4i *ldsA = (v4i *)lds_all;
-  unsigned char *ldsX = lds_all + (size_t)2 * kIntrAWords * 16 + (size_t)wave * 2 * kIntrXBytes;
+  unsigned char *ldsX = lds_all + (size_t)2 * kLongAWords * 16 + (size_t)wave * 2 * kLongXBytes;
 
   const int16_t *xrow = (const int16_t *)p.x + (int64_t)ch * p.in_stride;
   const int16_t *hrow = (const int16_t *)p.hist + (int64_t)ch * p.hl + p.hl;
@@ -86,21 +69,21 @@ fir_long_intr_kernel(FirParams p, const v4i *__restrict__ frag, LongIntrArgs a) 
   const int total = nsteps * IF * NSEG;
   const size_t plane_words = (size_t)IF * NB * 64;
 
-  v4i RA[kIntrAPerThread], RX[kIntrJN];
+  v4i RA[kLongAPerThread], RX[kLongJN];
   // global loads of iteration (step s, phase j, segment g): this thread's share of the A segment, this lane's share of the wave's window
   auto issue_loads = [&](int s, int j, int g) {
 #pragma unroll
-    for (int q = 0; q < kIntrAPerThread; q++) {
-      const int idx = threadIdx.x + 512 * q, pl = idx / (kIntrSB * 64), bl = (idx >> 6) % kIntrSB, ln = idx & 63;
-      int bg = g * kIntrSB + bl;
+    for (int q = 0; q < kLongAPerThread; q++) {
+      const int idx = threadIdx.x + 512 * q, pl = idx / (kLongSB * 64), bl = (idx >> 6) % kLongSB, ln = idx & 63;
+      int bg = g * kLongSB + bl;
       if (bg >= NB) { bg = NB - 1; }   // blocks past the phase in its last segment: never multiplied, any in-bounds fragment will do
       RA[q] = frag[(size_t)pl * plane_words + ((size_t)j * NB + bg) * 64 + ln];
     }
     // t is a multiple of 8 and so is hl: a load never straddles history and row, nor the history's first sample
-    const int64_t base = a.n0 + (s0 + s) * 1024 - 32 * (int64_t)(NB - 1) + 32 * kIntrSB * (int64_t)g;
+    const int64_t base = a.n0 + (s0 + s) * 1024 - 32 * (int64_t)(NB - 1) + 32 * kLongSB * (int64_t)g;
 #pragma unroll
-    for (int jx = 0; jx < kIntrJN; jx++) {
-      const int pc = (lane + 64 * jx < kIntrNP) ? lane + 64 * jx : kIntrNP - 1;
+    for (int jx = 0; jx < kLongJN; jx++) {
+      const int pc = (lane + 64 * jx < kLongNP) ? lane + 64 * jx : kLongNP - 1;
       const int64_t t = base + 8 * pc;
       v4i v = {0, 0, 0, 0};
       if (t < 0) {
@@ -125,22 +108,22 @@ fir_long_intr_kernel(FirParams p, const v4i *__restrict__ frag, LongIntrArgs a) 
   };
   // registers -> LDS: the A segment (all waves, read after the barrier) and the wave's byte planes
   auto commit = [&](int buf) {
-    v4i *dstA = ldsA + buf * kIntrAWords;
+    v4i *dstA = ldsA + buf * kLongAWords;
 #pragma unroll
-    for (int q = 0; q < kIntrAPerThread; q++) { dstA[threadIdx.x + 512 * q] = RA[q]; }
-    unsigned char *xb = ldsX + buf * kIntrXBytes;
+    for (int q = 0; q < kLongAPerThread; q++) { dstA[threadIdx.x + 512 * q] = RA[q]; }
+    unsigned char *xb = ldsX + buf * kLongXBytes;
 #pragma unroll
-    for (int jx = 0; jx < kIntrJN; jx++) {
+    for (int jx = 0; jx < kLongJN; jx++) {
       const int pc = lane + 64 * jx;
-      if (pc < kIntrNP) {
+      if (pc < kLongNP) {
         const int c = pc >> 2, hh_ = (pc >> 1) & 1, sub = pc & 1;
         const unsigned hi0 = __builtin_amdgcn_perm((unsigned)RX[jx].y, (unsigned)RX[jx].x, 0x07050301u);
         const unsigned hi1 = __builtin_amdgcn_perm((unsigned)RX[jx].w, (unsigned)RX[jx].z, 0x07050301u);
         const unsigned lo0 = __builtin_amdgcn_perm((unsigned)RX[jx].y, (unsigned)RX[jx].x, 0x06040200u) ^ 0x80808080u;
         const unsigned lo1 = __builtin_amdgcn_perm((unsigned)RX[jx].w, (unsigned)RX[jx].z, 0x06040200u) ^ 0x80808080u;
         typedef unsigned v2u __attribute__((ext_vector_type(2)));
-        *(v2u *)(xb + (0 * 2 + hh_) * kIntrARR + c * 16 + sub * 8) = (v2u){hi0, hi1};
-        *(v2u *)(xb + (1 * 2 + hh_) * kIntrARR + c * 16 + sub * 8) = (v2u){lo0, lo1};
+        *(v2u *)(xb + (0 * 2 + hh_) * kLongARR + c * 16 + sub * 8) = (v2u){hi0, hi1};
+        *(v2u *)(xb + (1 * 2 + hh_) * kLongARR + c * 16 + sub * 8) = (v2u){lo0, lo1};
       }
     }
   };
@@ -159,11 +142,11 @@ fir_long_intr_kernel(FirParams p, const v4i *__restrict__ frag, LongIntrArgs a) 
     __syncthreads();
 
     if (g == 0) { hh = (v16i){0}; mid = (v16i){0}; ll = (v16i){0}; }
-    const int b0 = g * kIntrSB, nbs = (NB - b0 < kIntrSB) ? NB - b0 : kIntrSB;
-    const v4i *ah = ldsA + buf * kIntrAWords + lane, *al = ah + kIntrSB * 64;
-    const unsigned char *xb = ldsX + buf * kIntrXBytes;
-    const unsigned char *fh = xb + (0 * 2 + h) * kIntrARR + n_col * 16;   // chunk n_col + bl <= 46
-    const unsigned char *fl = xb + (1 * 2 + h) * kIntrARR + n_col * 16;
+    const int b0 = g * kLongSB, nbs = (NB - b0 < kLongSB) ? NB - b0 : kLongSB;
+    const v4i *ah = ldsA + buf * kLongAWords + lane, *al = ah + kLongSB * 64;
+    const unsigned char *xb = ldsX + buf * kLongXBytes;
+    const unsigned char *fh = xb + (0 * 2 + h) * kLongARR + n_col * 16;   // chunk n_col + bl <= 46
+    const unsigned char *fl = xb + (1 * 2 + h) * kLongARR + n_col * 16;
     v4i Ahc = ah[0], Alc = al[0], Bhc = *(const v4i *)fh, Blc = *(const v4i *)fl;
     for (int bl = 0; bl < nbs; bl++) {
       v4i Ahn = Ahc, Aln = Alc, Bhn = Bhc, Bln = Blc;
@@ -274,51 +257,18 @@ polyintr_phase_merge_kernel(MergeArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-int polyintr_long_blocks(int nt) {
-  const int nb = (nt - 1 + 31) / 32 + 1;
-  return nb < 2 ? 2 : nb;
-}
-
 bool polyintr_long_plan(const int64_t *E, int ifac, int nt, const uint8_t *halve, PolyIntrLongPlan *plan, std::vector<uint32_t> *frag,
                         std::vector<int64_t> *corr, std::vector<uint8_t> *flags) {
   if (nt < 1 || nt > kPolyIntrLongMaxTaps || ifac < 1 || ifac > 255) { return false; }
-  const int nb = polyintr_long_blocks(nt);
+  const int nb = long_blocks(nt);
   if ((int64_t)ifac * nb > kPolyIntrLongMaxBlocks) { return false; }
-  const size_t blk = (size_t)64 * 4, plane = (size_t)ifac * nb * blk;
-  frag->assign(2 * plane, 0u);
-  corr->assign((size_t)ifac, 0);
   flags->assign(halve, halve + ifac);
-  std::vector<uint32_t> one((size_t)2 * nb * blk);
-  for (int j = 0; j < ifac; j++) {
-    FirMfmaPlan mp;
-    if (!fir_mfma_build_fragments_nb(E + (size_t)nt * j, nt, nb, &mp, one.data())) { return false; }
-    (*corr)[(size_t)j] = mp.corr;
-    for (int pl = 0; pl < 2; pl++) {   // [plane][nb] of the phase -> [plane][j][nb] of the set
-      std::copy(one.begin() + (size_t)pl * nb * blk, one.begin() + (size_t)(pl + 1) * nb * blk, frag->begin() + pl * plane + (size_t)j * nb * blk);
-    }
-  }
+  if (!long_phase_fragments(E, ifac, nt, frag, corr)) { return false; }   // accumulators per phase: every phase keeps its constant
   plan->nt = nt; plan->ifac = ifac; plan->nb = nb;
   return true;
 }
 
-PolyIntrLongGeom polyintr_long_geometry(int ifac, int out_eb, int n_ch, uint64_t cap) {
-  auto b = [&](uint64_t G) { return (uint64_t)ifac * G * (uint64_t)out_eb; };   // bytes of one channel's phase rows
-  PolyIntrLongGeom g;
-  uint64_t C = (uint64_t)n_ch;
-  if (C * b(1024) > cap) {
-    C = cap / b(1024) / 8 * 8;
-    if (C < 8) { C = 8; }
-    if (C > (uint64_t)n_ch) { C = (uint64_t)n_ch; }
-  }
-  // largest multiple of 1024 with C * b(G) <= cap, inside 1024 .. 65536
-  uint64_t G = cap / (C * b(1)) / 1024 * 1024;
-  if (G < 1024) { G = 1024; }
-  if (G > 65536) { G = 65536; }
-  g.slab = (int64_t)G; g.group = (int32_t)C; g.bytes = C * b(G);
-  return g;
-}
-
-hipError_t launch_polyintr_long(const FirParams &p, const PolyIntrLongPlan &plan, const PolyIntrLongGeom &geo, const uint32_t *d_frag,
+hipError_t launch_polyintr_long(const FirParams &p, const PolyIntrLongPlan &plan, const LongGeom &geo, const uint32_t *d_frag,
                                 const int64_t *d_corr, const uint8_t *d_halve, void *d_scratch, int skip, int64_t o_lo, int64_t n_out,
                                 hipStream_t s) {
   if (p.n <= 0 || n_out <= o_lo) { return hipSuccess; }
@@ -326,7 +276,7 @@ hipError_t launch_polyintr_long(const FirParams &p, const PolyIntrLongPlan &plan
       (p.out_eb != 2 && p.out_eb != 4 && p.out_eb != 8)) {
     return hipErrorInvalidValue;
   }
-  hipError_t e = hipFuncSetAttribute((const void *)fir_long_intr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kIntrLdsBytes);
+  hipError_t e = hipFuncSetAttribute((const void *)fir_long_intr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLdsBytes);
   if (e != hipSuccess) { return e; }
   const int IF = plan.ifac, P = IF | 1;
   int J = 1024;
@@ -341,15 +291,11 @@ hipError_t launch_polyintr_long(const FirParams &p, const PolyIntrLongPlan &plan
       a.n0 = n0; a.n_end = n0 + n_slab; a.G = geo.slab;
       a.nb = plan.nb; a.ifac = IF; a.ch0 = ch0; a.n_grp = n_grp;
       a.corr = d_corr; a.halve = d_halve; a.z = d_scratch;
-      // a workgroup is eight channels x steps_per_wave steps; >= 2048 workgroups (8 per CU) when the slab allows it.  No floor of 8 steps
-      // as in launch_fir_long: a step is IF * NSEG iterations here, not NSEG, and a slab may hold one step only (launch_polydec_long
-      // has none either)
-      const int64_t rows = ((int64_t)n_grp + 7) / 8;
-      int64_t spw = (a.n_steps * rows + 2047) / 2048;
-      if (spw < 1) { spw = 1; }
-      a.steps_per_wave = spw;
-      const dim3 grid((unsigned)((a.n_steps + spw - 1) / spw), (unsigned)rows);
-      hipLaunchKernelGGL(fir_long_intr_kernel, grid, dim3(512), kIntrLdsBytes, s, p, (const v4i *)d_frag, a);
+      // no floor of 8 steps as in launch_fir_long: a step is IF * NSEG iterations here, not NSEG, and a slab may hold one step only
+      // (launch_polydec_long has none either)
+      const LongGrid lg = long_grid(a.n_steps, n_grp, 1);
+      a.steps_per_wave = lg.steps_per_wave;
+      hipLaunchKernelGGL(fir_long_intr_kernel, dim3(lg.gx, lg.gy), dim3(512), kLongLdsBytes, s, p, (const v4i *)d_frag, a);
       if ((e = hipGetLastError()) != hipSuccess) { return e; }
       MergeArgs m;
       m.z = d_scratch; m.y = p.y; m.out_stride = p.out_stride; m.G = geo.slab;

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 F16 = A.Fmt(16, 2)
 FA = A.Fmt(48, 20)                          # F = 28 = F_in + F_coeff: exact products, 19 integer bits of headroom
 FO = A.Fmt(16, 10, True, "RND", "SAT")
-SB = 16                                     # K-blocks per LDS segment of the kernel (fir_long.hip: kLongSB)
+SB = 16                                     # K-blocks per LDS segment of the kernel (fir_long_kernels.hpp: kLongSB)
 
 
 def stream_len(n_taps):
@@ -81,6 +81,14 @@ def test_tap_counts_and_segment_edges(n_taps):
                                  [n_taps + 64]))             # a call of at least hl samples: history written in place
     assert fir.mfma_issued() == 4 * n_blocks(n_taps)         # dense: every high-byte block is issued
     assert fir.mfma_epilogue() is None                       # (-1 off the int8 path)
+
+
+# a workgroup is eight channels x at least eight steps: nine channels are two workgroup rows, the second with one live wave and seven
+# clamped to its channel; the single call of ten steps is two workgroup columns, the second with two steps, the last of them ragged
+def test_nine_channels_and_two_workgroup_columns():
+    n_ch = 9
+    x = rand_raw(np.random.default_rng(25), F16, (n_ch, 8192 + 1024 + 5))
+    long_case(1026, "SHIFT_REG", F16, F16, FA, FO, dense(1026), n_ch=n_ch, x=x, splits_list=([], [700, 9000]))
 
 
 # 2. accumulator bound: every product at its largest magnitude and of one sign, 16384 of them
