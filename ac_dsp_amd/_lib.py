@@ -214,6 +214,20 @@ SYMBOLS = {
     "acdsp_ddc_state_size": (_i64, [_vp]),
     "acdsp_ddc_state_get": (_i32, [_vp, _vp, C.c_uint64]),
     "acdsp_ddc_state_set": (_i32, [_vp, _vp, C.c_uint64]),
+    "acdsp_polydec_state_size": (_i64, [_vp]),
+    "acdsp_polydec_state_get": (_i32, [_vp, _vp, C.c_uint64]),
+    "acdsp_polydec_state_set": (_i32, [_vp, _vp, C.c_uint64]),
+    "acdsp_polyintr_state_size": (_i64, [_vp]),
+    "acdsp_polyintr_state_get": (_i32, [_vp, _vp, C.c_uint64]),
+    "acdsp_polyintr_state_set": (_i32, [_vp, _vp, C.c_uint64]),
+    "acdsp_intgdump_state_size": (_i64, [_vp]),
+    "acdsp_intgdump_state_get": (_i32, [_vp, _vp, C.c_uint64]),
+    "acdsp_intgdump_state_set": (_i32, [_vp, _vp, C.c_uint64]),
+    "acdsp_polydec_clone": (_i32, [_vp, C.POINTER(_vp)]),
+    "acdsp_polyintr_clone": (_i32, [_vp, C.POINTER(_vp)]),
+    "acdsp_intgdump_clone": (_i32, [_vp, C.POINTER(_vp)]),
+    "acdsp_mvavg_clone": (_i32, [_vp, C.POINTER(_vp)]),
+    "acdsp_ddc_clone": (_i32, [_vp, C.POINTER(_vp)]),
     "acdsp_stream_write": (_i32, [C.c_char_p, C.POINTER(StreamHdr), _vp]),
     "acdsp_stream_read_header": (_i32, [C.c_char_p, C.POINTER(StreamHdr)]),
     "acdsp_stream_read": (_i32, [C.c_char_p, _vp, C.c_uint64]),

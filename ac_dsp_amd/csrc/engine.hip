@@ -380,65 +380,19 @@ extern "C" int32_t acdsp_diag_fir_envelope_copygeom_ms(int32_t device, const int
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-// 64-byte little-endian header in front of the raw state words.
-struct StateHdr {
-  char magic[8];            // "ACDSPST1"
-  uint32_t version;         // 1
-  uint32_t kind;            // 1: FIR input history, 2: FIR reg_trans partial sums, 3: CIC input history + input count,
-                            // 4: fused DDC input history + input count, 5: two-kernel DDC (CIC blob + FIR blob follow)
-  uint32_t n_channels;
-  uint32_t elem_bytes;      // bytes per state word (IN container; reg_trans: 8, or 16 for an ACC_TYPE wider than 64 bits)
-  uint64_t per_channel;     // state words per channel
-  int64_t t_total;          // CIC: inputs consumed so far (decimation / interpolation phase); 0 for FIR
-  uint32_t p0, p1, p2, p3;  // FIR: n_taps, ftype, class, 0;  CIC: R, M, N, interp
-  uint64_t reserved;
-};
-static_assert(sizeof(StateHdr) == 64, "state header is 64 bytes");
-const char kStateMagic[8] = {'A', 'C', 'D', 'S', 'P', 'S', 'T', '1'};
-
+// (StateHdr and the checks every family shares: engine_common.hpp)
 StateHdr fir_state_hdr(const acdsp_fir *h) {
-  StateHdr s;
-  memset(&s, 0, sizeof s);
-  memcpy(s.magic, kStateMagic, 8);
-  s.version = 1;
-  s.kind = h->use_rt ? 2 : 1;
-  s.n_channels = (uint32_t)h->d.n_channels;
-  s.elem_bytes = h->use_rt ? (uint32_t)h->rt_eb : (uint32_t)h->in_eb;
-  s.per_channel = h->use_rt ? (uint64_t)h->d.n_taps : (uint64_t)h->hl;
+  StateHdr s = state_hdr(h->use_rt ? 2 : 1, (uint32_t)h->d.n_channels, h->use_rt ? (uint32_t)h->rt_eb : (uint32_t)h->in_eb,
+                         h->use_rt ? (uint64_t)h->d.n_taps : (uint64_t)h->hl);
   s.p0 = (uint32_t)h->d.n_taps; s.p1 = (uint32_t)h->d.ftype; s.p2 = (uint32_t)h->d.kind;
   return s;
 }
 StateHdr cic_state_hdr(const acdsp_cic *h) {
-  StateHdr s;
-  memset(&s, 0, sizeof s);
-  memcpy(s.magic, kStateMagic, 8);
-  s.version = 1;
-  s.kind = 3;
-  s.n_channels = (uint32_t)h->d.n_channels;
-  s.elem_bytes = (uint32_t)h->in_eb;
-  s.per_channel = (uint64_t)h->hl;
+  StateHdr s = state_hdr(3, (uint32_t)h->d.n_channels, (uint32_t)h->in_eb, (uint64_t)h->hl);
   s.t_total = h->t_total;
   s.p0 = (uint32_t)h->d.R; s.p1 = (uint32_t)h->d.M; s.p2 = (uint32_t)h->d.N; s.p3 = (uint32_t)h->d.interp;
   return s;
 }
-uint64_t state_payload(const StateHdr &s) { return (uint64_t)s.n_channels * s.per_channel * s.elem_bytes; }
-
-// everything but t_total must agree between the blob and the handle it is loaded into
-bool state_compatible(const StateHdr &blob, const StateHdr &mine) {
-  return memcmp(blob.magic, kStateMagic, 8) == 0 && blob.version == 1 && blob.kind == mine.kind && blob.n_channels == mine.n_channels &&
-         blob.elem_bytes == mine.elem_bytes && blob.per_channel == mine.per_channel && blob.p0 == mine.p0 && blob.p1 == mine.p1 &&
-         blob.p2 == mine.p2 && blob.p3 == mine.p3;
-}
-
-// device image of an input-history blob `s` (payload `src`) of another history length than the handle's (`mine`): the newest
-// min(blob, mine) samples of every channel are kept, older ones zero
-std::vector<unsigned char> relen_image(const StateHdr &s, const StateHdr &mine, const unsigned char *src) {
-  const size_t eb = mine.elem_bytes, pm = (size_t)mine.per_channel, pb = (size_t)s.per_channel, keep = pm < pb ? pm : pb;
-  std::vector<unsigned char> img((size_t)mine.n_channels * pm * eb, 0);
-  for (size_t c = 0; c < mine.n_channels; c++) { memcpy(&img[(c * pm + (pm - keep)) * eb], src + (c * pb + (pb - keep)) * eb, keep * eb); }
-  return img;
-}
-
 }  // namespace
 
 extern "C" {
@@ -540,11 +494,7 @@ int32_t acdsp_cic_state_set(acdsp_cic_t h, const void *buf, uint64_t bytes) {
 // DDC cascade.  Fused mode: the input history + input count are the whole state (stage B's window is recomputed from it):
 // one kind-4 blob.  Two-kernel mode: a kind-5 header followed by the stage blobs (CIC, then FIR).
 static StateHdr ddc_state_hdr(const acdsp_ddc *h) {
-  StateHdr s;
-  memset(&s, 0, sizeof s);
-  memcpy(s.magic, kStateMagic, 8);
-  s.version = 1;
-  s.kind = h->fused ? 4 : 5;
+  StateHdr s = state_hdr(h->fused ? 4 : 5, 0, 0, 0);
   s.n_channels = (uint32_t)h->cic->d.n_channels;
   s.p0 = (uint32_t)h->cic->d.R; s.p1 = (uint32_t)h->cic->d.M; s.p2 = (uint32_t)h->cic->d.N; s.p3 = (uint32_t)h->fir->d.n_taps;
   if (h->fused) { s.elem_bytes = (uint32_t)h->cic->in_eb; s.per_channel = (uint64_t)h->hl; s.t_total = h->t_total; }

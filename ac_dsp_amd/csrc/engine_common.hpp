@@ -355,6 +355,61 @@ int run_host_staged(Staging &st, const HostRows &r, bool pin_small, Run run) {
   return ACDSP_OK;
 }
 
+// ---- state blobs (acdsp_*_state_get / _set): what engine.hip (FIR, CIC, DDC) and the family files (poly_dec, poly_intr, intg_dump) share ----
+// 64-byte little-endian header in front of the raw state words.
+struct StateHdr {
+  char magic[8];            // "ACDSPST1"
+  uint32_t version;         // 1
+  uint32_t kind;            // 1: FIR input history, 2: FIR reg_trans partial sums, 3: CIC input history + input count,
+                            // 4: fused DDC input history + input count, 5: two-kernel DDC (CIC blob + FIR blob follow),
+                            // 6: ac_poly_dec input history, 7: ac_poly_intr input history + input count + saved sums, 8: ac_intg_dump temp[]
+  uint32_t n_channels;
+  uint32_t elem_bytes;      // bytes per state word (IN container; reg_trans: 8, or 16 for an ACC_TYPE wider than 64 bits; temp[]: 8)
+  uint64_t per_channel;     // state words per channel
+  int64_t t_total;          // CIC, poly_intr: inputs consumed so far (decimation / interpolation phase, "first sample" of the folded cores); else 0
+  uint32_t p0, p1, p2, p3;  // FIR: n_taps, ftype, class, 0;  CIC: R, M, N, interp;  poly_dec: NTAPS, DF;  poly_intr: NTAPS, IF, ftype, COEFFSZ;  intg_dump: NS, CHN
+  uint64_t reserved;        // two-kernel DDC: channel count;  intg_dump: bit 0 = pending (the stream stands behind a block that did not dump)
+};
+static_assert(sizeof(StateHdr) == 64, "state header is 64 bytes");
+
+inline StateHdr state_hdr(uint32_t kind, uint32_t n_channels, uint32_t elem_bytes, uint64_t per_channel) {
+  StateHdr s;
+  memset(&s, 0, sizeof s);
+  memcpy(s.magic, "ACDSPST1", 8);
+  s.version = 1;
+  s.kind = kind; s.n_channels = n_channels; s.elem_bytes = elem_bytes; s.per_channel = per_channel;
+  return s;
+}
+inline uint64_t state_payload(const StateHdr &s) { return (uint64_t)s.n_channels * s.per_channel * s.elem_bytes; }
+
+// everything but t_total must agree between the blob and the handle it is loaded into
+inline bool state_compatible(const StateHdr &blob, const StateHdr &mine) {
+  return memcmp(blob.magic, "ACDSPST1", 8) == 0 && blob.version == 1 && blob.kind == mine.kind && blob.n_channels == mine.n_channels &&
+         blob.elem_bytes == mine.elem_bytes && blob.per_channel == mine.per_channel && blob.p0 == mine.p0 && blob.p1 == mine.p1 &&
+         blob.p2 == mine.p2 && blob.p3 == mine.p3;
+}
+
+// device image of an input-history blob `s` (payload `src`) of another history length than the handle's (`mine`): the newest
+// min(blob, mine) samples of every channel are kept, older ones zero
+inline std::vector<unsigned char> relen_image(const StateHdr &s, const StateHdr &mine, const unsigned char *src) {
+  const size_t eb = mine.elem_bytes, pm = (size_t)mine.per_channel, pb = (size_t)s.per_channel, keep = pm < pb ? pm : pb;
+  std::vector<unsigned char> img((size_t)mine.n_channels * pm * eb, 0);
+  for (size_t c = 0; c < mine.n_channels; c++) { memcpy(&img[(c * pm + (pm - keep)) * eb], src + (c * pb + (pb - keep)) * eb, keep * eb); }
+  return img;
+}
+
+// An input-history blob `s` of `bytes` bytes (header, history, `extra` bytes behind it) against the header `mine` of the handle it is meant for:
+// 0 = not this handle's, 1 = the handle's own layout, 2 = another history LENGTH that still covers the filter memory of `mem` samples (the
+// rule of acdsp_fir_state_set: relen_image keeps the newest samples)
+inline int history_blob_fits(const StateHdr &s, const StateHdr &mine, uint64_t bytes, uint64_t extra, uint64_t mem) {
+  if (state_compatible(s, mine)) { return bytes == sizeof s + state_payload(mine) + extra ? 1 : 0; }
+  StateHdr same_len = s;
+  same_len.per_channel = mine.per_channel;
+  const bool relen = s.per_channel != mine.per_channel && s.per_channel >= mem && s.per_channel <= (uint64_t(1) << 20) && state_compatible(same_len, mine) &&
+                     bytes == sizeof s + state_payload(s) + extra;
+  return relen ? 2 : 0;
+}
+
 }  // namespace eng
 }  // namespace acdsp
 

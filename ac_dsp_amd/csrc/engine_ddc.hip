@@ -71,6 +71,35 @@ int32_t acdsp_ddc_set_coeffs(acdsp_ddc_t h, const int64_t *coeffs) {
   return ACDSP_OK;
 }
 
+// Deep copy: both stage descriptors, the coefficients when set, and the stream state of the mode the handle runs in -- the input history and
+// input count of the fused kernel, or clones of the two stage handles.  Plans, the intermediate buffer and the timers are the clone's own.
+int32_t acdsp_ddc_clone(acdsp_ddc_t h, acdsp_ddc_t *out) {
+  if (!h || !out) { return fail(ACDSP_EINVAL, "null argument"); }
+  acdsp_ddc_t c = nullptr;
+  int rc = acdsp_ddc_create(&h->cic->d, &h->fir->d, &c);
+  if (rc) { return rc; }
+  std::unique_ptr<acdsp_ddc, int32_t (*)(acdsp_ddc_t)> guard(c, acdsp_ddc_destroy);
+  // (the clone's stream has not started: a set that does not fit the fused kernel moves it to the two kernels, as it moved the original)
+  if (h->coeffs_set && (rc = acdsp_ddc_set_coeffs(c, h->fir->h_coeffs.data()))) { return rc; }
+  if (c->fused != h->fused) { return fail(ACDSP_EHIP, "internal: ddc_clone resolved to another kernel mode than its original"); }
+  HIP_TRY(hipDeviceSynchronize());
+  if (h->fused) {
+    if ((rc = c->hist.copy_from(h->hist))) { return rc; }
+    c->t_total = h->t_total;
+  } else {
+    acdsp_cic_t cic = nullptr;
+    acdsp_fir_t fir = nullptr;
+    if ((rc = acdsp_cic_clone(h->cic, &cic))) { return rc; }
+    acdsp_cic_destroy(c->cic);
+    c->cic = cic;
+    if ((rc = acdsp_fir_clone(h->fir, &fir))) { return rc; }
+    acdsp_fir_destroy(c->fir);
+    c->fir = fir;
+  }
+  *out = guard.release();
+  return ACDSP_OK;
+}
+
 int64_t acdsp_ddc_out_count(acdsp_ddc_t h, int64_t n_in) {
   if (!h || n_in < 0) { return -1; }
   if (!h->fused) { return acdsp_cic_out_count(h->cic, n_in); }

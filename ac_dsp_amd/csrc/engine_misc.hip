@@ -213,6 +213,77 @@ int32_t acdsp_intgdump_reset(acdsp_intgdump_t h) {
   return ACDSP_OK;
 }
 
+// Deep copy (the reference core is a plain aggregate: temp[CHN] goes with it, ac_intg_dump.h:96-103): descriptor, temp[] and what the host
+// knows about it.  Block table and staging are the clone's own: its first call uploads a table.
+int32_t acdsp_intgdump_clone(acdsp_intgdump_t h, acdsp_intgdump_t *out) {
+  if (!h || !out) { return fail(ACDSP_EINVAL, "null argument"); }
+  acdsp_intgdump_t c = nullptr;
+  int rc = acdsp_intgdump_create(&h->d, &c);
+  if (rc) { return rc; }
+  std::unique_ptr<acdsp_intgdump, int32_t (*)(acdsp_intgdump_t)> guard(c, acdsp_intgdump_destroy);
+  HIP_TRY(hipDeviceSynchronize());
+  if ((rc = c->temp.copy_from(h->temp))) { return rc; }
+  c->pending = h->pending;
+  c->temp_zero = h->temp_zero;
+  c->last_path = h->last_path;
+  *out = guard.release();
+  return ACDSP_OK;
+}
+
+// State blob, kind 8: temp[] of every object, [n_objects][CHN] int64 ACC raw words; bit 0 of the header's `reserved` = the stream stands
+// behind a block that did not dump (its sums sit in temp[]).
+static StateHdr intgdump_state_hdr(const acdsp_intgdump *h) {
+  StateHdr s = state_hdr(8, (uint32_t)h->d.n_objects, (uint32_t)sizeof(int64_t), (uint64_t)h->d.chn);
+  s.p0 = (uint32_t)h->d.ns; s.p1 = (uint32_t)h->d.chn;
+  s.reserved = h->pending ? 1 : 0;
+  return s;
+}
+
+int64_t acdsp_intgdump_state_size(acdsp_intgdump_t h) { return h ? (int64_t)(sizeof(StateHdr) + state_payload(intgdump_state_hdr(h))) : -1; }
+
+int32_t acdsp_intgdump_state_get(acdsp_intgdump_t h, void *buf, uint64_t cap_bytes) {
+  if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
+  const StateHdr s = intgdump_state_hdr(h);
+  const uint64_t pay = state_payload(s);
+  if (cap_bytes < sizeof s + pay) { return fail(ACDSP_EINVAL, "intgdump_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay)); }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous: the sums of the last call must have landed
+  memcpy(buf, &s, sizeof s);
+  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->temp.cur(), pay, hipMemcpyDeviceToHost));
+  return ACDSP_OK;
+}
+
+int32_t acdsp_intgdump_state_set(acdsp_intgdump_t h, const void *buf, uint64_t bytes) {
+  if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
+  const StateHdr mine = intgdump_state_hdr(h);
+  StateHdr s;
+  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "intgdump_state_set: blob shorter than its header"); }
+  memcpy(&s, buf, sizeof s);
+  if (!state_compatible(s, mine) || bytes != sizeof s + state_payload(mine) || (s.reserved & ~(uint64_t)1)) {
+    return fail(ACDSP_EINVAL, "intgdump_state_set: blob does not belong to an ac_intg_dump of this NS / CHN / object count");
+  }
+  const acdsp::DFmt af = make_dfmt(h->d.acc);
+  const unsigned char *pay = (const unsigned char *)buf + sizeof s;
+  bool all_zero = true;
+  for (uint64_t i = 0; i < state_payload(mine) / sizeof(int64_t); i++) {
+    int64_t w;
+    memcpy(&w, pay + i * sizeof(int64_t), sizeof w);
+    if (w < af.lo || w > af.hi) { return fail(ACDSP_EINVAL, "intgdump_state_set: word %llu = %lld is not an ACC_TYPE raw word", (unsigned long long)i, (long long)w); }
+    all_zero = all_zero && w == 0;
+  }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h->temp.cur(), pay, state_payload(mine), hipMemcpyHostToDevice));
+  // what run() derives from temp[]: the tile / stream kernels leave temp[] alone only when it is known to be zero, and sums that are carried
+  // keep a call on the exact-order kernel.  Sums in temp[] are pending whatever the flag of a hand-made blob says.
+  h->temp_zero = all_zero;
+  h->pending = (s.reserved & 1) != 0 || !all_zero;
+  h->last_ns.clear();   // the block table of the last call is rebuilt and uploaded by the next one, not trusted across a state load
+  return ACDSP_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
@@ -262,6 +333,19 @@ int32_t acdsp_mvavg_destroy(acdsp_mvavg_t h) {
   if (!h) { return ACDSP_OK; }
   (void)hipSetDevice(h->d.device);
   delete h;
+  return ACDSP_OK;
+}
+
+// Deep copy: descriptor and the coefficient set, when bound.  The reference builds its core inside run() (ac_mv_avg.h:154): there is no stream
+// state to carry, and staging is the clone's own.
+int32_t acdsp_mvavg_clone(acdsp_mvavg_t h, acdsp_mvavg_t *out) {
+  if (!h || !out) { return fail(ACDSP_EINVAL, "null argument"); }
+  acdsp_mvavg_t c = nullptr;
+  int rc = acdsp_mvavg_create(&h->d, &c);
+  if (rc) { return rc; }
+  if (h->coeffs_set && (rc = acdsp_mvavg_set_coeffs(c, h->h_coeffs.data()))) { acdsp_mvavg_destroy(c); return rc; }
+  c->last_path = h->last_path;
+  *out = c;
   return ACDSP_OK;
 }
 

@@ -255,6 +255,73 @@ int32_t acdsp_polydec_reset(acdsp_polydec_t h) {
   return h->hist.zero();
 }
 
+// Deep copy (the reference object is a plain aggregate: taps[], acc, acc1[] and coeffs_t go with it, ac_poly_dec.h:132-135): descriptor,
+// scratch cap, coefficients when set, input history.  Scratch and staging are the clone's own.
+int32_t acdsp_polydec_clone(acdsp_polydec_t h, acdsp_polydec_t *out) {
+  if (!h || !out) { return fail(ACDSP_EINVAL, "null argument"); }
+  acdsp_polydec_t c = nullptr;
+  int rc = acdsp_polydec_create(&h->d, &c);
+  if (rc) { return rc; }
+  std::unique_ptr<acdsp_polydec, int32_t (*)(acdsp_polydec_t)> guard(c, acdsp_polydec_destroy);
+  if (c->long_shape && h->scratch_cap != c->scratch_cap && (rc = polydec_size_scratch(c, h->scratch_cap))) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  if (h->coeffs_set) {
+    std::vector<int64_t> cf((size_t)h->d.n_taps * h->d.df);
+    HIP_TRY(hipMemcpy(cf.data(), h->d_coeffs.get(), cf.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if ((rc = acdsp_polydec_set_coeffs(c, cf.data()))) { return rc; }
+  }
+  if ((rc = c->hist.copy_from(h->hist))) { return rc; }
+  c->last_path = h->last_path;
+  *out = guard.release();
+  return ACDSP_OK;
+}
+
+// State blob, kind 6: the newest `hl` input samples of every channel, oldest first, in IN containers (the reference's taps[NTAPS*DF]; acc and
+// acc1[] are rebuilt by every group).  A call consumes whole groups of DF, so there is no phase to carry.
+static StateHdr polydec_state_hdr(const acdsp_polydec *h) {
+  StateHdr s = state_hdr(6, (uint32_t)h->d.n_channels, (uint32_t)h->in_eb, (uint64_t)h->hl);
+  s.p0 = (uint32_t)h->d.n_taps; s.p1 = (uint32_t)h->d.df;
+  return s;
+}
+
+int64_t acdsp_polydec_state_size(acdsp_polydec_t h) { return h ? (int64_t)(sizeof(StateHdr) + state_payload(polydec_state_hdr(h))) : -1; }
+
+int32_t acdsp_polydec_state_get(acdsp_polydec_t h, void *buf, uint64_t cap_bytes) {
+  if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
+  const StateHdr s = polydec_state_hdr(h);
+  const uint64_t pay = state_payload(s);
+  if (cap_bytes < sizeof s + pay) { return fail(ACDSP_EINVAL, "polydec_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay)); }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous: the state of the last call must have landed
+  memcpy(buf, &s, sizeof s);
+  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
+  return ACDSP_OK;
+}
+
+int32_t acdsp_polydec_state_set(acdsp_polydec_t h, const void *buf, uint64_t bytes) {
+  if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
+  const StateHdr mine = polydec_state_hdr(h);
+  StateHdr s;
+  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "polydec_state_set: blob shorter than its header"); }
+  memcpy(&s, buf, sizeof s);
+  // every kernel path of a descriptor keeps the same history today; a blob of another length (another build) is taken as long as it covers
+  // the NTAPS*DF - 1 samples an output reaches back
+  const int fit = history_blob_fits(s, mine, bytes, 0, (uint64_t)h->d.n_taps * h->d.df - 1);
+  if (!fit) { return fail(ACDSP_EINVAL, "polydec_state_set: blob does not belong to an ac_poly_dec of this NTAPS / DF / channel count"); }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  const unsigned char *pay = (const unsigned char *)buf + sizeof s;
+  if (fit == 2) {
+    const std::vector<unsigned char> img = relen_image(s, mine, pay);
+    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy(h->hist.cur(), pay, state_payload(mine), hipMemcpyHostToDevice));
+  }
+  return ACDSP_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
@@ -709,6 +776,90 @@ int32_t acdsp_polyintr_reset(acdsp_polyintr_t h) {
     if ((rc = sv.zero((size_t)h->d.n_channels * h->d.ifac * sizeof(int64_t)))) { return rc; }
   }
   h->t_total = 0;
+  return ACDSP_OK;
+}
+
+// Deep copy (the reference core is a plain aggregate: taps[], acc_a[], acc_b[] and the control structs go with it, ac_poly_intr.h:106-109):
+// descriptor, scratch cap, control words when set, input history, saved sums, input count.  Scratch, side stream and staging are the clone's own.
+int32_t acdsp_polyintr_clone(acdsp_polyintr_t h, acdsp_polyintr_t *out) {
+  if (!h || !out) { return fail(ACDSP_EINVAL, "null argument"); }
+  acdsp_polyintr_t c = nullptr;
+  int rc = acdsp_polyintr_create(&h->d, &c);
+  if (rc) { return rc; }
+  std::unique_ptr<acdsp_polyintr, int32_t (*)(acdsp_polyintr_t)> guard(c, acdsp_polyintr_destroy);
+  if (c->long_shape != h->long_shape) { return fail(ACDSP_EHIP, "polyintr_clone: the buffers of the long kernels could not be allocated a second time"); }
+  if (c->long_shape && h->scratch_cap != c->scratch_cap && (rc = polyintr_size_scratch(c, h->scratch_cap))) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  if (h->ctrl_set) {
+    std::vector<int64_t> cf((size_t)h->d.coeff_sz);
+    std::vector<uint8_t> sg((size_t)h->d.ifac), cr((size_t)h->d.ifac);
+    HIP_TRY(hipMemcpy(cf.data(), h->d_coeffs.get(), cf.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sg.data(), h->d_sign.get(), sg.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cr.data(), h->d_corr.get(), cr.size(), hipMemcpyDeviceToHost));
+    if ((rc = acdsp_polyintr_set_ctrl(c, cf.data(), sg.data(), cr.data()))) { return rc; }
+  }
+  if ((rc = c->hist.copy_from(h->hist))) { return rc; }   // (the clone's current index is 0: so is that of its saved sums)
+  HIP_TRY(hipMemcpy(c->d_saved[0].get(), h->d_saved[h->hist.index()].get(), (size_t)h->d.n_channels * h->d.ifac * sizeof(int64_t), hipMemcpyDeviceToDevice));
+  c->t_total = h->t_total;
+  c->last_path = h->last_path;
+  *out = guard.release();
+  return ACDSP_OK;
+}
+
+// State blob, kind 7: the newest `hl` input samples of every channel, oldest first, in IN containers (taps[]), the input count in t_total
+// (the folded cores emit nothing for the first sample of a stream) and, behind the histories, the sub-filter sums of the last sample
+// [channel][IF] as int64 ACC raw words (the bank of acc_a / acc_b that the next sample emits: formed with the control words of their own
+// time, so carried, not recomputed; all zero on FOLD_ANTI, which emits at once).
+static StateHdr polyintr_state_hdr(const acdsp_polyintr *h) {
+  StateHdr s = state_hdr(7, (uint32_t)h->d.n_channels, (uint32_t)h->in_eb, (uint64_t)h->hl);
+  s.t_total = h->t_total;
+  s.p0 = (uint32_t)h->d.n_taps; s.p1 = (uint32_t)h->d.ifac; s.p2 = (uint32_t)h->d.ftype; s.p3 = (uint32_t)h->d.coeff_sz;
+  return s;
+}
+static uint64_t polyintr_saved_bytes(const acdsp_polyintr *h) { return (uint64_t)h->d.n_channels * h->d.ifac * sizeof(int64_t); }
+
+int64_t acdsp_polyintr_state_size(acdsp_polyintr_t h) {
+  return h ? (int64_t)(sizeof(StateHdr) + state_payload(polyintr_state_hdr(h)) + polyintr_saved_bytes(h)) : -1;
+}
+
+int32_t acdsp_polyintr_state_get(acdsp_polyintr_t h, void *buf, uint64_t cap_bytes) {
+  if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
+  const StateHdr s = polyintr_state_hdr(h);
+  const uint64_t pay = state_payload(s), sv = polyintr_saved_bytes(h);
+  if (cap_bytes < sizeof s + pay + sv) { return fail(ACDSP_EINVAL, "polyintr_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay + sv)); }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous, on two streams: the state of the last call must have landed
+  memcpy(buf, &s, sizeof s);
+  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy((char *)buf + sizeof s + pay, h->d_saved[h->hist.index()].get(), sv, hipMemcpyDeviceToHost));
+  return ACDSP_OK;
+}
+
+int32_t acdsp_polyintr_state_set(acdsp_polyintr_t h, const void *buf, uint64_t bytes) {
+  if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
+  const StateHdr mine = polyintr_state_hdr(h);
+  StateHdr s;
+  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "polyintr_state_set: blob shorter than its header"); }
+  memcpy(&s, buf, sizeof s);
+  // every kernel path of a descriptor keeps the same history today; a blob of another length (another build) is taken as long as it covers
+  // the NTAPS samples the sums of a call's first group reach back
+  const uint64_t sv = polyintr_saved_bytes(h);
+  const int fit = history_blob_fits(s, mine, bytes, sv, (uint64_t)h->d.n_taps);
+  if (!fit || s.t_total < 0) { return fail(ACDSP_EINVAL, "polyintr_state_set: blob does not belong to an ac_poly_intr of this NTAPS / IF / ftype / COEFFSZ / channel count"); }
+  int rc = check_device(h->d.device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  const unsigned char *pay = (const unsigned char *)buf + sizeof s;
+  if (fit == 2) {
+    const std::vector<unsigned char> img = relen_image(s, mine, pay);
+    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy(h->hist.cur(), pay, state_payload(mine), hipMemcpyHostToDevice));
+  }
+  // the saved sums are indexed like the history: they go beside the buffer just written
+  HIP_TRY(hipMemcpy(h->d_saved[h->hist.index()].get(), pay + state_payload(s), sv, hipMemcpyHostToDevice));
+  h->t_total = s.t_total;
   return ACDSP_OK;
 }
 

@@ -173,6 +173,22 @@ def diag_fir_envelope_copygeom_ms(coeffs, mfma_per_step, mfma_hi_per_step, x, y,
     return ms.value, nbytes
 
 
+def _clone(obj, clone_fn):
+    """A new object of obj's class around clone_fn(obj's handle): same descriptor, coefficients and stream state, independent afterwards."""
+    h = C.c_void_p()
+    check(clone_fn(obj._h, C.byref(h)))
+    twin = object.__new__(type(obj))
+    twin.__dict__.update(obj.__dict__)
+    twin._h = h
+    return twin
+
+
+def _state_get(h, size_fn, get_fn):
+    buf = (C.c_char * size_fn(h))()
+    check(get_fn(h, buf, len(buf)))
+    return bytes(buf)
+
+
 class Fir:
     """n_channels independent reference FIR objects (ac_fir_{const,load,prog}_coeffs) behind one handle."""
 
@@ -255,6 +271,10 @@ class Fir:
         check(lib.acdsp_fir_mfma_issued(self._h, C.byref(v)))
         return v.value
 
+    def clone(self):
+        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_fir_clone)."""
+        return _clone(self, lib.acdsp_fir_clone)
+
     def close(self):
         if getattr(self, "_h", None):
             lib.acdsp_fir_destroy(self._h)
@@ -333,6 +353,10 @@ class Cic:
         check(lib.acdsp_cic_kernel_stats(self._h, last_k, C.byref(a), C.byref(m)))
         return a.value, m.value
 
+    def clone(self):
+        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_cic_clone)."""
+        return _clone(self, lib.acdsp_cic_clone)
+
     def close(self):
         if getattr(self, "_h", None):
             lib.acdsp_cic_destroy(self._h)
@@ -383,6 +407,17 @@ class PolyDec:
 
     def reset(self):
         check(lib.acdsp_polydec_reset(self._h))
+
+    def state(self):
+        """Versioned state blob (bytes): input history of every channel (acdsp_polydec_state_get)."""
+        return _state_get(self._h, lib.acdsp_polydec_state_size, lib.acdsp_polydec_state_get)
+
+    def set_state(self, blob):
+        check(lib.acdsp_polydec_state_set(self._h, C.c_char_p(blob), len(blob)))
+
+    def clone(self):
+        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_polydec_clone)."""
+        return _clone(self, lib.acdsp_polydec_clone)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -451,6 +486,10 @@ class Ddc:
         check(lib.acdsp_ddc_kernel_stats(self._h, last_k, C.byref(a), C.byref(m)))
         return a.value, m.value
 
+    def clone(self):
+        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_ddc_clone)."""
+        return _clone(self, lib.acdsp_ddc_clone)
+
     def close(self):
         if getattr(self, "_h", None):
             lib.acdsp_ddc_destroy(self._h)
@@ -515,6 +554,17 @@ class PolyIntr:
     def reset(self):
         check(lib.acdsp_polyintr_reset(self._h))
 
+    def state(self):
+        """Versioned state blob (bytes): input history, input count and saved sub-filter sums of every channel (acdsp_polyintr_state_get)."""
+        return _state_get(self._h, lib.acdsp_polyintr_state_size, lib.acdsp_polyintr_state_get)
+
+    def set_state(self, blob):
+        check(lib.acdsp_polyintr_state_set(self._h, C.c_char_p(blob), len(blob)))
+
+    def clone(self):
+        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_polyintr_clone)."""
+        return _clone(self, lib.acdsp_polyintr_clone)
+
     def close(self):
         if getattr(self, "_h", None):
             lib.acdsp_polyintr_destroy(self._h)
@@ -558,6 +608,17 @@ class IntgDump:
 
     def reset(self):
         check(lib.acdsp_intgdump_reset(self._h))
+
+    def state(self):
+        """Versioned state blob (bytes): temp[] of every object and the pending flag (acdsp_intgdump_state_get)."""
+        return _state_get(self._h, lib.acdsp_intgdump_state_size, lib.acdsp_intgdump_state_get)
+
+    def set_state(self, blob):
+        check(lib.acdsp_intgdump_state_set(self._h, C.c_char_p(blob), len(blob)))
+
+    def clone(self):
+        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_intgdump_clone)."""
+        return _clone(self, lib.acdsp_intgdump_clone)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -606,6 +667,10 @@ class MvAvg:
         check(lib.acdsp_mvavg_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), n_sample, n_frames, C.c_void_p(out.data_ptr()), out.stride(0),
                                   C.byref(n_out), _stream_ptr(x)))
         return out[:, :n_out.value]
+
+    def clone(self):
+        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_mvavg_clone)."""
+        return _clone(self, lib.acdsp_mvavg_clone)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -6,6 +6,8 @@
 // interleaved samples; the accumulation (`temp[i] = temp[i] + data_in`, ACC_TYPE, :97) runs as a HIP kernel behind
 // include/acdsp.h (acdsp_intgdump_*).  Like the reference, a block that the FIFO cannot complete is an error (the
 // reference reads an empty ac_channel); here it aborts with a message before any sample is consumed.
+// Like the reference class the object is copyable: a copy carries temp[] (sums of blocks that have not dumped yet), and the
+// two objects are independent afterwards.
 #ifndef _INCLUDED_AC_INTG_DUMP_H_
 #define _INCLUDED_AC_INTG_DUMP_H_
 
@@ -23,8 +25,7 @@ template < class IN_TYPE, class ACC_TYPE, class OUT_TYPE, class N_TYPE, int NS, 
 class ac_intg_dump
 {
 public:
-  ac_intg_dump() : h_(0) {}
-  ~ac_intg_dump() { if (h_) { acdsp_intgdump_destroy(h_); } }
+  ac_intg_dump() : eng_(NS, CHN) {}
 
 #pragma hls_pipeline_init_interval 1
 #pragma hls_design interface
@@ -39,31 +40,19 @@ public:
       blocks.push_back(n);
     }
     if (blocks.empty()) { return; }
-    ensure();
     const int ib = acdsp_elem_bytes(IN_TYPE::width), ob = acdsp_elem_bytes(OUT_TYPE::width);
     std::vector<unsigned char> bi, bo(blocks.size() * (size_t)CHN * (size_t)ob + 16);
     acdsp::pack(raw, ib, bi);
     int64_t n_out = 0;
-    acdsp::check(acdsp_intgdump_run_host(h_, bi.data(), blocks.data(), (int64_t)blocks.size(), bo.data(), (int64_t)blocks.size() * CHN, &n_out),
-                 "acdsp_intgdump_run_host");
+    eng_.run_host(bi.data(), blocks.data(), (int64_t)blocks.size(), bo.data(), (int64_t)blocks.size() * CHN, &n_out);
     for (int64_t i = 0; i < n_out; i++) {
       data_out.write(acdsp::from_raw<OUT_TYPE>(acdsp::unpack_one(&bo[(size_t)i * ob], ob, OUT_TYPE::sign)));
     }
   }
 
 private:
-  ac_intg_dump(const ac_intg_dump &);
-  ac_intg_dump &operator=(const ac_intg_dump &);
   static void die(const char *why) { fprintf(stderr, "ac_intg_dump (MI355X engine): %s\n", why); abort(); }
-  void ensure() {
-    if (h_) { return; }
-    acdsp_intgdump_desc_t d;
-    d.ns = NS; d.chn = CHN; d.n_objects = 1;
-    d.in = acdsp::fmt_of<IN_TYPE>(); d.acc = acdsp::fmt_of<ACC_TYPE>(); d.out = acdsp::fmt_of<OUT_TYPE>();
-    d.device = acdsp::default_device(); d.flags = 0;
-    acdsp::check(acdsp_intgdump_create(&d, &h_), "acdsp_intgdump_create");
-  }
-  acdsp_intgdump_t h_;
+  acdsp::intgdump_engine<IN_TYPE, ACC_TYPE, OUT_TYPE> eng_;   // (copying it clones the handle: temp[] goes along)
 };
 
 #endif

@@ -5,6 +5,9 @@
 // frames of n_sample inputs while data is available (:164-189).  The per-sample window / MAC loop of ac_mv_avg_core
 // (:111-123) is replaced by one batched call into libacdsp (acdsp_mvavg_*: mv_avg.hip).  The reference builds its core
 // object inside run(), so no filter state survives a call -- neither here.
+// The object is copyable: a copy borrows the same coefficient array and owns an engine handle of its own.  cff_ptr is a const
+// member, as in the reference: assignment cannot rebind it, so the target keeps reading the array it was constructed on (there is
+// no stream state to move).
 //
 // ac_window_1d_flag (from <ac_window.h>, part of ac_types, not of ac_dsp) supplies the boundary behaviour in the reference;
 // include/ac_types/ac_window.h states the semantics this engine implements.
@@ -28,8 +31,9 @@ public:
   // public in the reference too: testbenches read the coefficient array back through it
   const COEFF_TYPE *const cff_ptr;
 
-  ac_mv_avg(const COEFF_TYPE *const c_ptr) : cff_ptr(c_ptr), h_(0) { }
-  ~ac_mv_avg() { if (h_) { acdsp_mvavg_destroy(h_); } }
+  ac_mv_avg(const COEFF_TYPE *const c_ptr) : cff_ptr(c_ptr), eng_(MAX_SAMPLE, TAPS, win_code()) { }
+  ac_mv_avg(const ac_mv_avg &o) : cff_ptr(o.cff_ptr), eng_(o.eng_) { }
+  ac_mv_avg &operator=(const ac_mv_avg &o) { eng_ = o.eng_; return *this; }
 
   void CCS_BLOCK(run)(ac_channel < IN_TYPE > &data_in, ac_channel < OUT_TYPE > &data_out, ac_channel < S_TYPE > &n_sample) {
     bool have = false;
@@ -48,17 +52,16 @@ public:
     std::vector<int64_t> x;
     while (data_in.available(1)) { x.push_back(acdsp::raw_of(data_in.read())); }
     if (x.size() % (size_t)n != 0) { die("input does not hold whole frames: the reference would read an empty channel"); }
-    ensure();
     std::vector<int64_t> c((size_t)TAPS);
     for (int i = 0; i < TAPS; i++) { c[(size_t)i] = acdsp::raw_of(cff_ptr[i]); }   // borrowed pointer: read at every call
-    acdsp::check(acdsp_mvavg_set_coeffs(h_, c.data()), "acdsp_mvavg_set_coeffs");
+    eng_.set_coeffs_raw(c);   // (uploaded only when the words changed)
     const int64_t n_frames = (int64_t)(x.size() / (size_t)n);
-    const int64_t opf = acdsp_mvavg_out_per_frame(h_, n);
+    const int64_t opf = eng_.out_per_frame(n);
     const int ib = acdsp_elem_bytes(IN_TYPE::width), ob = acdsp_elem_bytes(OUT_TYPE::width);
     std::vector<unsigned char> bi, bo((size_t)(opf * n_frames > 0 ? opf * n_frames : 1) * (size_t)ob);
     acdsp::pack(x, ib, bi);
     int64_t n_out = 0;
-    acdsp::check(acdsp_mvavg_run_host(h_, bi.data(), n, n_frames, bo.data(), opf * n_frames > 0 ? opf * n_frames : 1, &n_out), "acdsp_mvavg_run_host");
+    eng_.run_host(bi.data(), n, n_frames, bo.data(), opf * n_frames > 0 ? opf * n_frames : 1, &n_out);
     for (int64_t i = 0; i < n_out; i++) {
       data_out.write(acdsp::from_raw<OUT_TYPE>(acdsp::unpack_one(&bo[(size_t)i * (size_t)ob], ob, OUT_TYPE::sign)));
     }
@@ -69,19 +72,8 @@ private:
     fprintf(stderr, "ac_mv_avg (MI355X engine): %s\n", why);
     abort();
   }
-  void ensure() {
-    if (h_) { return; }
-    acdsp_mvavg_desc_t d;
-    d.max_sample = MAX_SAMPLE; d.taps = TAPS;
-    d.win_mode = WIN_TYPE == AC_WIN ? ACDSP_WIN_PLAIN : (WIN_TYPE == AC_MIRROR ? ACDSP_WIN_MIRROR : ACDSP_WIN_CLIP);
-    d.n_objects = 1;
-    d.in = acdsp::fmt_of<IN_TYPE>(); d.coeff = acdsp::fmt_of<COEFF_TYPE>(); d.acc = acdsp::fmt_of<ACC_TYPE>(); d.out = acdsp::fmt_of<OUT_TYPE>();
-    d.device = acdsp::default_device(); d.flags = 0;
-    acdsp::check(acdsp_mvavg_create(&d, &h_), "acdsp_mvavg_create");
-  }
-  ac_mv_avg(const ac_mv_avg &);
-  ac_mv_avg &operator=(const ac_mv_avg &);
-  acdsp_mvavg_t h_;
+  static int win_code() { return WIN_TYPE == AC_WIN ? ACDSP_WIN_PLAIN : (WIN_TYPE == AC_MIRROR ? ACDSP_WIN_MIRROR : ACDSP_WIN_CLIP); }
+  acdsp::mvavg_engine<IN_TYPE, COEFF_TYPE, ACC_TYPE, OUT_TYPE> eng_;
 };
 
 #endif

@@ -5,6 +5,8 @@
 // wins, :101-106), data is consumed in whole groups of DF samples (`while (data_in.available(DF))`, :109 --
 // fewer than DF left-over samples stay in the channel) and every group yields one output.  The loop nest
 // (:112-128) runs as HIP kernels behind include/acdsp.h.
+// Like the reference class the object is copyable: a copy carries the stream (the engine's input history = taps[]) and the
+// coefficient struct, and the two objects are independent afterwards.
 #ifndef _INCLUDED_AC_POLY_DEC_H_
 #define _INCLUDED_AC_POLY_DEC_H_
 
@@ -17,8 +19,7 @@ template < class IN_TYPE, class COEFF_TYPE, class STR_COEFF_TYPE, class ACC_TYPE
 class ac_poly_dec
 {
 public:
-  ac_poly_dec() : h_(0), have_coeffs_(false) {}
-  ~ac_poly_dec() { if (h_) { acdsp_polydec_destroy(h_); } }
+  ac_poly_dec() : eng_(NTAPS, DF), have_coeffs_(false) {}
 
 #pragma hls_pipeline_init_interval 1
 #pragma hls_design interface
@@ -29,34 +30,23 @@ public:
       for (int i = 0; i < DF; i++) { raw.push_back(acdsp::raw_of(data_in.read())); }
     }
     if (raw.empty()) { return; }
-    ensure();
     std::vector<int64_t> c((size_t)NTAPS * DF, 0);   // coefficients are zero until the first struct arrives (don't care in the reference)
     if (have_coeffs_) { for (int i = 0; i < NTAPS * DF; i++) { c[(size_t)i] = acdsp::raw_of(coeffs_t.coeffs[i]); } }
-    if (c != last_c_) { acdsp::check(acdsp_polydec_set_coeffs(h_, c.data()), "acdsp_polydec_set_coeffs"); last_c_ = c; }
+    eng_.set_coeffs_raw(c);   // (uploaded only when the set changed)
     const int ib = acdsp_elem_bytes(IN_TYPE::width), ob = acdsp_elem_bytes(OUT_TYPE::width);
     std::vector<unsigned char> bi, bo(raw.size() / DF * (size_t)ob);
     acdsp::pack(raw, ib, bi);
-    acdsp::check(acdsp_polydec_run_host(h_, bi.data(), (int64_t)raw.size(), bo.data()), "acdsp_polydec_run_host");
+    eng_.run_host(bi.data(), (int64_t)raw.size(), bo.data());
     for (size_t i = 0; i < raw.size() / DF; i++) {
       data_out.write(acdsp::from_raw<OUT_TYPE>(acdsp::unpack_one(&bo[i * ob], ob, OUT_TYPE::sign)));
     }
   }
 
 private:
-  ac_poly_dec(const ac_poly_dec &);             // the engine handle is not shared: no copies
-  ac_poly_dec &operator=(const ac_poly_dec &);
-  void ensure() {
-    if (h_) { return; }
-    acdsp_polydec_desc_t d;
-    d.n_taps = NTAPS; d.df = DF; d.n_channels = 1;
-    d.in = acdsp::fmt_of<IN_TYPE>(); d.coeff = acdsp::fmt_of<COEFF_TYPE>(); d.acc = acdsp::fmt_of<ACC_TYPE>(); d.out = acdsp::fmt_of<OUT_TYPE>();
-    d.device = acdsp::default_device(); d.flags = 0;
-    acdsp::check(acdsp_polydec_create(&d, &h_), "acdsp_polydec_create");
-  }
-  acdsp_polydec_t h_;
+  // members copy one by one: the engine clones its handle (stream state and the coefficient set on it), the struct is plain data
+  acdsp::polydec_engine<IN_TYPE, COEFF_TYPE, ACC_TYPE, OUT_TYPE> eng_;
   bool have_coeffs_;
   STR_COEFF_TYPE coeffs_t;
-  std::vector<int64_t> last_c_;
 };
 
 #endif

@@ -5,8 +5,12 @@
 //   * the drop-in class templates ac_fir_{const,load,prog}_coeffs and
 //     ac_cic_{dec,intr}_full (one channel, ac_channel I/O, same signatures as
 //     the reference's include/ac_dsp/*.h), and
-//   * the batched many-channel API acdsp::fir_engine / acdsp::cic_engine, which
+//   * the batched many-channel API acdsp::fir_engine / cic_engine / ddc_engine /
+//     polydec_engine / polyintr_engine / intgdump_engine / mvavg_engine, which
 //     works on [channel][time] arrays of raw words (host or device memory).
+// Every engine is copyable with the reference's meaning: the reference blocks are
+// plain objects whose streaming state lives in data members, so a copy carries the
+// stream and the two objects are independent afterwards (acdsp_*_clone).
 //
 // Only public AC Datatypes API is used on the ac_fixed side (width, i_width,
 // sign, q_mode, o_mode, slc, set_slc), so the headers work both with the
@@ -131,6 +135,41 @@ inline int64_t unpack_one(const unsigned char *p, int eb, bool is_signed) {
   if (eb == 2) { int16_t t; memcpy(&t, p, 2); return is_signed ? (int64_t)t : (int64_t)(uint16_t)t; }
   if (eb == 4) { int32_t t; memcpy(&t, p, 4); return is_signed ? (int64_t)t : (int64_t)(uint32_t)t; }
   int64_t t; memcpy(&t, p, 8); return t;
+}
+
+// Owner of one engine handle with value semantics: copying clones the handle (acdsp_*_clone: descriptor, coefficients / control words,
+// stream state), assignment replaces the stream of the target, and an owner that has not created its handle yet copies to one that has not
+// either (the copy creates its own on first use).
+template <class H, int32_t (*CLONE)(H, H *), int32_t (*DESTROY)(H)>
+class cloned_handle {
+public:
+  cloned_handle() : h_(0) {}
+  ~cloned_handle() { if (h_) { DESTROY(h_); } }
+  cloned_handle(const cloned_handle &o) : h_(0) {
+    if (o.h_) { check(CLONE(o.h_, &h_), "acdsp_*_clone"); }
+  }
+  cloned_handle &operator=(const cloned_handle &o) {
+    if (this != &o) {
+      H fresh = 0;
+      if (o.h_) { check(CLONE(o.h_, &fresh), "acdsp_*_clone"); }
+      if (h_) { DESTROY(h_); }
+      h_ = fresh;
+    }
+    return *this;
+  }
+  H get() const { return h_; }
+  H *slot() { return &h_; }   // for acdsp_*_create on an empty owner
+
+private:
+  H h_;
+};
+
+// state blob of a handle (include/acdsp.h, "state save / restore") through its size / get pair
+template <class H>
+inline std::vector<unsigned char> state_of(H h, int64_t (*size)(H), int32_t (*get)(H, void *, uint64_t)) {
+  std::vector<unsigned char> blob((size_t)size(h));
+  check(get(h, blob.data(), (uint64_t)blob.size()), "acdsp_*_state_get");
+  return blob;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -400,7 +439,7 @@ private:
 template <class IN_TYPE, class INT_TYPE, class OUT_TYPE, class COEFF_TYPE, class ACC_TYPE>
 class ddc_engine {
 public:
-  ddc_engine(unsigned R, unsigned M, unsigned N, int fir_kind, int ftype, int n_taps, int n_channels = 1, int device = -1) : h_(0) {
+  ddc_engine(unsigned R, unsigned M, unsigned N, int fir_kind, int ftype, int n_taps, int n_channels = 1, int device = -1) {
     acdsp_cic_desc_t c;
     c.interp = 0; c.R = (int32_t)R; c.M = (int32_t)M; c.N = (int32_t)N; c.n_channels = n_channels;
     c.in = fmt_of<IN_TYPE>(); c.out = fmt_of<INT_TYPE>(); c.device = device < 0 ? default_device() : device; c.flags = 0;
@@ -409,27 +448,231 @@ public:
     f.in = fmt_of<INT_TYPE>(); f.coeff = fmt_of<COEFF_TYPE>(); f.acc = fmt_of<ACC_TYPE>(); f.out = fmt_of<OUT_TYPE>();
     f.device = c.device; f.flags = 0;
     n_taps_ = n_taps;
-    check(acdsp_ddc_create(&c, &f, &h_), "acdsp_ddc_create");
+    check(acdsp_ddc_create(&c, &f, h_.slot()), "acdsp_ddc_create");
   }
-  ~ddc_engine() { if (h_) { acdsp_ddc_destroy(h_); } }
+  // (copyable: acdsp_ddc_clone carries coefficients, kernel mode and the stream of both stages)
   void set_coeffs(const COEFF_TYPE *c) {
     std::vector<int64_t> r((size_t)n_taps_);
     for (size_t i = 0; i < r.size(); i++) { r[i] = raw_of(c[i]); }
-    check(acdsp_ddc_set_coeffs(h_, r.data()), "acdsp_ddc_set_coeffs");
+    check(acdsp_ddc_set_coeffs(h_.get(), r.data()), "acdsp_ddc_set_coeffs");
   }
-  int64_t out_count(int64_t n_in) { return acdsp_ddc_out_count(h_, n_in); }
-  bool fused() { return acdsp_ddc_path(h_) == 1; }
+  int64_t out_count(int64_t n_in) { return acdsp_ddc_out_count(h_.get(), n_in); }
+  bool fused() { return acdsp_ddc_path(h_.get()) == 1; }
   void run_device(const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride, int64_t *n_out, void *stream = 0) {
-    check(acdsp_ddc_run(h_, d_in, in_stride, n_in, d_out, out_stride, n_out, stream), "acdsp_ddc_run");
+    check(acdsp_ddc_run(h_.get(), d_in, in_stride, n_in, d_out, out_stride, n_out, stream), "acdsp_ddc_run");
   }
-  void reset() { check(acdsp_ddc_reset(h_), "acdsp_ddc_reset"); }
-  acdsp_ddc_t handle() { return h_; }
+  void reset() { check(acdsp_ddc_reset(h_.get()), "acdsp_ddc_reset"); }
+  acdsp_ddc_t handle() { return h_.get(); }
 
 private:
-  ddc_engine(const ddc_engine &);
-  ddc_engine &operator=(const ddc_engine &);
-  acdsp_ddc_t h_;
+  cloned_handle<acdsp_ddc_t, acdsp_ddc_clone, acdsp_ddc_destroy> h_;
   int n_taps_;
+};
+
+// ---------------------------------------------------------------------------------------------
+// Batched ac_poly_dec / ac_poly_intr / ac_intg_dump / ac_mv_avg: rows = channels (objects) behind one engine handle, in the shape of
+// cic_engine.  The descriptor comes from the template types; run() takes raw device rows (containers of in_bytes() / out_bytes(), strides in
+// elements, asynchronous on `stream`), run_host() dense host rows.  state() / set_state() are the checkpoint blobs of include/acdsp.h.
+// Copies go through acdsp_*_clone; an engine that has not created its handle yet copies nothing and the copy creates its own on first use.
+// ---------------------------------------------------------------------------------------------
+template <class IN_TYPE, class COEFF_TYPE, class ACC_TYPE, class OUT_TYPE>
+class polydec_engine {
+public:
+  polydec_engine(int n_taps, int df, int n_channels = 1, int device = -1, int flags = 0)
+      : n_taps_(n_taps), df_(df), n_ch_(n_channels), device_(device < 0 ? default_device() : device), flags_(flags) {}
+
+  int n_channels() const { return n_ch_; }
+  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
+  acdsp_polydec_t handle() { ensure(); return h_.get(); }
+  // raw STR_COEFF_TYPE words [n_taps * df]; uploaded only when they changed
+  void set_coeffs_raw(const std::vector<int64_t> &c) {
+    ensure();
+    if (c == coeffs_) { return; }
+    check(acdsp_polydec_set_coeffs(h_.get(), c.data()), "acdsp_polydec_set_coeffs");
+    coeffs_ = c;
+  }
+  void set_coeffs(const COEFF_TYPE *c) {
+    std::vector<int64_t> r((size_t)n_taps_ * df_);
+    for (size_t i = 0; i < r.size(); i++) { r[i] = raw_of(c[i]); }
+    set_coeffs_raw(r);
+  }
+  // n_in per channel, a multiple of df; n_in / df outputs per channel
+  void run(const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride, void *stream = 0) {
+    ensure();
+    check(acdsp_polydec_run(h_.get(), d_in, in_stride, n_in, d_out, out_stride, stream), "acdsp_polydec_run");
+  }
+  void run_host(const void *h_in, int64_t n_in, void *h_out) {
+    ensure();
+    check(acdsp_polydec_run_host(h_.get(), h_in, n_in, h_out), "acdsp_polydec_run_host");
+  }
+  void reset() { if (h_.get()) { check(acdsp_polydec_reset(h_.get()), "acdsp_polydec_reset"); } }
+  int path() { ensure(); return acdsp_polydec_path(h_.get()); }
+  std::vector<unsigned char> state() { ensure(); return state_of(h_.get(), acdsp_polydec_state_size, acdsp_polydec_state_get); }
+  void set_state(const std::vector<unsigned char> &blob) {
+    ensure();
+    check(acdsp_polydec_state_set(h_.get(), blob.data(), (uint64_t)blob.size()), "acdsp_polydec_state_set");
+  }
+
+private:
+  void ensure() {
+    if (h_.get()) { return; }
+    acdsp_polydec_desc_t d;
+    d.n_taps = n_taps_; d.df = df_; d.n_channels = n_ch_;
+    d.in = fmt_of<IN_TYPE>(); d.coeff = fmt_of<COEFF_TYPE>(); d.acc = fmt_of<ACC_TYPE>(); d.out = fmt_of<OUT_TYPE>();
+    d.device = device_; d.flags = flags_;
+    check(acdsp_polydec_create(&d, h_.slot()), "acdsp_polydec_create");
+  }
+  cloned_handle<acdsp_polydec_t, acdsp_polydec_clone, acdsp_polydec_destroy> h_;
+  int n_taps_, df_, n_ch_, device_, flags_;
+  std::vector<int64_t> coeffs_;   // the set on the handle
+};
+
+// ftype: ACDSP_POLY_FOLD_EVEN / _FOLD_ODD / _FOLD_ANTI
+template <class IN_TYPE, class COEFF_TYPE, class ACC_TYPE, class OUT_TYPE>
+class polyintr_engine {
+public:
+  polyintr_engine(int n_taps, int coeff_sz, int ifac, int ftype, int n_channels = 1, int device = -1, int flags = 0)
+      : n_taps_(n_taps), coeff_sz_(coeff_sz), ifac_(ifac), ftype_(ftype), n_ch_(n_channels), device_(device < 0 ? default_device() : device), flags_(flags) {}
+
+  int n_channels() const { return n_ch_; }
+  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
+  acdsp_polyintr_t handle() { ensure(); return h_.get(); }
+  // the read_ctrl phase of the reference's run(): coeffs[coeff_sz] raw words, sign[ifac], corr[ifac]; uploaded only when they changed
+  void set_ctrl_raw(const std::vector<int64_t> &c, const std::vector<unsigned char> &sign, const std::vector<unsigned char> &corr) {
+    ensure();
+    if (c == coeffs_ && sign == sign_ && corr == corr_) { return; }
+    check(acdsp_polyintr_set_ctrl(h_.get(), c.data(), sign.data(), corr.data()), "acdsp_polyintr_set_ctrl");
+    coeffs_ = c; sign_ = sign; corr_ = corr;
+  }
+  int64_t out_count(int64_t n_in) { ensure(); return acdsp_polyintr_out_count(h_.get(), n_in); }
+  void run(const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride, int64_t *n_out, void *stream = 0) {
+    ensure();
+    check(acdsp_polyintr_run(h_.get(), d_in, in_stride, n_in, d_out, out_stride, n_out, stream), "acdsp_polyintr_run");
+  }
+  void run_host(const void *h_in, int64_t n_in, void *h_out, int64_t out_cap, int64_t *n_out) {
+    ensure();
+    check(acdsp_polyintr_run_host(h_.get(), h_in, n_in, h_out, out_cap, n_out), "acdsp_polyintr_run_host");
+  }
+  void reset() { if (h_.get()) { check(acdsp_polyintr_reset(h_.get()), "acdsp_polyintr_reset"); } }
+  int path() { ensure(); return acdsp_polyintr_path(h_.get()); }
+  std::vector<unsigned char> state() { ensure(); return state_of(h_.get(), acdsp_polyintr_state_size, acdsp_polyintr_state_get); }
+  void set_state(const std::vector<unsigned char> &blob) {
+    ensure();
+    check(acdsp_polyintr_state_set(h_.get(), blob.data(), (uint64_t)blob.size()), "acdsp_polyintr_state_set");
+  }
+
+private:
+  void ensure() {
+    if (h_.get()) { return; }
+    acdsp_polyintr_desc_t d;
+    d.n_taps = n_taps_; d.coeff_sz = coeff_sz_; d.ifac = ifac_; d.ftype = ftype_; d.n_channels = n_ch_;
+    d.in = fmt_of<IN_TYPE>(); d.coeff = fmt_of<COEFF_TYPE>(); d.acc = fmt_of<ACC_TYPE>(); d.out = fmt_of<OUT_TYPE>();
+    d.device = device_; d.flags = flags_;
+    check(acdsp_polyintr_create(&d, h_.slot()), "acdsp_polyintr_create");
+  }
+  cloned_handle<acdsp_polyintr_t, acdsp_polyintr_clone, acdsp_polyintr_destroy> h_;
+  int n_taps_, coeff_sz_, ifac_, ftype_, n_ch_, device_, flags_;
+  std::vector<int64_t> coeffs_;               // the control words on the handle
+  std::vector<unsigned char> sign_, corr_;
+};
+
+// rows = objects; a row is the interleaved stream of one ac_intg_dump object, n_sample[] the per-block N_TYPE words shared by the objects
+template <class IN_TYPE, class ACC_TYPE, class OUT_TYPE>
+class intgdump_engine {
+public:
+  intgdump_engine(int ns, int chn, int n_objects = 1, int device = -1)
+      : ns_(ns), chn_(chn), n_obj_(n_objects), device_(device < 0 ? default_device() : device) {}
+
+  int n_objects() const { return n_obj_; }
+  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
+  acdsp_intgdump_t handle() { ensure(); return h_.get(); }
+  // samples a call with this block table consumes / outputs it yields, per object
+  void counts(const int64_t *n_sample, int64_t n_blocks, int64_t *n_in, int64_t *n_out) {
+    ensure();
+    check(acdsp_intgdump_counts(h_.get(), n_sample, n_blocks, n_in, n_out), "acdsp_intgdump_counts");
+  }
+  void run(const void *d_in, int64_t in_stride, const int64_t *n_sample, int64_t n_blocks, void *d_out, int64_t out_stride, int64_t *n_out,
+           void *stream = 0) {
+    ensure();
+    check(acdsp_intgdump_run(h_.get(), d_in, in_stride, n_sample, n_blocks, d_out, out_stride, n_out, stream), "acdsp_intgdump_run");
+  }
+  void run_host(const void *h_in, const int64_t *n_sample, int64_t n_blocks, void *h_out, int64_t out_cap, int64_t *n_out) {
+    ensure();
+    check(acdsp_intgdump_run_host(h_.get(), h_in, n_sample, n_blocks, h_out, out_cap, n_out), "acdsp_intgdump_run_host");
+  }
+  void reset() { if (h_.get()) { check(acdsp_intgdump_reset(h_.get()), "acdsp_intgdump_reset"); } }
+  int path() { ensure(); return acdsp_intgdump_path(h_.get()); }
+  std::vector<unsigned char> state() { ensure(); return state_of(h_.get(), acdsp_intgdump_state_size, acdsp_intgdump_state_get); }
+  void set_state(const std::vector<unsigned char> &blob) {
+    ensure();
+    check(acdsp_intgdump_state_set(h_.get(), blob.data(), (uint64_t)blob.size()), "acdsp_intgdump_state_set");
+  }
+
+private:
+  void ensure() {
+    if (h_.get()) { return; }
+    acdsp_intgdump_desc_t d;
+    d.ns = ns_; d.chn = chn_; d.n_objects = n_obj_;
+    d.in = fmt_of<IN_TYPE>(); d.acc = fmt_of<ACC_TYPE>(); d.out = fmt_of<OUT_TYPE>();
+    d.device = device_; d.flags = 0;
+    check(acdsp_intgdump_create(&d, h_.slot()), "acdsp_intgdump_create");
+  }
+  cloned_handle<acdsp_intgdump_t, acdsp_intgdump_clone, acdsp_intgdump_destroy> h_;
+  int ns_, chn_, n_obj_, device_;
+};
+
+// rows = objects; win_mode: ACDSP_WIN_PLAIN / _MIRROR / _CLIP.  ac_mv_avg keeps nothing between calls (the reference builds its core inside
+// run()): a copy carries the descriptor and the bound coefficients, reset() has nothing to do, and there is no state blob.
+template <class IN_TYPE, class COEFF_TYPE, class ACC_TYPE, class OUT_TYPE>
+class mvavg_engine {
+public:
+  mvavg_engine(int max_sample, int taps, int win_mode, int n_objects = 1, int device = -1, int flags = 0)
+      : max_sample_(max_sample), taps_(taps), win_mode_(win_mode), n_obj_(n_objects), device_(device < 0 ? default_device() : device), flags_(flags) {}
+
+  int n_objects() const { return n_obj_; }
+  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
+  acdsp_mvavg_t handle() { ensure(); return h_.get(); }
+  // raw COEFF_TYPE words [taps]; uploaded only when they changed
+  void set_coeffs_raw(const std::vector<int64_t> &c) {
+    ensure();
+    if (c == coeffs_) { return; }
+    check(acdsp_mvavg_set_coeffs(h_.get(), c.data()), "acdsp_mvavg_set_coeffs");
+    coeffs_ = c;
+  }
+  void set_coeffs(const COEFF_TYPE *c) {
+    std::vector<int64_t> r((size_t)taps_);
+    for (size_t i = 0; i < r.size(); i++) { r[i] = raw_of(c[i]); }
+    set_coeffs_raw(r);
+  }
+  int64_t out_per_frame(int64_t n_sample) { ensure(); return acdsp_mvavg_out_per_frame(h_.get(), n_sample); }
+  // n_frames frames of n_sample inputs back to back in every row = one run() call of every object
+  void run(const void *d_in, int64_t in_stride, int64_t n_sample, int64_t n_frames, void *d_out, int64_t out_stride, int64_t *n_out, void *stream = 0) {
+    ensure();
+    check(acdsp_mvavg_run(h_.get(), d_in, in_stride, n_sample, n_frames, d_out, out_stride, n_out, stream), "acdsp_mvavg_run");
+  }
+  void run_host(const void *h_in, int64_t n_sample, int64_t n_frames, void *h_out, int64_t out_cap, int64_t *n_out) {
+    ensure();
+    check(acdsp_mvavg_run_host(h_.get(), h_in, n_sample, n_frames, h_out, out_cap, n_out), "acdsp_mvavg_run_host");
+  }
+  void reset() {}
+  int path() { ensure(); return acdsp_mvavg_path(h_.get()); }
+
+private:
+  void ensure() {
+    if (h_.get()) { return; }
+    acdsp_mvavg_desc_t d;
+    d.max_sample = max_sample_; d.taps = taps_; d.win_mode = win_mode_; d.n_objects = n_obj_;
+    d.in = fmt_of<IN_TYPE>(); d.coeff = fmt_of<COEFF_TYPE>(); d.acc = fmt_of<ACC_TYPE>(); d.out = fmt_of<OUT_TYPE>();
+    d.device = device_; d.flags = flags_;
+    check(acdsp_mvavg_create(&d, h_.slot()), "acdsp_mvavg_create");
+  }
+  cloned_handle<acdsp_mvavg_t, acdsp_mvavg_clone, acdsp_mvavg_destroy> h_;
+  int max_sample_, taps_, win_mode_, n_obj_, device_, flags_;
+  std::vector<int64_t> coeffs_;   // the set on the handle
 };
 
 // ---------------------------------------------------------------------------------------------

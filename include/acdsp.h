@@ -281,6 +281,7 @@ int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride
                           int64_t out_stride, void *stream);
 int32_t acdsp_polydec_run_host(acdsp_polydec_t h, const void *h_in, int64_t n_in, void *h_out);
 int32_t acdsp_polydec_reset(acdsp_polydec_t h);
+int32_t acdsp_polydec_clone(acdsp_polydec_t h, acdsp_polydec_t *out);   /* deep copy, stream state included: "clone" below */
 int32_t acdsp_polydec_path(acdsp_polydec_t h);  /* last run(): ACDSP_PATH_GENERIC, ACDSP_PATH_MFMA_GEN (ring kernel) or ACDSP_PATH_MFMA_LONG (long prototypes) */
 /* Long prototypes (NTAPS*DF up to 16384, DF up to 256; exact-sum types of up to 16 bits whose shape the ring kernel cannot plan) run as DF
  * matrix-core FIRs on the phase streams, which a first kernel writes into a scratch buffer owned by the handle.  A call is walked as channel
@@ -305,6 +306,7 @@ int64_t acdsp_ddc_out_count(acdsp_ddc_t h, int64_t n_in);
 int32_t acdsp_ddc_run(acdsp_ddc_t h, const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride,
                       int64_t *n_out, void *stream);
 int32_t acdsp_ddc_reset(acdsp_ddc_t h);
+int32_t acdsp_ddc_clone(acdsp_ddc_t h, acdsp_ddc_t *out);               /* deep copy in the same kernel mode, stream state included: "clone" below */
 int32_t acdsp_ddc_path(acdsp_ddc_t h);                                  /* 1: fused kernel, 0: two kernels */
 int32_t acdsp_ddc_kernel_stats(acdsp_ddc_t h, int32_t last_k, float *avg_ms, float *min_ms);
 
@@ -320,6 +322,7 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
                            int64_t *n_out, void *stream);
 int32_t acdsp_polyintr_run_host(acdsp_polyintr_t h, const void *h_in, int64_t n_in, void *h_out, int64_t out_cap, int64_t *n_out);
 int32_t acdsp_polyintr_reset(acdsp_polyintr_t h);
+int32_t acdsp_polyintr_clone(acdsp_polyintr_t h, acdsp_polyintr_t *out);   /* deep copy, stream state included: "clone" below */
 int32_t acdsp_polyintr_path(acdsp_polyintr_t h);   /* kernel family of the last run(): ACDSP_PATH_GENERIC, _LOSSLESS64, _MFMA_GEN or _MFMA_LONG */
 /* Long sub-filters (NTAPS + lag >= 65 taps per phase, lag = 1 on the folded cores; up to 16384) of the exact-accumulation class on 16-bit
  * types run as IF matrix-core FIRs on the input stream.  Their phase rows go to a scratch buffer owned by the handle, and a second kernel
@@ -345,6 +348,7 @@ int32_t acdsp_intgdump_run(acdsp_intgdump_t h, const void *d_in, int64_t in_stri
 int32_t acdsp_intgdump_run_host(acdsp_intgdump_t h, const void *h_in, const int64_t *n_sample, int64_t n_blocks, void *h_out,
                                 int64_t out_cap, int64_t *n_out);
 int32_t acdsp_intgdump_reset(acdsp_intgdump_t h);
+int32_t acdsp_intgdump_clone(acdsp_intgdump_t h, acdsp_intgdump_t *out);   /* deep copy, temp[] included: "clone" below */
 int32_t acdsp_intgdump_path(acdsp_intgdump_t h);   /* kernel family of the last run(): 0 exact order (ragged blocks / carried sums / saturating ACC), 1 LDS-tiled, 2 streaming, 3 matrix cores (selection-matrix product: CHN that does not divide a 16-byte load) */
 
 /* ---- moving average (reference ac_mv_avg.h:93-196) ----
@@ -355,6 +359,7 @@ int32_t acdsp_intgdump_path(acdsp_intgdump_t h);   /* kernel family of the last 
  * calls (the reference constructs its core object inside run(), :154); coefficients are bound like ac_fir_const_coeffs'. */
 int32_t acdsp_mvavg_create(const acdsp_mvavg_desc_t *desc, acdsp_mvavg_t *out);
 int32_t acdsp_mvavg_destroy(acdsp_mvavg_t h);
+int32_t acdsp_mvavg_clone(acdsp_mvavg_t h, acdsp_mvavg_t *out);           /* descriptor and bound coefficients (there is no stream state): "clone" below */
 int32_t acdsp_mvavg_set_coeffs(acdsp_mvavg_t h, const int64_t *coeffs);   /* raw COEFF_TYPE words [TAPS] */
 int64_t acdsp_mvavg_out_per_frame(acdsp_mvavg_t h, int64_t n_sample);     /* -1: n_sample outside 1..MAX_SAMPLE */
 int32_t acdsp_mvavg_path(acdsp_mvavg_t h);   /* kernel family of the last run(): 0 exact per-tap order, 1 order-free int64 sums, 2 streaming (16-bit samples, int32 sums), 3 sliding window on 32-bit samples (int64 sums), 4 streaming with the window sums on the matrix cores (17 taps and more) */
@@ -372,8 +377,28 @@ int32_t acdsp_mvavg_run_host(acdsp_mvavg_t h, const void *h_in, int64_t n_sample
  *            reference's shift register); TRANSPOSED load/prog filters: reg_trans[0..N_TAPS-1] as int64 ACC raw words;
  *   CIC   -- the last `per_channel` input samples (both directions are FIR systems of the input)
  *            plus the number of inputs consumed so far (= rate_cnt phase).
+ *   ac_poly_dec  (kind 6; p0 = NTAPS, p1 = DF) -- the last `per_channel` input samples of every channel, oldest first, in IN containers
+ *            (taps[NTAPS*DF], ac_poly_dec.h:132; acc and acc1[] are rebuilt by every group).  A call consumes whole groups of DF: no phase.
+ *   ac_poly_intr (kind 7; p0 .. p3 = NTAPS, IF, ftype, COEFFSZ) -- the input history as above (taps[NTAPS], ac_poly_intr.h:106), the number of
+ *            inputs consumed so far in t_total (the folded cores emit nothing for a stream's first sample), and behind the histories
+ *            [channel][IF] int64 ACC raw words: the sub-filter sums of the last sample, i.e. the bank of acc_a / acc_b (:107-108) the next
+ *            sample emits.  They were formed with the control words of their own time, so they are carried, not recomputed; FOLD_ANTI emits
+ *            at once and carries zeros.
+ *   ac_intg_dump (kind 8; p0 = NS, p1 = CHN; elem_bytes 8, per_channel = CHN, n_channels = objects) -- temp[] of every object,
+ *            [object][CHN] int64 ACC raw words (ac_intg_dump.h:96-103); bit 0 of the header's last quadword is set when the stream stands
+ *            behind a block that did not dump (sums are pending in temp[]).  state_set refuses words outside ACC_TYPE, treats any non-zero
+ *            sum as pending, and the next run() rebuilds its block table instead of reusing the cached one.
+ *   ac_mv_avg keeps nothing between calls (ac_mv_avg.h:154) and has no blob.
  * state_get waits for the handle's pending run() calls.  state_set accepts only a blob from a handle of the same class,
- * parameters and channel count (ACDSP_EINVAL otherwise); coefficients are not part of the state. */
+ * parameters and channel count (ACDSP_EINVAL otherwise, the handle is left as it was); coefficients and control words are not part of
+ * the state.  A blob restores into any handle of the same descriptor whatever kernel path that handle takes (ACDSP_FLAG_FORCE_GENERIC set or
+ * clear, ring or long kernel, another set_scratch_cap): the payload is the reference's state, not a kernel's.  An input-history blob of
+ * another history LENGTH is taken when it covers the filter memory (n_taps - 1 samples; NTAPS*DF - 1; NTAPS): the newest samples are kept,
+ * older ones zero.
+ * clone (acdsp_*_clone) creates a new handle on the same device with the same descriptor, the same coefficients / control words when set,
+ * the same scratch cap on long handles and the same stream state; scratch, side stream, staging buffers, block tables and timers are its
+ * own, and afterwards neither handle is affected by what the other does.
+ * state_get, state_set and clone are synchronising host calls (they drain the device): not for a stream that is capturing a graph. */
 int64_t acdsp_fir_state_size(acdsp_fir_t h);                                   /* bytes state_get writes; -1 on a null handle */
 int32_t acdsp_fir_state_get(acdsp_fir_t h, void *h_buf, uint64_t cap_bytes);
 int32_t acdsp_fir_state_set(acdsp_fir_t h, const void *h_buf, uint64_t bytes);
@@ -385,6 +410,15 @@ int32_t acdsp_cic_state_set(acdsp_cic_t h, const void *h_buf, uint64_t bytes);
 int64_t acdsp_ddc_state_size(acdsp_ddc_t h);
 int32_t acdsp_ddc_state_get(acdsp_ddc_t h, void *h_buf, uint64_t cap_bytes);
 int32_t acdsp_ddc_state_set(acdsp_ddc_t h, const void *h_buf, uint64_t bytes);
+int64_t acdsp_polydec_state_size(acdsp_polydec_t h);
+int32_t acdsp_polydec_state_get(acdsp_polydec_t h, void *h_buf, uint64_t cap_bytes);
+int32_t acdsp_polydec_state_set(acdsp_polydec_t h, const void *h_buf, uint64_t bytes);
+int64_t acdsp_polyintr_state_size(acdsp_polyintr_t h);
+int32_t acdsp_polyintr_state_get(acdsp_polyintr_t h, void *h_buf, uint64_t cap_bytes);
+int32_t acdsp_polyintr_state_set(acdsp_polyintr_t h, const void *h_buf, uint64_t bytes);
+int64_t acdsp_intgdump_state_size(acdsp_intgdump_t h);
+int32_t acdsp_intgdump_state_get(acdsp_intgdump_t h, void *h_buf, uint64_t cap_bytes);
+int32_t acdsp_intgdump_state_set(acdsp_intgdump_t h, const void *h_buf, uint64_t bytes);
 
 /* ---- node level: one filter bank sharded over the GPUs of a node ----
  * Channels are independent filter objects (reference ac_fir_const_coeffs.h:124-127, ac_cic_full_core.h:71-74,219), so a bank of
