@@ -11,9 +11,10 @@ O_MODES = {"WRAP": 0, "SAT": 1, "SAT_ZERO": 2, "SAT_SYM": 3}
 FTYPES = {"SHIFT_REG": 0, "ROTATE_SHIFT": 1, "C_BUFF": 2, "FOLD_EVEN": 3, "FOLD_ODD": 4, "TRANSPOSED": 5,
           "FOLD_EVEN_ANTI": 6, "FOLD_ODD_ANTI": 7}
 KINDS = {"const": 0, "load": 1, "prog": 2, "reg_share": 3}
-PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 5: "mfma_lossy", 8: "mfma_long"}   # (6 = ACDSP_PATH_CIC_2STAGE: Cic.path only)
+PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 5: "mfma_lossy", 8: "mfma_long", 9: "mfma_s8"}   # (6 = ACDSP_PATH_CIC_2STAGE: Cic.path only)
 KCLASSES = {**PATHS, 6: "lossy16", 7: "satacc16"}
 FLAG_FORCE_GENERIC = 1
+FLAG_IN_BYTES = 2   # Fir / NodeFir: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
 
 
 class AcdspError(RuntimeError):
@@ -161,6 +162,7 @@ SYMBOLS = {
     "acdsp_fir_last_kernel_ms": (_i32, [_vp, C.POINTER(C.c_float)]),
     "acdsp_fir_kernel_stats": (_i32, [_vp, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "acdsp_fir_mfma_issued": (_i32, [_vp, C.POINTER(C.c_int32)]),
+    "acdsp_fir_in_elem_bytes": (_i32, [_vp]),
     "acdsp_cic_create": (_i32, [C.POINTER(CicDesc), C.POINTER(_vp)]),
     "acdsp_cic_destroy": (_i32, [_vp]),
     "acdsp_cic_clone": (_i32, [_vp, C.POINTER(_vp)]),

@@ -121,12 +121,14 @@ __host__ __device__ inline int64_t requant64(int64_t x, int f_src, const DFmt &d
 
 // Load / store a raw word from an IN / OUT container of eb bytes.
 __device__ inline int64_t load_raw(const void *p, int64_t idx, int eb, int S) {
+  if (eb == 1) { return S ? (int64_t)((const int8_t *)p)[idx] : (int64_t)((const uint8_t *)p)[idx]; }   // ACDSP_FLAG_IN_BYTES
   if (eb == 2) { return S ? (int64_t)((const int16_t *)p)[idx] : (int64_t)((const uint16_t *)p)[idx]; }
   if (eb == 4) { return S ? (int64_t)((const int32_t *)p)[idx] : (int64_t)((const uint32_t *)p)[idx]; }
   return ((const int64_t *)p)[idx];
 }
 __device__ inline void store_raw(void *p, int64_t idx, int eb, int64_t v) {
-  if (eb == 2) { ((int16_t *)p)[idx] = (int16_t)v; }
+  if (eb == 1) { ((int8_t *)p)[idx] = (int8_t)v; }
+  else if (eb == 2) { ((int16_t *)p)[idx] = (int16_t)v; }
   else if (eb == 4) { ((int32_t *)p)[idx] = (int32_t)v; }
   else { ((int64_t *)p)[idx] = v; }
 }

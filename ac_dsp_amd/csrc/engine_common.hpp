@@ -454,6 +454,10 @@ struct acdsp_fir {
   // d_corr hold its fragments
   bool long_shape = false, long_ok = false;
   FirLongPlan lplan;
+  // ACDSP_FLAG_IN_BYTES (fir_s8.hip): in_eb == 1; s8_shape = the descriptor is byte-eligible (create), s8_ok = the current set runs there; lplan,
+  // d_frag / d_corr hold its plan and fragments, s8_sum_abs = sum |c| of the effective taps (the 32-bit epilogue's bound)
+  bool s8_shape = false, s8_ok = false;
+  int64_t s8_sum_abs = 0;
   DevBuf d_gfrag;               // fragments of the generalised (wide-input) MFMA kernel
   FirGenPlan gplan;
   bool gen_ok = false;

@@ -94,6 +94,18 @@ const char *fir_long_refusal(const acdsp_fir_desc_t &d) {
   return nullptr;
 }
 
+// Byte samples (ACDSP_FLAG_IN_BYTES, fir_s8.hip): the conditions of fir_long_refusal() with the sample width and the tap range taken out -- the
+// condition a flagged descriptor fails, or nullptr when it is byte-eligible (1 .. 16384 taps on ACDSP_PATH_MFMA_S8)
+const char *fir_bytes_refusal(const acdsp_fir_desc_t &d) {
+  if (d.coeffs_per_channel) { return "one coefficient set per channel"; }
+  if (d.flags & ACDSP_FLAG_FORCE_GENERIC) { return "ACDSP_FLAG_FORCE_GENERIC (the exact-order kernels end at 2048 taps)"; }
+  if (d.coeff.S ? d.coeff.W > 16 : d.coeff.W > 15) { return "COEFF_TYPE wider than 16 bits signed / 15 bits unsigned"; }
+  if (d.acc.W > 64 || d.out.W > 64) { return "ACC_TYPE or OUT_TYPE wider than 64 bits"; }
+  if (d.ftype == ACDSP_TRANSPOSED && d.kind != ACDSP_FIR_CONST) { return "TRANSPOSED with loadable coefficients (carried reg_trans partial sums)"; }
+  if (!fir_exact_shape(d)) { return "ACC_TYPE is not an exact-sum accumulator (F_acc >= F_in + F_coeff, shift below 64; FOLD_ODD: the pre-add must fit too)"; }
+  return nullptr;
+}
+
 int fir_validate(const acdsp_fir_desc_t &d) {
   if (d.kind < ACDSP_FIR_CONST || d.kind > ACDSP_FIR_REG_SHARE) { return fail(ACDSP_EINVAL, "bad FIR class %d", d.kind); }
   if (d.ftype < 0 || d.ftype > ACDSP_FOLD_ODD_ANTI) { return fail(ACDSP_EINVAL, "bad ftype %d", d.ftype); }
@@ -125,6 +137,15 @@ int fir_validate(const acdsp_fir_desc_t &d) {
     return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 256-bit intermediates");
   }
   if (wide && d.kind == ACDSP_FIR_REG_SHARE) { return fail(ACDSP_EUNSUPPORTED, "ac_fir_reg_share: ACC / OUT wider than 64 bits not supported"); }
+  if (d.flags & ACDSP_FLAG_IN_BYTES) {
+    if (d.in.W > 8) { return fail(ACDSP_EINVAL, "ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
+    if (wide) { return fail(ACDSP_EUNSUPPORTED, "ACDSP_FLAG_IN_BYTES: ACC_TYPE or OUT_TYPE wider than 64 bits not supported"); }
+    // more than 2048 taps: the byte-sample matrix-core kernel or nothing
+    if (d.n_taps > 2048) {
+      if (const char *why = fir_bytes_refusal(d)) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: more than 2048 taps of byte samples run on the byte-sample matrix-core kernel only, which does not take %s", d.n_taps, why); }
+    }
+    return ACDSP_OK;
+  }
   // more than 2048 taps: the long matrix-core kernel or nothing
   if (d.n_taps > 2048) {
     if (const char *why = fir_long_refusal(d)) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: more than 2048 taps run on the long matrix-core kernel only, which does not take %s", d.n_taps, why); }
@@ -143,7 +164,8 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_fir> h(new acdsp_fir());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
-  h->in_eb = elem_bytes(desc->in.W);
+  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
+  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
   h->out_eb = elem_bytes(desc->out.W);
   h->wide = desc->acc.W > 64 || desc->out.W > 64;
   h->rt_eb = h->wide ? 16 : 8;
@@ -163,7 +185,9 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   h->rt_since = desc->n_taps - 1;   // an all-zero state carries no coefficients
   const bool lossless = fir_exact_shape(*desc) && (!h->use_rt || h->rt_hybrid) && !h->wide;   // (the overflow mode: below)
   h->lossless_shape = lossless;
-  h->long_shape = desc->n_taps >= kFirLongMinTaps && fir_long_refusal(*desc) == nullptr;
+  h->long_shape = !in_bytes && desc->n_taps >= kFirLongMinTaps && fir_long_refusal(*desc) == nullptr;
+  h->s8_shape = in_bytes && fir_bytes_refusal(*desc) == nullptr;
+  if (h->s8_shape && h->hl < 32 * (long_blocks(desc->n_taps) - 1)) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the byte-sample kernel's reach", h->hl); }
   // the long kernel's first step reaches 32 (NB - 1) samples back
   if (h->long_shape && h->hl < 32 * (long_blocks(desc->n_taps) - 1)) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
   h->sat_free = false;
@@ -171,7 +195,8 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   h->coeffs_set = false;
   h->path = ACDSP_PATH_GENERIC;
   const size_t n_sets = desc->coeffs_per_channel ? (size_t)desc->n_channels : 1;
-  const int nbk = fir_mfma_plan_blocks(desc->n_taps);
+  int nbk = fir_mfma_plan_blocks(desc->n_taps);
+  if (h->s8_shape && nbk < long_blocks(desc->n_taps)) { nbk = long_blocks(desc->n_taps); }   // (one tap: two K-blocks there)
   if ((rc = h->hist.init(desc->n_channels, h->hl, h->in_eb))) { return rc; }
   for (DevBuf &rt : h->d_rt) {
     if (h->use_rt && (rc = rt.alloc_zeroed((size_t)desc->n_channels * desc->n_taps * h->rt_eb))) { return rc; }
@@ -371,11 +396,34 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
       }
     }
   }
+  // byte samples (ACDSP_FLAG_IN_BYTES): one sample plane on fir_s8.hip for every tap count; above 2048 taps nothing else exists
+  h->s8_ok = false;
+  if (h->s8_shape) {
+    if (!h->lossless) {
+      if (d.n_taps > 2048) {
+        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", d.n_taps);
+      }
+    } else {
+      const std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
+      std::vector<uint32_t> frag;
+      FirLongPlan lp;
+      int64_t sa = 0;
+      if (long_plan_blocks(eff.data(), d.n_taps, &lp, &frag, &sa)) {
+        if (d.in.S) { lp.corr = 0; }   // (128 * sum(c) undoes the x - 128 of UNSIGNED samples; signed ones are the B operand as they are)
+        if ((rc = h->d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = h->d_corr.upload(&lp.corr, sizeof(int64_t)))) { return rc; }
+        h->lplan = lp;
+        h->s8_sum_abs = sa;
+        h->s8_ok = true;
+      } else if (d.n_taps > 2048) {
+        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: a coefficient of 32640 or more cannot be split into two signed bytes, and more than 2048 taps run on the matrix cores only", d.n_taps);
+      }
+    }
+  }
   // wide inputs (more than 16 bits) / other misses of the int16 kernel: generalised multi-plane MFMA kernel
   h->gen_ok = false;
   static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
   if (!h->mfma_ok && !h->long_ok && h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel && !no_gen &&
-      fits_container(d.in, h->in_eb)) {
+      (h->in_eb == 2 || h->in_eb == 4 || h->in_eb == 8) && fits_container(d.in, h->in_eb)) {
     std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
     std::vector<uint32_t> gfrag;
     if (fir_gen_plan(eff.data(), d.n_taps, 1, 0, &h->gplan, &gfrag)) {
@@ -441,6 +489,7 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
     }
   }
   h->path = h->wide ? ACDSP_PATH_WIDE
+            : h->s8_ok ? ACDSP_PATH_MFMA_S8
             : h->long_ok ? ACDSP_PATH_MFMA_LONG
             : h->mfma_ok ? ACDSP_PATH_MFMA_I8
             : h->gen_ok ? ACDSP_PATH_MFMA_GEN
@@ -483,6 +532,8 @@ int32_t acdsp_fir_kernel_class(acdsp_fir_t h) { return (h && h->coeffs_set) ? h-
 static bool fir_rows_aligned(const acdsp_fir *h, const void *d_in, int64_t in_stride, int64_t n) {
   static const bool aligned_only = getenv("ACDSP_ALIGNED_ONLY") != nullptr;   // A/B knob: the round-2 behaviour
   const int path = h->path;
+  // byte rows (fir_s8.hip) may start anywhere: a row must be readable up to the next multiple of 16 samples = 16 bytes
+  if (path == ACDSP_PATH_MFMA_S8) { return in_stride >= (n + 15) / 16 * 16; }
   bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) &&
                  (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || in_stride >= (n + 15) / 16 * 16);
   if (!aligned && !aligned_only && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG) && in_stride >= (n + 7) / 8 * 8) { aligned = true; }
@@ -498,7 +549,7 @@ int acdsp::eng::fir_capture_check(const acdsp_fir *h, const void *d_in, int64_t 
     }
   }
   const int path = h->path;
-  if (!h->wide && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) && !fir_rows_aligned(h, d_in, in_stride, n)) {
+  if (!h->wide && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_S8 || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) && !fir_rows_aligned(h, d_in, in_stride, n)) {
     // rows the matrix-core kernels do not take as they are go through the aligned staging image, which is allocated on growth
     const size_t need = (size_t)h->d.n_channels * ((n + 15) / 16 * 16) * h->in_eb;
     if (need > h->st.cap_in) {
@@ -568,7 +619,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     k.in_flip = 1;
     k.in.S = 1; k.in.lo = -32768; k.in.hi = 32767;
   }
-  if (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) {
+  if (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_S8 || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) {
     // The matrix-core kernels read rows with 16-byte vector loads (fir_gen: in whole 16-sample slots).  gfx950 serves a vector
     // access at any ELEMENT-aligned address, so the int8 kernel takes unaligned rows as they are (round 3: a row stride of 2^20 + 3
     // samples costs +12 %, profiles/r3_unaligned.txt; the staging copy below -- hipMemcpy2DAsync of misaligned rows -- cost 6.4 ms
@@ -599,6 +650,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     e = launch_fir_mfma(km, h->plan, d.coeffs_per_channel, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s);
   }
   else if (path == ACDSP_PATH_MFMA_LONG) { e = launch_fir_long(k, h->lplan, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s); }
+  else if (path == ACDSP_PATH_MFMA_S8) { e = launch_fir_s8(k, h->lplan, h->s8_sum_abs, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s); }
   else if (path == ACDSP_PATH_MFMA_GEN) { e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, 0, n, s); }
   else if (path == ACDSP_PATH_MFMA_LOSSY) {
     // complete chunks on the matrix cores, the ragged rest (and calls shorter than a chunk) on the exact-order kernel
@@ -699,9 +751,13 @@ int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples) {
     *per_1024_samples = fir_mfma_issued_per_step(fir_class_params(h, h->mfma_cshift), h->plan);
   } else if (h->path == ACDSP_PATH_MFMA_LONG) {
     *per_1024_samples = fir_long_issued_per_step(h->lplan);
+  } else if (h->path == ACDSP_PATH_MFMA_S8) {
+    *per_1024_samples = fir_s8_issued_per_step(h->lplan);
   }
   return ACDSP_OK;
 }
+
+int32_t acdsp_fir_in_elem_bytes(acdsp_fir_t h) { return h ? h->in_eb : -1; }
 
 }  // extern "C"
 

@@ -76,8 +76,15 @@ struct FirLongPlan {
 };
 // host: fragments frag[2][nb][64][4] and the plan; false if a coefficient cannot be split into two signed bytes
 bool fir_long_plan(const int64_t *coeffs, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag);
+// ... the same for any tap count of 1 .. kFirLongMaxTaps (fir_s8.hip shares the K-block count and the high-byte range); *sum_abs = sum |c| when asked for
+bool long_plan_blocks(const int64_t *coeffs, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag, int64_t *sum_abs);
 int fir_long_issued_per_step(const FirLongPlan &plan);   // two low-plane products per K-block + two per K-block of [hb0, hb1]
 hipError_t launch_fir_long(const FirParams &p, const FirLongPlan &plan, const uint32_t *d_frag, const int64_t *d_corr, hipStream_t s);
+// Byte samples (ACDSP_FLAG_IN_BYTES, fir_s8.hip): 1 .. 16384 taps of the exact-sum class on 1-byte IN containers, ONE sample plane: one product
+// per K-block and one more per K-block of [hb0, hb1].  plan / d_frag / d_corr as for launch_fir_long (corr: 128 * sum(c) for unsigned samples,
+// 0 for signed ones); sum_abs = sum |c| picks the 32-bit epilogue where it is provably exact
+int fir_s8_issued_per_step(const FirLongPlan &plan);
+hipError_t launch_fir_s8(const FirParams &p, const FirLongPlan &plan, int64_t sum_abs, const uint32_t *d_frag, const int64_t *d_corr, hipStream_t s);
 // The polyphase long kernels (polydec_long.hip, polyintr_long.hip) walk `phases` filters of nt taps each per step.  host: c = [phases][nt]
 // taps -> fragments frag[2][phases * long_blocks(nt)][64][4] and the per-phase corrections 128 * sum(c_d); false if a tap cannot be split
 // into two signed bytes

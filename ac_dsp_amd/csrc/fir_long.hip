@@ -203,14 +203,14 @@ LongGrid long_grid(int64_t n_steps, int rows, int64_t min_steps) {
   return {spw, (unsigned)((n_steps + spw - 1) / spw), (unsigned)wg_rows};
 }
 
-bool fir_long_plan(const int64_t *c, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag) {
-  if (n_taps < kFirLongMinTaps || n_taps > kFirLongMaxTaps) { return false; }
+bool long_plan_blocks(const int64_t *c, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag, int64_t *sum_abs) {
   const int nb = long_blocks(n_taps);
   frag->assign((size_t)2 * nb * 64 * 4, 0u);
   FirMfmaPlan mp;
   if (!fir_mfma_build_fragments_nb(c, n_taps, nb, &mp, frag->data())) { return false; }
   plan->nb = nb;
   plan->corr = mp.corr;
+  if (sum_abs) { *sum_abs = mp.sum_abs; }
   // K-block b holds taps i - k + 32 (nb - 1 - b), i, k = 0 .. 31: tap t sits in the blocks b with |32 (nb - 1 - b) - t| <= 31.  The range
   // of blocks with a non-zero high byte follows from the first and the last such tap (the 64-bit masks of FirMfmaPlan end at block 63).
   int t_first = -1, t_last = -1;
@@ -227,6 +227,11 @@ bool fir_long_plan(const int64_t *c, int n_taps, FirLongPlan *plan, std::vector<
   plan->hb1 = nb - 1 - (t_first > 31 ? (t_first - 31 + 31) / 32 : 0);
   if (plan->hb0 < 0) { plan->hb0 = 0; }
   return true;
+}
+
+bool fir_long_plan(const int64_t *c, int n_taps, FirLongPlan *plan, std::vector<uint32_t> *frag) {
+  if (n_taps < kFirLongMinTaps || n_taps > kFirLongMaxTaps) { return false; }
+  return long_plan_blocks(c, n_taps, plan, frag, nullptr);
 }
 
 int fir_long_issued_per_step(const FirLongPlan &plan) {

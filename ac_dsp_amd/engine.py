@@ -21,6 +21,13 @@ def _np_dtype_for(fmt):
     return {2: np.int16, 4: np.int32, 8: np.int64, 16: np.int64}[lib.acdsp_elem_bytes(fmt.W)]
 
 
+def _np_in_dtype(fmt, in_bytes):
+    """numpy dtype of FIR input rows: 1-byte containers under in_bytes (ACDSP_FLAG_IN_BYTES)"""
+    if in_bytes:
+        return np.int8 if fmt.S else np.uint8
+    return _np_dtype_for(fmt)
+
+
 def is_wide(fmt):
     return lib.acdsp_elem_bytes(fmt.W) == 16
 
@@ -193,13 +200,15 @@ class Fir:
     """n_channels independent reference FIR objects (ac_fir_{const,load,prog}_coeffs) behind one handle."""
 
     def __init__(self, n_taps, ftype, fin, fcoeff, facc, fout, n_channels=1, kind="load", coeffs_per_channel=False,
-                 device=0, force_generic=False):
+                 device=0, force_generic=False, in_bytes=False):
+        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
         self.fin, self.fcoeff, self.facc, self.fout = fin, fcoeff, facc, fout
         self.n_taps, self.n_channels, self.device = n_taps, n_channels, device
         self.coeffs_per_channel = bool(coeffs_per_channel)
+        self.in_bytes = bool(in_bytes)
         d = FirDesc(KINDS[kind] if isinstance(kind, str) else kind, FTYPES[ftype] if isinstance(ftype, str) else ftype,
                     n_taps, n_channels, int(self.coeffs_per_channel), fin, fcoeff, facc, fout, device,
-                    _lib.FLAG_FORCE_GENERIC if force_generic else 0)
+                    (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0))
         self._h = C.c_void_p()
         check(lib.acdsp_fir_create(C.byref(d), C.byref(self._h)))
 
@@ -208,6 +217,13 @@ class Fir:
         want = (self.n_channels, self.n_taps) if self.coeffs_per_channel else (self.n_taps,)
         assert c.shape == want, (c.shape, want)
         check(lib.acdsp_fir_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
+
+    @property
+    def in_dtype(self):
+        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
+        if self.in_bytes:
+            return torch.int8 if self.fin.S else torch.uint8
+        return torch_dtype_for(self.fin)
 
     @property
     def path(self):
@@ -226,7 +242,7 @@ class Fir:
     def run(self, x, out=None):
         """x: [n_channels][n] device tensor of IN containers -> [n_channels][n] OUT containers."""
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_channels and x.stride(1) == 1
-        assert x.dtype == torch_dtype_for(self.fin), (x.dtype, self.fin)
+        assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         n = x.shape[1]
         if out is None:
             out = _alloc_out(self.fout, self.n_channels, n, x.device)
@@ -236,7 +252,7 @@ class Fir:
         return out
 
     def run_host(self, x):
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_dtype_for(self.fin))
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_in_dtype(self.fin, self.in_bytes))
         assert x.shape[0] == self.n_channels
         y = _alloc_out_host(self.fout, self.n_channels, x.shape[1])
         check(lib.acdsp_fir_run_host(self._h, x.ctypes.data_as(C.c_void_p), x.shape[1], y.ctypes.data_as(C.c_void_p)))
@@ -266,7 +282,7 @@ class Fir:
         return a.value, m.value
 
     def mfma_issued(self):
-        """32x32x32 int8 MFMAs the selected kernel issues per 1024 samples of one channel (0 off the "mfma_i8" and "mfma_long" paths)."""
+        """32x32x32 int8 MFMAs the selected kernel issues per 1024 samples of one channel (0 off the "mfma_i8", "mfma_long" and "mfma_s8" paths)."""
         v = C.c_int32()
         check(lib.acdsp_fir_mfma_issued(self._h, C.byref(v)))
         return v.value
@@ -706,10 +722,11 @@ class _Node:
     def _dev_array(devices):
         return (C.c_int32 * len(devices))(*devices)
 
-    def _ptrs(self, tensors, fmt):
+    def _ptrs(self, tensors, fmt, dtype=None):
         assert len(tensors) == self.n_shards
+        dtype = dtype or torch_dtype_for(fmt)
         for t, (lo, hi), d in zip(tensors, self.slices, self.devices):
-            assert t.is_cuda and _dev_index(t.device) == d and t.shape[0] == hi - lo and t.dtype == torch_dtype_for(fmt), (t.shape, t.device, lo, hi, d)
+            assert t.is_cuda and _dev_index(t.device) == d and t.shape[0] == hi - lo and t.dtype == dtype, (t.shape, t.device, lo, hi, d)
         strides = {_row_stride(t, fmt) for t in tensors}
         assert len(strides) == 1, "every shard's block must have the same row stride"
         # The node handle launches on its workers' own non-blocking streams, which do not order with torch's streams: the blocks must be
@@ -752,11 +769,12 @@ class _Node:
 class NodeFir(_Node):
     """A Fir bank sharded over `devices` (acdsp_node_fir_*): no collective, coefficients replicated (or sliced when per channel)."""
 
-    def __init__(self, n_taps, ftype, fin, fcoeff, facc, fout, n_channels, devices, kind="load", coeffs_per_channel=False):
+    def __init__(self, n_taps, ftype, fin, fcoeff, facc, fout, n_channels, devices, kind="load", coeffs_per_channel=False, in_bytes=False):
         self.fin, self.fout, self.n_taps, self.n_channels = fin, fout, n_taps, n_channels
         self.coeffs_per_channel = bool(coeffs_per_channel)
+        self.in_bytes = bool(in_bytes)
         d = FirDesc(KINDS[kind], FTYPES[ftype] if isinstance(ftype, str) else ftype, n_taps, n_channels, int(self.coeffs_per_channel),
-                    fin, fcoeff, facc, fout, 0, 0)
+                    fin, fcoeff, facc, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
         self._h = C.c_void_p()
         check(lib.acdsp_node_fir_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -772,13 +790,13 @@ class NodeFir(_Node):
         assert all(x.shape[1] == n for x in xs)
         if outs is None:
             outs = self.alloc(self.fout, n)
-        pin, sin = self._ptrs(xs, self.fin)
+        pin, sin = self._ptrs(xs, self.fin, (torch.int8 if self.fin.S else torch.uint8) if self.in_bytes else None)
         pout, sout = self._ptrs(outs, self.fout)
         check(lib.acdsp_node_fir_run(self._h, pin, sin, n, pout, sout))
         return outs
 
     def run_host(self, x):
-        x = np.ascontiguousarray(x, dtype=_np_dtype_for(self.fin))
+        x = np.ascontiguousarray(x, dtype=_np_in_dtype(self.fin, self.in_bytes))
         assert x.shape[0] == self.n_channels
         y = _alloc_out_host(self.fout, self.n_channels, x.shape[1])
         check(lib.acdsp_node_fir_run_host(self._h, x.ctypes.data_as(C.c_void_p), x.shape[1], y.ctypes.data_as(C.c_void_p)))

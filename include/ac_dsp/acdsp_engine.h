@@ -93,13 +93,15 @@ template <class T> inline T from_raw(int64_t r) {
 template <class T, bool WIDE = (T::width > 64)> struct container_io {
   static void store(const T &v, unsigned char *p, int eb) {
     const int64_t r = raw_of(v);
-    if (eb == 2) { int16_t t = (int16_t)r; memcpy(p, &t, 2); }
+    if (eb == 1) { p[0] = (unsigned char)r; }   // ACDSP_FLAG_IN_BYTES
+    else if (eb == 2) { int16_t t = (int16_t)r; memcpy(p, &t, 2); }
     else if (eb == 4) { int32_t t = (int32_t)r; memcpy(p, &t, 4); }
     else { memcpy(p, &r, 8); }
   }
   static T load(const unsigned char *p, int eb) {
     int64_t r;
-    if (eb == 2) { int16_t t; memcpy(&t, p, 2); r = T::sign ? (int64_t)t : (int64_t)(uint16_t)t; }
+    if (eb == 1) { r = T::sign ? (int64_t)(signed char)p[0] : (int64_t)p[0]; }
+    else if (eb == 2) { int16_t t; memcpy(&t, p, 2); r = T::sign ? (int64_t)t : (int64_t)(uint16_t)t; }
     else if (eb == 4) { int32_t t; memcpy(&t, p, 4); r = T::sign ? (int64_t)t : (int64_t)(uint32_t)t; }
     else { memcpy(&r, p, 8); }
     return from_raw<T>(r);
@@ -178,20 +180,21 @@ inline std::vector<unsigned char> state_of(H h, int64_t (*size)(H), int32_t (*ge
 template <class IN_TYPE, class OUT_TYPE, class COEFF_TYPE, class ACC_TYPE>
 class fir_engine {
 public:
-  fir_engine(int kind, int ftype, int n_taps, int n_channels = 1, bool coeffs_per_channel = false, int device = -1)
+  // flags: ACDSP_FLAG_* of acdsp_fir_desc_t (ACDSP_FLAG_IN_BYTES: in_bytes() == 1, rows of 1-byte containers)
+  fir_engine(int kind, int ftype, int n_taps, int n_channels = 1, bool coeffs_per_channel = false, int device = -1, int flags = 0)
       : h_(0), kind_(kind), ftype_(ftype), n_taps_(n_taps), n_ch_(n_channels), per_ch_(coeffs_per_channel),
-        device_(device < 0 ? default_device() : device), head_(0), host_valid_(true), host_ahead_(false) {}
+        device_(device < 0 ? default_device() : device), flags_(flags), head_(0), host_valid_(true), host_ahead_(false) {}
   ~fir_engine() { if (h_) { acdsp_fir_destroy(h_); } }
   // The reference objects are plain aggregates: copying one copies its state.
   fir_engine(const fir_engine &o)
       : h_(0), kind_(o.kind_), ftype_(o.ftype_), n_taps_(o.n_taps_), n_ch_(o.n_ch_), per_ch_(o.per_ch_), device_(o.device_),
-        coeffs_(o.coeffs_), ring_(o.ring_), rt_(o.rt_), head_(o.head_), host_valid_(o.host_valid_), host_ahead_(o.host_ahead_) {
+        flags_(o.flags_), coeffs_(o.coeffs_), ring_(o.ring_), rt_(o.rt_), head_(o.head_), host_valid_(o.host_valid_), host_ahead_(o.host_ahead_) {
     if (o.h_) { check(acdsp_fir_clone(o.h_, &h_), "acdsp_fir_clone"); }
   }
   fir_engine &operator=(const fir_engine &o) {
     if (this != &o) {
       if (h_) { acdsp_fir_destroy(h_); h_ = 0; }
-      kind_ = o.kind_; ftype_ = o.ftype_; n_taps_ = o.n_taps_; n_ch_ = o.n_ch_; per_ch_ = o.per_ch_; device_ = o.device_;
+      kind_ = o.kind_; ftype_ = o.ftype_; n_taps_ = o.n_taps_; n_ch_ = o.n_ch_; per_ch_ = o.per_ch_; device_ = o.device_; flags_ = o.flags_;
       coeffs_ = o.coeffs_;
       ring_ = o.ring_; rt_ = o.rt_; head_ = o.head_; host_valid_ = o.host_valid_; host_ahead_ = o.host_ahead_;
       if (o.h_) { check(acdsp_fir_clone(o.h_, &h_), "acdsp_fir_clone"); }
@@ -200,7 +203,7 @@ public:
   }
 
   int n_channels() const { return n_ch_; }
-  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int in_bytes() const { return (flags_ & ACDSP_FLAG_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
   int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
   // the raw engine handle (state blobs, kernel statistics ...): the device becomes the authority on the filter state
   acdsp_fir_t handle() { ensure(); to_device(); host_valid_ = false; return h_; }
@@ -357,13 +360,13 @@ private:
     acdsp_fir_desc_t d;
     d.kind = kind_; d.ftype = ftype_; d.n_taps = n_taps_; d.n_channels = n_ch_; d.coeffs_per_channel = per_ch_ ? 1 : 0;
     d.in = fmt_of<IN_TYPE>(); d.coeff = fmt_of<COEFF_TYPE>(); d.acc = fmt_of<ACC_TYPE>(); d.out = fmt_of<OUT_TYPE>();
-    d.device = device_; d.flags = 0;
+    d.device = device_; d.flags = flags_;
     check(acdsp_fir_create(&d, &h_), "acdsp_fir_create");
   }
   acdsp_fir_t h_;
   int kind_, ftype_, n_taps_, n_ch_;
   bool per_ch_;
-  int device_;
+  int device_, flags_;
   std::vector<int64_t> coeffs_;
   // host-side mirror of the one-channel state (tiny calls): ring of the last N_TAPS samples, or the TRANSPOSED partial sums
   std::vector<IN_TYPE> ring_;

@@ -61,6 +61,11 @@ enum {
 
 /* flags */
 #define ACDSP_FLAG_FORCE_GENERIC 1 /* never pick the MFMA / fast kernels (parity tests) */
+/* acdsp_fir_desc_t::flags only.  IN_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE containers: the caller's input rows, the handle's
+ * history and the FIR state blob hold int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() == 1; acdsp_elem_bytes() is not asked for the
+ * input).  in_stride stays in elements; the output containers are unchanged.  W > 8: ACDSP_EINVAL; ACC_TYPE / OUT_TYPE wider than 64 bits and
+ * the FIR of acdsp_ddc_create: ACDSP_EUNSUPPORTED.  INTEGRATION.md "Byte samples". */
+#define ACDSP_FLAG_IN_BYTES 2
 
 /* which kernel family a FIR handle resolved to (acdsp_fir_path) */
 enum { ACDSP_PATH_GENERIC = 0, ACDSP_PATH_LOSSLESS64 = 1, ACDSP_PATH_MFMA_I8 = 2, ACDSP_PATH_MFMA_GEN = 3,
@@ -68,7 +73,9 @@ enum { ACDSP_PATH_GENERIC = 0, ACDSP_PATH_LOSSLESS64 = 1, ACDSP_PATH_MFMA_I8 = 2
        ACDSP_PATH_MFMA_LOSSY = 5 /* lossy wrapping accumulator (per-tap AC_TRN / AC_RND): exact sum on the matrix cores minus the dropped bits */,
        ACDSP_PATH_CIC_2STAGE = 6 /* ac_cic_dec_full with R = R1 R2: FIR identity of rate R1 on the matrix cores, integrators / combs of rate R2 behind it, one launch */,
        ACDSP_PATH_MFMA_LONG = 8 /* 1026 .. 16384 taps of the exact-sum class on 16-bit types: the int8 split of ACDSP_PATH_MFMA_I8 with the coefficient
-                                  * fragments walked in LDS segments (7 is ACDSP_KCLASS_SATACC16 in the value space of acdsp_fir_kernel_class) */ };
+                                  * fragments walked in LDS segments (7 is ACDSP_KCLASS_SATACC16 in the value space of acdsp_fir_kernel_class) */,
+       ACDSP_PATH_MFMA_S8 = 9 /* ACDSP_FLAG_IN_BYTES, 1 .. 16384 taps of the exact-sum class: the samples are ONE byte plane, one product per K-block
+                                * and one more where the coefficient set has a high byte (fir_s8.hip) */ };
 /* finer: the kernel family inside ACDSP_PATH_GENERIC (acdsp_fir_kernel_class; the other values equal the path) */
 enum { ACDSP_KCLASS_LOSSY16 = 6 /* fir_lossy_kernel: class B on 16-bit types, int32 VALU */,
        ACDSP_KCLASS_SATACC16 = 7 /* fir_satacc_kernel: saturating accumulator of <= 32 bits on 16-bit types, reference tap order */ };
@@ -78,7 +85,8 @@ typedef struct {
   int32_t ftype;              /* ACDSP_SHIFT_REG ... */
   int32_t n_taps;             /* 1 .. 2048 for every class; 2049 .. 16384 only for descriptors the long matrix-core kernel takes (one shared
                                * coefficient set, 16-bit samples and coefficients, exact-sum ACC_TYPE of <= 64 bits, no carried reg_trans:
-                               * INTEGRATION.md "Long filters"), else acdsp_fir_create fails with ACDSP_EUNSUPPORTED */
+                               * INTEGRATION.md "Long filters"; with ACDSP_FLAG_IN_BYTES the same conditions on 8-bit samples: "Byte samples"),
+                               * else acdsp_fir_create fails with ACDSP_EUNSUPPORTED */
   int32_t n_channels;
   int32_t coeffs_per_channel; /* 0: one coefficient set shared by all channels, 1: one set per channel */
   acdsp_fmt_t in, coeff, acc, out;
@@ -253,9 +261,12 @@ int32_t acdsp_fir_last_kernel_ms(acdsp_fir_t h, float *ms);
 /* Average / minimum main-kernel duration over the last `last_k` (<= 64) run() calls. */
 int32_t acdsp_fir_kernel_stats(acdsp_fir_t h, int32_t last_k, float *avg_ms, float *min_ms);
 /* 32x32x32 int8 MFMA instructions the selected kernel issues per 1024 samples of one channel (0 when the current
- * coefficients run on neither ACDSP_PATH_MFMA_I8 nor ACDSP_PATH_MFMA_LONG): the numerator of an MFMA-utilisation figure.  All-zero
- * high-byte blocks of the coefficient set are not issued, so this is <= 4 * (ceil((n_taps - 1) / 32) + 1). */
+ * coefficients run on none of ACDSP_PATH_MFMA_I8, ACDSP_PATH_MFMA_LONG and ACDSP_PATH_MFMA_S8): the numerator of an MFMA-utilisation figure.
+ * All-zero high-byte blocks of the coefficient set are not issued, so this is <= 4 * (ceil((n_taps - 1) / 32) + 1).  ACDSP_PATH_MFMA_S8:
+ * nb + (hb1 - hb0 + 1), nb = max(2, ceil((n_taps - 1) / 32) + 1) K-blocks and [hb0, hb1] those that hold a non-zero high coefficient byte. */
 int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples);
+/* bytes of one INPUT container of the handle: 1 under ACDSP_FLAG_IN_BYTES, else acdsp_elem_bytes(in.W) */
+int32_t acdsp_fir_in_elem_bytes(acdsp_fir_t h);
 
 /* ---- CIC ---- */
 int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out);
