@@ -14,7 +14,7 @@ KINDS = {"const": 0, "load": 1, "prog": 2, "reg_share": 3}
 PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 5: "mfma_lossy", 8: "mfma_long", 9: "mfma_s8"}   # (6 = ACDSP_PATH_CIC_2STAGE: Cic.path only)
 KCLASSES = {**PATHS, 6: "lossy16", 7: "satacc16"}
 FLAG_FORCE_GENERIC = 1
-FLAG_IN_BYTES = 2   # Fir / NodeFir: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
+FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator): IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
 
 
 class AcdspError(RuntimeError):
@@ -172,6 +172,8 @@ SYMBOLS = {
     "acdsp_cic_run_host": (_i32, [_vp, _vp, _i64, _vp, _i64, C.POINTER(_i64)]),
     "acdsp_cic_reset": (_i32, [_vp]),
     "acdsp_cic_path": (_i32, [_vp]),
+    "acdsp_cic_in_elem_bytes": (_i32, [_vp]),
+    "acdsp_cic_two_stage_rates": (_i32, [C.POINTER(CicDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "acdsp_cic_last_kernel_ms": (_i32, [_vp, C.POINTER(C.c_float)]),
     "acdsp_cic_kernel_stats": (_i32, [_vp, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "acdsp_polydec_create": (_i32, [C.POINTER(PolyDecDesc), C.POINTER(_vp)]),

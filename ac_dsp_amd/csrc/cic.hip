@@ -135,6 +135,7 @@ __global__ void __launch_bounds__(64) cic_kernel(CicParams p) {
     if (sizeof(TIN) == 8) { return (uint64_t)raw; }
     if (p.in.S) { return (uint64_t)(int64_t)raw; }
     if (sizeof(TIN) == 4) { return (uint64_t)(uint32_t)raw; }
+    if (sizeof(TIN) == 1) { return (uint64_t)(uint8_t)raw; }   // ACDSP_FLAG_IN_BYTES
     return (uint64_t)(uint16_t)raw;
   };
   auto out_word = [&](uint64_t val) -> int64_t {
@@ -245,9 +246,19 @@ static hipError_t launch_n_t(const CicParams &p, dim3 grid, hipStream_t s) {
   return hipGetLastError();
 }
 
+// byte rows (ACDSP_FLAG_IN_BYTES): the decimator only -- acdsp_cic_create refuses the flag on an interpolator
+template <int N>
+static hipError_t launch_n_bytes(const CicParams &p, dim3 grid, hipStream_t s) {
+  if (p.interp) { return hipErrorInvalidValue; }
+  if (p.me == 2) { hipLaunchKernelGGL((cic_kernel<N, int8_t, false, 2>), grid, dim3(64), 0, s, p); }
+  else { hipLaunchKernelGGL((cic_kernel<N, int8_t, false, 1>), grid, dim3(64), 0, s, p); }
+  return hipGetLastError();
+}
+
 template <int N>
 static hipError_t launch_n(const CicParams &p, dim3 grid, hipStream_t s) {
   switch (p.in_eb) {
+    case 1: return launch_n_bytes<N>(p, grid, s);
     case 2: return launch_n_t<N, int16_t>(p, grid, s);
     case 4: return launch_n_t<N, int32_t>(p, grid, s);
     default: return launch_n_t<N, int64_t>(p, grid, s);

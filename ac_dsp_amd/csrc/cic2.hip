@@ -2,7 +2,7 @@
 //
 // The factorisation R = R1 R2, the two stages and the kernel itself are in cic2_kernels.hpp, with the table of compiled stage-1 shapes.
 // This unit holds the host side (cic2_factor, cic2_hist_len, launch_cic2) and compiles the first shape; cic2_b.hip .. cic2_f.hip compile
-// the others, for compile time.
+// the others and cic2_s8.hip .. cic2_s8_c.hip the byte-row shapes (ACDSP_FLAG_IN_BYTES), for compile time.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -121,6 +121,9 @@ hipError_t launch_cic2(const CicParams &p, const FirGenPlan &pl, const uint32_t 
     a.pw = (ok && !no_pw) ? 1 : 0;
     unsigned __int128 bias = 0;
     for (int q = 0; q < px - 1; q++) { bias += (unsigned __int128)1 << (8 * q); }
+    // byte rows (px = 1) of an unsigned IN_TYPE: the kernel flips the sign bit of its only plane, x - 128, and reads a non-zero corr as the
+    // order to do so (sum_h = R1^N > 0 and far below 2^57: 128 sum_h is never 0 mod 2^64)
+    if (px == 1 && !p.in.S) { bias += 1; }
     a.corr = (int64_t)(unsigned long long)((unsigned __int128)128 * bias * (unsigned long long)pl.sum_h);
   }
   { ACDSP_TUNE_ENV(dbg_env, "ACDSP_CIC2_DBG"); a.dbg = dbg_env ? atoi(dbg_env) : 0; }

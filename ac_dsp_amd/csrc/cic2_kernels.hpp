@@ -1,5 +1,5 @@
 // cic2_kernels.hpp -- the kernel of the two-stage CIC decimator, its launcher templates and the table of compiled stage-1 shapes, shared by
-// the six translation units of the family: cic2.hip (host side) and cic2_b.hip .. cic2_f.hip.  Each unit names the shapes it compiles
+// the translation units of the family: cic2.hip (host side), cic2_b.hip .. cic2_f.hip and cic2_s8.hip .. cic2_s8_c.hip (byte rows).  Each unit names the shapes it compiles
 // (ACDSP_CIC2_COMPILE) and compiles no other kernel; cic_kernels.hpp stays the interface to the engine layer.
 //
 // What it replaces: ac_cic_full_core_intg::intStage / decIntgCore (reference include/ac_dsp/ac_cic_full_core.h:80-87,110-135) and
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(64, 2) cic2_kernel(Cic2Args a, const v4i *__re
   constexpr int NLD = R1 * S * M / 4;
   constexpr int PPB = 16 / S;
   constexpr int SPK = 64 / S;
-  static_assert(S == 2 || S == 4, "2- and 4-byte samples");
+  static_assert(S == 1 || S == 2 || S == 4, "1- (ACDSP_FLAG_IN_BYTES), 2- and 4-byte samples");
   static_assert(G % (2 * M) == 0 && G <= 4, "a batch holds whole pairs of load groups");
   constexpr bool HOLES = (R1 % 2 == 0 && SPK % R1 == 0);
   static_assert(H <= ADV && S * H <= 64 && NLD * SPK == M * ADV && NLD >= 1, "ring geometry");
@@ -184,6 +184,14 @@ __global__ void __launch_bounds__(64, 2) cic2_kernel(Cic2Args a, const v4i *__re
     }
   };
   auto stage_piece = [&](const v4i &v, int off) __attribute__((always_inline)) {
+    if constexpr (S == 1) {
+      // byte rows: a 16-byte piece is one whole slot of the only plane, which is the signed top plane -- no gather, no re-bias.  Unsigned
+      // samples (offset binary) have their sign bit flipped here, x - 128; the host then sets corr = 128 sum(h1), and with one plane corr is
+      // non-zero for nothing else (launch_cic2), so it doubles as the flag and Cic2Args keeps its layout
+      const int fx = a.corr != 0 ? (int)0x80808080u : 0;
+      *(v4i *)(lds + off) = v ^ (v4i){fx, fx, fx, fx};
+      return;
+    }
 #pragma unroll
     for (int pp = 0; pp < PX; pp++) {
       if constexpr (S == 2) {
@@ -425,7 +433,7 @@ hipError_t launch_g(int g, int n, dim3 grid, hipStream_t s, const Cic2Args &a, c
 // z^-(N-1) boxcar(R1)^N for every N <= 6 (R1 = 15: N <= 5 -- fifteen 1 KB loads per register set leave no room for a third digit plane;
 // launch_cic2 declines a plan that does not fit and the call stays on the recurrence kernel).  The order is the order of preference where several rates divide R: the most input bytes per
 // step first (a step's fixed work -- fragment reads, recombination, the prefix-sum levels -- is per 256 u, whatever R1).
-// Every shape has one launcher, cic2_launch_<tag>, declared here; the shapes are spread over the six translation units for compile time:
+// Every shape has one launcher, cic2_launch_<tag>, declared here; the shapes are spread over the translation units for compile time:
 // the unit that names a tag in ACDSP_CIC2_COMPILE defines its launcher and so compiles its kernels (a shape no unit names, or one that two
 // units name, does not link).
 #define ACDSP_CIC2_SHAPES(X)                                                                                     \
@@ -435,7 +443,8 @@ hipError_t launch_g(int g, int n, dim3 grid, hipStream_t s, const Cic2Args &a, c
   X(int16_t, s16_r3, 2, 3, 2, 2)                                                                                 \
   X(int32_t, s32_r10, 4, 10, 3, 4) X(int32_t, s32_r8, 4, 8, 2, 3) X(int32_t, s32_r7, 4, 7, 2, 3)                 \
   X(int32_t, s32_r6, 4, 6, 2, 2) X(int32_t, s32_r5, 4, 5, 2, 2) X(int32_t, s32_r4, 4, 4, 2, 2)                   \
-  X(int32_t, s32_r3, 4, 3, 2, 2)
+  X(int32_t, s32_r3, 4, 3, 2, 2)                                                                                 \
+  X(int8_t, s8_r16, 1, 16, 3, 6) X(int8_t, s8_r8, 1, 8, 2, 3) X(int8_t, s8_r4, 1, 4, 2, 2)
 #define ACDSP_CIC2_DECL(TIN, TAG, EB, R1V, PCTV, NBTV)                                                                    \
   struct cic2_shape_##TAG { typedef TIN tin; static constexpr int r1 = R1V, pct = PCTV, nbt = NBTV; };                   \
   hipError_t cic2_launch_##TAG(int g, int n, dim3 grid, hipStream_t s, const Cic2Args &a, const v4i *frag);

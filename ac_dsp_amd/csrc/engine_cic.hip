@@ -31,6 +31,14 @@ int cic_int_type(const acdsp_cic_desc_t &d, acdsp_fmt_t *it) {
   return ACDSP_OK;
 }
 
+// ACDSP_FLAG_IN_BYTES on a CIC descriptor: what is refused before any device use
+int cic_bytes_refusal(const acdsp_cic_desc_t &d) {
+  if (d.in.W > 8) { return fail(ACDSP_EINVAL, "CIC: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
+  if (d.interp) { return fail(ACDSP_EUNSUPPORTED, "CIC: ACDSP_FLAG_IN_BYTES on an interpolator (interp == 1) is not supported: its input stream is the thin one"); }
+  if (d.out.W > 64) { return fail(ACDSP_EUNSUPPORTED, "CIC: ACDSP_FLAG_IN_BYTES with an OUT_TYPE wider than 64 bits (W=%d) is not supported", d.out.W); }
+  return ACDSP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -59,11 +67,13 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   if (desc->interp && desc->N > 255) { return fail(ACDSP_EUNSUPPORTED, "CIC: N too large"); }
   if (desc->n_channels < 1) { return fail(ACDSP_EINVAL, "CIC: n_channels=%d must be positive", desc->n_channels); }
   if (desc->n_channels > 65535) { return fail(ACDSP_EUNSUPPORTED, "CIC: n_channels=%d outside 1..65535", desc->n_channels); }
+  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
+  if (in_bytes && (rc = cic_bytes_refusal(*desc))) { return rc; }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_cic> h(new acdsp_cic());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   h->it = it;
-  h->in_eb = elem_bytes(desc->in.W);
+  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
   h->out_eb = elem_bytes(desc->out.W);
   h->me = desc->M < 2 ? desc->M : 2;  // effective comb delay of the reference's delay line, see cic.hip
   h->wide = it.W > 64 || desc->out.W > 64;
@@ -76,7 +86,8 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   FirGenPlan probe;
   std::vector<uint32_t> fr;
   // decimator on the matrix cores through that identity (fir_gen.hip): where the taps have a plan at both ends of the window offsets
-  h->gen_ok = !desc->interp && !h->wide && !no_gen && fits_container(desc->in, h->in_eb) &&
+  // (byte rows: fir_gen.hip has no 1-byte shape -- every rate with a byte stage-1 shape goes to the two-stage kernel, the rest to the recurrence kernel)
+  h->gen_ok = !in_bytes && !desc->interp && !h->wide && !no_gen && fits_container(desc->in, h->in_eb) &&
               fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 15, &probe, &fr) &&   // worst-case window offset
               fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 0, &probe, &fr);
   {
@@ -89,7 +100,7 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
     // (ACDSP_NO_GEN: the two-stage kernel is a multi-plane matrix-core kernel too -- without the check a handle whose one-stage identity the knob
     // switched off came here instead of to the recurrence kernel, with the longer history of this kernel)
     static const bool c2_all = getenv("ACDSP_CIC2_ALL") != nullptr;       // A/B knob: also where the one-stage FIR identity fits (R < 32)
-    if (!desc->interp && !h->wide && !no_c2 && !no_gen && (desc->R >= 32 || c2_all || !one_stage) && fits_container(desc->in, h->in_eb) && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) &&
+    if (!desc->interp && !h->wide && !no_c2 && !no_gen && (desc->R >= 32 || c2_all || !one_stage) && (in_bytes || fits_container(desc->in, h->in_eb)) && !(desc->flags & ACDSP_FLAG_FORCE_GENERIC) &&
         cic2_factor(h->in_eb, desc->R, h->me, desc->N, &h->c2_R1, &h->c2_R2, &h->c2_wu)) {
       cic2_stage1_taps(h->c2_R1, desc->N, &h->c2_taps);
       h->c2_ok = fir_gen_plan(h->c2_taps.data(), (int)h->c2_taps.size(), h->c2_R1, 15, &probe, &fr) &&
@@ -147,6 +158,25 @@ int32_t acdsp_cic_clone(acdsp_cic_t h, acdsp_cic_t *out) {
 }
 
 int32_t acdsp_cic_path(acdsp_cic_t h) { return h ? h->last_path : -1; }
+
+int32_t acdsp_cic_in_elem_bytes(acdsp_cic_t h) { return h ? h->in_eb : -1; }
+
+int32_t acdsp_cic_two_stage_rates(const acdsp_cic_desc_t *desc, int32_t *R1, int32_t *R2) {
+  if (!desc || !R1 || !R2) { return fail(ACDSP_EINVAL, "null argument"); }
+  *R1 = *R2 = 0;
+  int rc;
+  if ((rc = check_fmt(desc->in, "IN_TYPE")) || (rc = check_fmt(desc->out, "OUT_TYPE", 128))) { return rc; }
+  acdsp_fmt_t it;
+  if ((rc = cic_int_type(*desc, &it))) { return rc; }
+  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
+  if (in_bytes && (rc = cic_bytes_refusal(*desc))) { return rc; }
+  const int in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
+  if (desc->interp || it.W > 64 || desc->out.W > 64 || desc->N > kCicMaxN || desc->R > 256) { return ACDSP_OK; }
+  if ((desc->flags & ACDSP_FLAG_FORCE_GENERIC) || !(in_bytes || fits_container(desc->in, in_eb))) { return ACDSP_OK; }
+  int r1 = 0, r2 = 0, wu = 0;
+  if (cic2_factor(in_eb, desc->R, desc->M < 2 ? desc->M : 2, desc->N, &r1, &r2, &wu)) { *R1 = r1; *R2 = r2; }
+  return ACDSP_OK;
+}
 
 int32_t acdsp_cic_reset(acdsp_cic_t h) {
   if (!h) { return fail(ACDSP_EINVAL, "null handle"); }

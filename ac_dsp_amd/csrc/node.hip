@@ -348,6 +348,7 @@ int32_t acdsp_node_cic_create(const acdsp_cic_desc_t *desc, int32_t n_devices, c
     return r;
   });
   if (rc) { const std::string keep = acdsp_last_error(); free_node(h); return set_error(rc, keep.c_str()); }
+  h->in_eb = acdsp_cic_in_elem_bytes((acdsp_cic_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES
   *out = h;
   return ACDSP_OK;
 }
@@ -375,6 +376,7 @@ int32_t acdsp_node_cic_run(acdsp_node_t h, const void *const *d_in, int64_t in_s
 // ---- fused DDC ----
 int32_t acdsp_node_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t n_devices, const int32_t *devices, acdsp_node_t *out) {
   if (!cic || !fir) { return set_error(ACDSP_EINVAL, "node_ddc_create: null descriptor"); }
+  if (cic->flags & ACDSP_FLAG_IN_BYTES) { return set_error(ACDSP_EUNSUPPORTED, "node_ddc_create: ACDSP_FLAG_IN_BYTES on the cascade's CIC decimator (the cascade kernel reads int16 rows)"); }
   acdsp_node *h = nullptr;
   int rc = make_node(kNodeDdc, cic->n_channels, n_devices, devices, &h);
   if (rc) { return rc; }

@@ -22,7 +22,7 @@ def _np_dtype_for(fmt):
 
 
 def _np_in_dtype(fmt, in_bytes):
-    """numpy dtype of FIR input rows: 1-byte containers under in_bytes (ACDSP_FLAG_IN_BYTES)"""
+    """numpy dtype of FIR / CIC input rows: 1-byte containers under in_bytes (ACDSP_FLAG_IN_BYTES)"""
     if in_bytes:
         return np.int8 if fmt.S else np.uint8
     return _np_dtype_for(fmt)
@@ -303,10 +303,13 @@ class Fir:
 class Cic:
     """n_channels independent ac_cic_dec_full (interp=False) / ac_cic_intr_full (interp=True) objects."""
 
-    def __init__(self, interp, R, M, N, fin, fout, n_channels=1, device=0, force_generic=False):
+    def __init__(self, interp, R, M, N, fin, fout, n_channels=1, device=0, force_generic=False, in_bytes=False):
+        """in_bytes: decimator on an IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
         self.interp, self.R, self.M, self.N = bool(interp), R, M, N
         self.fin, self.fout, self.n_channels, self.device = fin, fout, n_channels, device
-        self._d = CicDesc(int(self.interp), R, M, N, n_channels, fin, fout, device, _lib.FLAG_FORCE_GENERIC if force_generic else 0)
+        self.in_bytes = bool(in_bytes)
+        self._d = CicDesc(int(self.interp), R, M, N, n_channels, fin, fout, device,
+                          (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0))
         self._h = C.c_void_p()
         check(lib.acdsp_cic_create(C.byref(self._d), C.byref(self._h)))
 
@@ -315,6 +318,21 @@ class Cic:
         it = Fmt()
         check(lib.acdsp_cic_int_type(C.byref(self._d), C.byref(it)))
         return it
+
+    @property
+    def in_dtype(self):
+        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
+        if self.in_bytes:
+            return torch.int8 if self.fin.S else torch.uint8
+        return torch_dtype_for(self.fin)
+
+    @property
+    def two_stage_rates(self):
+        """(R1, R2) of the two-stage kernel if the handle takes it, (0, 0) where no compiled stage-1 rate serves the descriptor
+        (acdsp_cic_two_stage_rates: host only)"""
+        r1, r2 = C.c_int32(), C.c_int32()
+        check(lib.acdsp_cic_two_stage_rates(C.byref(self._d), C.byref(r1), C.byref(r2)))
+        return r1.value, r2.value
 
     def out_count(self, n_in):
         return lib.acdsp_cic_out_count(self._h, n_in)
@@ -325,7 +343,7 @@ class Cic:
 
     def run(self, x, out=None):
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_channels and x.stride(1) == 1
-        assert x.dtype == torch_dtype_for(self.fin), (x.dtype, self.fin)
+        assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         n_in = x.shape[1]
         no = self.out_count(n_in)
         if out is None:
@@ -339,7 +357,7 @@ class Cic:
         return out[:, :n_out.value]
 
     def run_host(self, x):
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_dtype_for(self.fin))
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_in_dtype(self.fin, self.in_bytes))
         no = self.out_count(x.shape[1])
         y = _alloc_out_host(self.fout, self.n_channels, max(no, 1))
         n_out = C.c_int64()
@@ -806,9 +824,10 @@ class NodeFir(_Node):
 class NodeCic(_Node):
     """A Cic bank sharded over `devices` (acdsp_node_cic_*)."""
 
-    def __init__(self, interp, R, M, N, fin, fout, n_channels, devices):
+    def __init__(self, interp, R, M, N, fin, fout, n_channels, devices, in_bytes=False):
         self.fin, self.fout, self.n_channels = fin, fout, n_channels
-        d = CicDesc(int(bool(interp)), R, M, N, n_channels, fin, fout, 0, 0)
+        self.in_bytes = bool(in_bytes)
+        d = CicDesc(int(bool(interp)), R, M, N, n_channels, fin, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
         self._h = C.c_void_p()
         check(lib.acdsp_node_cic_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -822,7 +841,7 @@ class NodeCic(_Node):
         if outs is None:
             per64 = max(1, 64 // lib.acdsp_elem_bytes(self.fout.W))
             outs = self.alloc(self.fout, (max(no, 1) + per64 - 1) // per64 * per64)
-        pin, sin = self._ptrs(xs, self.fin)
+        pin, sin = self._ptrs(xs, self.fin, (torch.int8 if self.fin.S else torch.uint8) if self.in_bytes else None)
         pout, sout = self._ptrs(outs, self.fout)
         n_out = C.c_int64()
         check(lib.acdsp_node_cic_run(self._h, pin, sin, n_in, pout, sout, C.byref(n_out)))

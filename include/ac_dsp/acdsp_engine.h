@@ -128,7 +128,8 @@ template <class T> struct container_io<T, true> {
 inline void pack(const std::vector<int64_t> &src, int eb, std::vector<unsigned char> &dst) {
   dst.resize(src.size() * (size_t)eb);
   for (size_t i = 0; i < src.size(); i++) {
-    if (eb == 2) { int16_t t = (int16_t)src[i]; memcpy(&dst[i * 2], &t, 2); }
+    if (eb == 1) { dst[i] = (unsigned char)src[i]; }   // ACDSP_FLAG_IN_BYTES
+    else if (eb == 2) { int16_t t = (int16_t)src[i]; memcpy(&dst[i * 2], &t, 2); }
     else if (eb == 4) { int32_t t = (int32_t)src[i]; memcpy(&dst[i * 4], &t, 4); }
     else { memcpy(&dst[i * 8], &src[i], 8); }
   }
@@ -382,24 +383,31 @@ private:
 template <class IN_TYPE, class OUT_TYPE>
 class cic_engine {
 public:
-  cic_engine(bool interp, unsigned R, unsigned M, unsigned N, int n_channels = 1, int device = -1)
-      : h_(0), interp_(interp), R_(R), M_(M), N_(N), n_ch_(n_channels), device_(device < 0 ? default_device() : device) {}
+  // flags: ACDSP_FLAG_* of acdsp_cic_desc_t (ACDSP_FLAG_IN_BYTES on a decimator: in_bytes() == 1, rows of 1-byte containers)
+  cic_engine(bool interp, unsigned R, unsigned M, unsigned N, int n_channels = 1, int device = -1, int flags = 0)
+      : h_(0), interp_(interp), R_(R), M_(M), N_(N), n_ch_(n_channels), device_(device < 0 ? default_device() : device), flags_(flags) {}
   ~cic_engine() { if (h_) { acdsp_cic_destroy(h_); } }
-  cic_engine(const cic_engine &o) : h_(0), interp_(o.interp_), R_(o.R_), M_(o.M_), N_(o.N_), n_ch_(o.n_ch_), device_(o.device_) {
+  cic_engine(const cic_engine &o) : h_(0), interp_(o.interp_), R_(o.R_), M_(o.M_), N_(o.N_), n_ch_(o.n_ch_), device_(o.device_), flags_(o.flags_) {
     if (o.h_) { check(acdsp_cic_clone(o.h_, &h_), "acdsp_cic_clone"); }
   }
   cic_engine &operator=(const cic_engine &o) {
     if (this != &o) {
       if (h_) { acdsp_cic_destroy(h_); h_ = 0; }
-      interp_ = o.interp_; R_ = o.R_; M_ = o.M_; N_ = o.N_; n_ch_ = o.n_ch_; device_ = o.device_;
+      interp_ = o.interp_; R_ = o.R_; M_ = o.M_; N_ = o.N_; n_ch_ = o.n_ch_; device_ = o.device_; flags_ = o.flags_;
       if (o.h_) { check(acdsp_cic_clone(o.h_, &h_), "acdsp_cic_clone"); }
     }
     return *this;
   }
 
-  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int in_bytes() const { return (flags_ & ACDSP_FLAG_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
   int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
   acdsp_cic_t handle() { ensure(); return h_; }
+  // checkpoint blobs of include/acdsp.h (input history and phase of every channel)
+  std::vector<unsigned char> state() { ensure(); return state_of(h_, acdsp_cic_state_size, acdsp_cic_state_get); }
+  void set_state(const std::vector<unsigned char> &blob) {
+    ensure();
+    check(acdsp_cic_state_set(h_, blob.data(), (uint64_t)blob.size()), "acdsp_cic_state_set");
+  }
   int64_t out_count(int64_t n_in) { ensure(); return acdsp_cic_out_count(h_, n_in); }
 
   void run_device(const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride, int64_t *n_out, void *stream = 0) {
@@ -427,13 +435,13 @@ private:
     if (h_) { return; }
     acdsp_cic_desc_t d;
     d.interp = interp_ ? 1 : 0; d.R = (int32_t)R_; d.M = (int32_t)M_; d.N = (int32_t)N_; d.n_channels = n_ch_;
-    d.in = fmt_of<IN_TYPE>(); d.out = fmt_of<OUT_TYPE>(); d.device = device_; d.flags = 0;
+    d.in = fmt_of<IN_TYPE>(); d.out = fmt_of<OUT_TYPE>(); d.device = device_; d.flags = flags_;
     check(acdsp_cic_create(&d, &h_), "acdsp_cic_create");
   }
   acdsp_cic_t h_;
   bool interp_;
   unsigned R_, M_, N_;
-  int n_ch_, device_;
+  int n_ch_, device_, flags_;
 };
 
 // DDC cascade on device-resident streams: n_channels x { ac_cic_dec_full<IN, INT, R, M, N> -> FIR<INT, OUT, COEFF, ACC> }

@@ -61,10 +61,12 @@ enum {
 
 /* flags */
 #define ACDSP_FLAG_FORCE_GENERIC 1 /* never pick the MFMA / fast kernels (parity tests) */
-/* acdsp_fir_desc_t::flags only.  IN_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE containers: the caller's input rows, the handle's
- * history and the FIR state blob hold int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() == 1; acdsp_elem_bytes() is not asked for the
- * input).  in_stride stays in elements; the output containers are unchanged.  W > 8: ACDSP_EINVAL; ACC_TYPE / OUT_TYPE wider than 64 bits and
- * the FIR of acdsp_ddc_create: ACDSP_EUNSUPPORTED.  INTEGRATION.md "Byte samples". */
+/* acdsp_fir_desc_t::flags, and acdsp_cic_desc_t::flags of a decimator (interp == 0).  IN_TYPE has W <= 8 (signed or unsigned) and travels in
+ * 1-BYTE containers: the caller's input rows, the handle's history and the FIR / CIC state blob hold int8_t / uint8_t raw words
+ * (acdsp_fir_in_elem_bytes() / acdsp_cic_in_elem_bytes() == 1; acdsp_elem_bytes() is not asked for the input).  in_stride stays in elements;
+ * the output containers are unchanged.  W > 8: ACDSP_EINVAL; ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its
+ * input stream is the thin one) and either stage of acdsp_ddc_create / acdsp_node_ddc_create: ACDSP_EUNSUPPORTED, all before any device
+ * use.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_IN_BYTES 2
 
 /* which kernel family a FIR handle resolved to (acdsp_fir_path) */
@@ -279,7 +281,18 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
 int32_t acdsp_cic_run_host(acdsp_cic_t h, const void *h_in, int64_t n_in, void *h_out, int64_t out_cap, int64_t *n_out);
 int32_t acdsp_cic_reset(acdsp_cic_t h);
 int32_t acdsp_cic_path(acdsp_cic_t h);         /* last run(): 0 recurrence kernel, 3 FIR-identity MFMA kernel (ACDSP_PATH_MFMA_GEN), 6 two-stage kernel (ACDSP_PATH_CIC_2STAGE; decimation
-                                                  factors from 32 on that a compiled stage-1 rate divides -- others keep the recurrence kernel), 4 wide */
+                                                  factors from 32 on that a compiled stage-1 rate divides -- others keep the recurrence kernel), 4 wide.  Under ACDSP_FLAG_IN_BYTES: 6 for every
+                                                  rate a byte stage-1 rate (16, 8, 4) divides, rates below 32 included, else 0; never 3 */
+/* bytes of one INPUT container of the handle: 1 under ACDSP_FLAG_IN_BYTES, else acdsp_elem_bytes(in.W).  A flagged handle's path is 6 or 0,
+ * never 3; its state blobs carry elem_bytes = 1 and move between flagged handles of one descriptor only (two-stage or
+ * ACDSP_FLAG_FORCE_GENERIC alike, under the history-length rule of acdsp_cic_state_set); blobs of unflagged handles are ACDSP_EINVAL there,
+ * and the other way round */
+int32_t acdsp_cic_in_elem_bytes(acdsp_cic_t h);
+/* Host only, no device: the rates R = R1 * R2 of the two-stage kernel if the handle takes it (ACDSP_PATH_CIC_2STAGE: slot-aligned rows, calls
+ * of at least a chunk; the A/B environment switches are not its business), flagged with ACDSP_FLAG_IN_BYTES or not.  R1 = R2 = 0 where no
+ * compiled stage-1 rate of the descriptor's input container serves it, for interpolators, types wider than 64 bits and
+ * ACDSP_FLAG_FORCE_GENERIC.  Fails as acdsp_cic_create does on a descriptor that is invalid in itself. */
+int32_t acdsp_cic_two_stage_rates(const acdsp_cic_desc_t *desc, int32_t *R1, int32_t *R2);
 int32_t acdsp_cic_last_kernel_ms(acdsp_cic_t h, float *ms);
 int32_t acdsp_cic_kernel_stats(acdsp_cic_t h, int32_t last_k, float *avg_ms, float *min_ms);
 
