@@ -108,7 +108,7 @@ hipError_t launch_cic2(const CicParams &p, const FirGenPlan &pl, const uint32_t 
   a.ring_delta = (int32_t)(((w0slot % ls) + ls) % ls);
   a.wu = wu;
   a.rcp2 = (uint32_t)((0x100000000ull + R2 - 1) / R2);
-  // pairwise recombination of the plane accumulators (fir_gen.hip: set_pairwise)
+  // pairwise recombination of the plane accumulators (fir_gen.hip: gen_fill_args)
   {
     const int px = p.in_eb;
     int64_t bw[16] = {0};

@@ -13,7 +13,7 @@
 // i.e.  H(z) = [z^-(N-1) boxcar(R1)^N](z) * [boxcar(R2 M')^N](z^R1): a CIC of rate R1 (M = 1) followed by a CIC of rate R2 (M = M')
 // running on the first one's outputs (noble identity).  So:
 //   stage 1  u[m] = (h1 * x)[first + m R1],  h1 = z^-(N-1) boxcar(R1)^N  -- the ring kernel's strided-Toeplitz form on the matrix cores
-//            (fir_gen.hip: byte planes in an LDS ring of two steps, every input byte loaded once, 256 u per step);
+//            (fir_gen_kernels.hpp: byte planes in an LDS ring of two steps, every input byte loaded once, 256 u per step);
 //   stage 2  y[j] = sum_i (-1)^i C(N, i) s_N[(j - i M') R2],  s_N = the N-fold running sum of u  -- N integrators at the u rate, the combs
 //            at the output rate, all mod 2^64.  The N integrators of a step are N cascaded prefix sums over the wave: the step's 256 u
 //            pass through a 2 KB LDS tile into time order (four consecutive u per lane), each level is three in-lane adds, one
@@ -33,12 +33,9 @@
 
 #include "cic_kernels.hpp"
 #include "fir_kernels.hpp"
+#include "mfma_planes.hpp"
 
 namespace acdsp {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef long v2l __attribute__((ext_vector_type(2)));
 
 constexpr int kCic2MaxN = 6;       // (R M)^N < 2^31 with R >= 32 leaves N <= 6
 constexpr int kCic2Zero = 16;      // zero entries in front of the decimated ring: the comb line of a chunk starts empty (N M' <= 12)
@@ -87,15 +84,8 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
   return __builtin_bit_cast(uint64_t, s);
 }
 
-__device__ __forceinline__ unsigned c2_gather4(unsigned d0, unsigned d1, unsigned d2, unsigned d3, int p) {
-  const unsigned sel = 0x0c0c0400u + 0x0101u * (unsigned)p;
-  const unsigned lo = __builtin_amdgcn_perm(d1, d0, sel);
-  const unsigned hi = __builtin_amdgcn_perm(d3, d2, sel);
-  return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-}
-
 // One wave = one channel x a chunk of `nst` steps (the first `wu` of them warm-up); a step = 256 stage-1 outputs = 256 R1 inputs.
-// Ring geometry, slot map and load / staging order are fir_gen_ring_kernel's (fir_gen.hip), rolled into a loop over batches of G steps
+// Ring geometry (RingGeom, mfma_planes.hpp), slot map and load / staging order are fir_gen_ring_kernel's (fir_gen_kernels.hpp), rolled into a loop over batches of G steps
 // (load groups alternate between two register sets, each fetched two groups ahead; a group is one step, or two where a step advances
 // half a 1 KB load: M = 2).  Stage 2 runs once per batch: the G x 256 u of a batch wait in an LDS tile and come back in time order, 4 G
 // consecutive u per lane, so a prefix-sum level costs 8 G - 1 adds and ONE wave scan per G steps.
@@ -105,13 +95,8 @@ __device__ __forceinline__ unsigned c2_gather4(unsigned d0, unsigned d1, unsigne
 template <typename TIN, int PCT, int NBT, int R1, int G, int NN>
 __global__ void __launch_bounds__(64, 2) cic2_kernel(Cic2Args a, const v4i *__restrict__ frag) {
   constexpr int S = (int)sizeof(TIN), PX = S;
-  constexpr int LS = 8 / S;
-  constexpr int ADV = 16 * R1, NSL = 15 * R1 + 4 * NBT;
-  constexpr int H = (LS - 1 + NSL - ADV + LS - 1) / LS * LS;
-  constexpr int M = (R1 * S) % 4 == 0 ? 1 : 2;
-  constexpr int NLD = R1 * S * M / 4;
-  constexpr int PPB = 16 / S;
-  constexpr int SPK = 64 / S;
+  typedef RingGeom<S, R1, NBT> RG;
+  constexpr int ADV = RG::ADV, H = RG::H, M = RG::M, NLD = RG::NLD, PPB = RG::PPB, SPK = RG::SPK;
   static_assert(S == 1 || S == 2 || S == 4, "1- (ACDSP_FLAG_IN_BYTES), 2- and 4-byte samples");
   static_assert(G % (2 * M) == 0 && G <= 4, "a batch holds whole pairs of load groups");
   constexpr bool HOLES = (R1 % 2 == 0 && SPK % R1 == 0);
@@ -190,20 +175,9 @@ __global__ void __launch_bounds__(64, 2) cic2_kernel(Cic2Args a, const v4i *__re
       // non-zero for nothing else (launch_cic2), so it doubles as the flag and Cic2Args keeps its layout
       const int fx = a.corr != 0 ? (int)0x80808080u : 0;
       *(v4i *)(lds + off) = v ^ (v4i){fx, fx, fx, fx};
-      return;
-    }
+    } else {
 #pragma unroll
-    for (int pp = 0; pp < PX; pp++) {
-      if constexpr (S == 2) {
-        const unsigned sel = pp == 0 ? 0x06040200u : 0x07050301u;
-        unsigned lo = __builtin_amdgcn_perm((unsigned)v.y, (unsigned)v.x, sel), hi = __builtin_amdgcn_perm((unsigned)v.w, (unsigned)v.z, sel);
-        if (pp < PX - 1) { lo ^= 0x80808080u; hi ^= 0x80808080u; }
-        *(v2u *)(lds + pp * PLANE + off) = (v2u){lo, hi};
-      } else {
-        unsigned w = c2_gather4((unsigned)v.x, (unsigned)v.y, (unsigned)v.z, (unsigned)v.w, pp);
-        if (pp < PX - 1) { w ^= 0x80808080u; }
-        *(unsigned *)(lds + pp * PLANE + off) = w;
-      }
+      for (int pp = 0; pp < PX; pp++) { put_piece_plane<S, PX>(v, pp, lds, PLANE, off); }
     }
   };
 

@@ -461,7 +461,7 @@ struct acdsp_fir {
   DevBuf d_gfrag;               // fragments of the generalised (wide-input) MFMA kernel
   FirGenPlan gplan;
   bool gen_ok = false;
-  // class B on the matrix cores (fir_gen.hip, LZ ring shapes): gplan / d_gfrag hold the plan of the effective taps, lzp the residue table
+  // class B on the matrix cores (fir_gen_ring.hip, LZ ring shapes): gplan / d_gfrag hold the plan of the effective taps, lzp the residue table
   bool lz_ok = false;
   FirLossyPlan lzp;
   DevBuf d_lzcl;

@@ -105,7 +105,16 @@ struct LongGrid {
 };
 LongGrid long_grid(int64_t n_steps, int rows, int64_t min_steps);
 
-// Generalised exact FIR on the matrix cores (fir_gen.hip): wide inputs / coefficients, decimation.
+// Host: pops the lowest balanced base-256 digit (-128 .. 127) of v, v = digit + 256 v' -- the signed bytes the int8 matrix cores multiply.
+// What a rest after the last digit means stays with the caller.
+inline int pop_balanced_digit(__int128 &v) {
+  int lo = (int)(((v % 256) + 256) % 256);
+  if (lo >= 128) { lo -= 256; }
+  v = (v - lo) / 256;
+  return lo;
+}
+
+// Generalised exact FIR on the matrix cores (fir_gen.hip, fir_gen_ring.hip; kernels in fir_gen_kernels.hpp): wide inputs / coefficients, decimation.
 // FirParams::ftype values of the ac_fir_reg_share cores (ascending MAC order, anti-symmetric folds:
 // reference ac_fir_reg_share.h:136-260); the const/load/prog cores use the public ACDSP_* values.
 enum { kRsShiftReg = 16, kRsFoldEven = 17, kRsFoldEvenAnti = 18, kRsFoldOdd = 19, kRsFoldOddAnti = 20 };
@@ -123,7 +132,7 @@ bool fir_gen_plan(const int64_t *h, int n_taps, int R, int first_mod16, FirGenPl
 bool fir_gen_window(int n_taps, int R, int first_mod16, int *off, int *nb);
 // out_mode 0: FIR class A epilogue (p.lossless_shift, p.acc wrap, requant to p.out);
 // out_mode 1: CIC epilogue (wrap to w_int, requant from p.in.F to p.out).  p.n = inputs, p.hist holds >= off samples.
-// Class B on the ring kernel (lossy accumulator, AC_TRN / AC_RND into AC_WRAP; fir_gen.hip: LZ instantiations).  pl / d_frag are the
+// Class B on the ring kernel (lossy accumulator, AC_TRN / AC_RND into AC_WRAP; fir_gen_ring.hip: LZ instantiations).  pl / d_frag are the
 // plan of the EFFECTIVE tap vector (the exact sum), this struct the per-tap residues.
 struct FirLossyPlan {
   int32_t s;                           // F_in + F_c - F_acc, 1 .. 15
@@ -147,7 +156,7 @@ bool fir_gen_lossy_shape_ok(const FirParams &p, const FirGenPlan &pl, int acc_bi
 hipError_t launch_fir_gen(const FirParams &p, const FirGenPlan &pl, const uint32_t *d_frag, int out_mode, int w_int,
                           int64_t first, int64_t n_out, hipStream_t s, const FirLossyPlan *lz = nullptr, int64_t *covered = nullptr);
 
-// Fused decimator -> FIR cascade on the matrix cores (fir_gen.hip).  pa = stage A as for launch_fir_gen with
+// Fused decimator -> FIR cascade on the matrix cores (fir_gen_cascade.hip).  pa = stage A as for launch_fir_gen with
 // out_mode 1 (history of >= 256*R + off + 16 samples), pb = stage B formats + output buffer (int32 containers).
 // hipErrorNotSupported: shapes outside the compiled ones (run the two kernels instead).
 // A second stream of a handle (round 5) for the small kernels of a call that neither feed nor follow its main kernel -- the head / tail of an

@@ -26,10 +26,8 @@ bool fir_up_plan(const int64_t *E, int L, int nt, int px, FirUpPlan *pl, std::ve
   for (int i = 0; i < L * nt; i++) {
     __int128 v = E[i];
     for (int q = 0; q < kUpMaxPC; q++) {
-      int lo = (int)(((v % 256) + 256) % 256);
-      if (lo >= 128) { lo -= 256; }
+      const int lo = pop_balanced_digit(v);
       dig[q][(size_t)i] = (int8_t)lo;
-      v = (v - lo) / 256;
       if (lo != 0 && q + 1 > pc) { pc = q + 1; }
     }
     if (v != 0) { return false; }

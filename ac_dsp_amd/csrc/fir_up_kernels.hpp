@@ -21,7 +21,7 @@
 //     X_c[kappa] = x[n0 + SPC (c + 1) - 32 NB + kappa],   kappa in [0, 32 NB)
 // (NB = 1 or 2 K blocks; only SPC + NT - 1 of the 32 NB window positions carry taps -- the matrix pipe has slack to burn
 // here, HBM write bandwidth does not).  The Toeplitz fragments A are the same for every column group and stay in
-// registers.  Operands are split into byte planes exactly as in fir_gen.hip (x: 2 or 4 planes, lower ones re-biased to
+// registers.  Operands are split into byte planes exactly as in fir_gen_kernels.hpp (put_piece_plane of mfma_planes.hpp; x: 2 or 4 planes, lower ones re-biased to
 // signed; taps: balanced base-256 digits), products of equal weight share an int32 accumulator, the 64-bit recombination
 // runs once per output.  The re-bias correction depends on the phase: 128 * sum_k E_j[k] * sum_{p < PX-1} 256^p, a small
 // per-lane table (the rows of a lane repeat with period L <= 32).
@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "fir_kernels.hpp"
+#include "mfma_planes.hpp"
 
 // Load policy of the 512 new samples of a step (read exactly once).  Round 4 A/B (profiles/r4_ab_up_nt.txt, pipelined form: non-temporal
 // loads +2.3 % on the ac_cic_intr_full row, +-0 on the ac_poly_intr row; profiles/r4_up_oneshot.txt, one-shot form: +2 - 3 %) -- the
@@ -54,19 +55,11 @@
 
 namespace acdsp {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 namespace {
 
 constexpr int kUpMaxPC = 3;
-
-__device__ inline unsigned up_gather4(unsigned d0, unsigned d1, unsigned d2, unsigned d3, int p) {
-  const unsigned sel = 0x0c0c0400u + 0x0101u * (unsigned)p;
-  const unsigned lo = __builtin_amdgcn_perm(d1, d0, sel);
-  const unsigned hi = __builtin_amdgcn_perm(d3, d2, sel);
-  return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-}
 
 // index into the per-lane phase table of accumulator register r (row i = (r & 3) + 8 (r >> 2) + 4 h, phase i % L); factors that do not
 // divide 32 have no period inside the 16 registers: one entry per register
@@ -182,28 +175,15 @@ __global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0) ? 2
     }
     preh[S] = ((const v4i *)(src - HP))[hl];
   };
-  // byte plane pp of the SPL samples in one 16-byte register set -> SPL bytes at `dst`
-  auto put = [&](const v4i &v, int pp, unsigned char *dst) {
-    if constexpr (sizeof(TIN) == 2) {
-      const unsigned sel = pp == 0 ? 0x06040200u : 0x07050301u;
-      unsigned lo = __builtin_amdgcn_perm((unsigned)v.y, (unsigned)v.x, sel), hi = __builtin_amdgcn_perm((unsigned)v.w, (unsigned)v.z, sel);
-      if (pp < PX - 1) { lo ^= 0x80808080u; hi ^= 0x80808080u; }
-      typedef unsigned v2u __attribute__((ext_vector_type(2)));
-      *(v2u *)dst = (v2u){lo, hi};
-    } else {
-      unsigned w = up_gather4((unsigned)v.x, (unsigned)v.y, (unsigned)v.z, (unsigned)v.w, pp);
-      if (pp < PX - 1) { w ^= 0x80808080u; }
-      *(unsigned *)dst = w;
-    }
-  };
+  // byte plane pp of the SPL samples in one 16-byte register set -> SPL bytes (put_piece_plane, mfma_planes.hpp)
   auto stage = [&](auto set_c) {
     constexpr int S = decltype(set_c)::value;
 #pragma unroll
     for (int pp = 0; pp < PX; pp++) {
       unsigned char *pl = lds + pp * PLB;
 #pragma unroll
-      for (int q = 0; q < NLD; q++) { put(pre[S][q], pp, pl + HP + (64 * q + lane) * SPL); }
-      put(preh[S], pp, lane < NHL ? pl + lane * SPL : sink + lane * 16);   // ... and dump it into a private sink (branch-free)
+      for (int q = 0; q < NLD; q++) { put_piece_plane<(int)sizeof(TIN), PX>(pre[S][q], pp, pl + HP + (64 * q + lane) * SPL); }
+      put_piece_plane<(int)sizeof(TIN), PX>(preh[S], pp, lane < NHL ? pl + lane * SPL : sink + lane * 16);   // ... and dump it into a private sink (branch-free)
     }
   };
 
@@ -365,12 +345,10 @@ __global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0) ? 2
         if (EPI == 1 || EPI == 3) {
           if (OEB == 4) { *(v4i *)dst = (v4i){o32[0], o32[1], o32[2], o32[3]}; }
           else {
-            typedef unsigned v2u __attribute__((ext_vector_type(2)));
             *(v2u *)dst = (v2u){__builtin_amdgcn_perm((unsigned)o32[1], (unsigned)o32[0], 0x05040100u),
                                 __builtin_amdgcn_perm((unsigned)o32[3], (unsigned)o32[2], 0x05040100u)};
           }
         } else if (OEB == 8) {
-          typedef long v2l __attribute__((ext_vector_type(2)));
           *(v2l *)dst = (v2l){o[0], o[1]};
           *(v2l *)(dst + 16) = (v2l){o[2], o[3]};
         } else if (OEB == 4) {

@@ -154,7 +154,7 @@ def test_no_kernel_uses_scratch():
 
 
 def test_every_kernel_is_compiled_once():
-    """The kernel templates of fir_mfma_kernels.hpp, fir_up_kernels.hpp and cic2_kernels.hpp are instantiated by whichever translation unit
+    """The kernel templates of fir_mfma_kernels.hpp, fir_up_kernels.hpp, cic2_kernels.hpp and fir_gen_kernels.hpp are instantiated by whichever translation unit
     names them: a shape named in two units would compile twice (same work, a second copy in the library) without any error.  No kernel
     name may occur in more than one code object of the shipped library."""
     import collections

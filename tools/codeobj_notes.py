@@ -108,6 +108,11 @@ def instruction_streams(path):
                 cur = out.setdefault(line[1:-2], [])
             elif cur is not None and line.startswith(("\t", " ")):
                 cur.append(line.split("//")[0].strip())   # (the comment holds the address and the encoding)
+    for insns in out.values():
+        # objdump's mark for a run of zeros, "...": behind a function's last instruction it is the padding up to whatever stands next in
+        # the section, not part of the function; anywhere else it stays and is compared
+        while insns and insns[-1] == "...":
+            insns.pop()
     return out
 
 
