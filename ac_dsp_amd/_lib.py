@@ -14,7 +14,7 @@ KINDS = {"const": 0, "load": 1, "prog": 2, "reg_share": 3}
 PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 5: "mfma_lossy", 8: "mfma_long", 9: "mfma_s8"}   # (6 = ACDSP_PATH_CIC_2STAGE: Cic.path only)
 KCLASSES = {**PATHS, 6: "lossy16", 7: "satacc16"}
 FLAG_FORCE_GENERIC = 1
-FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator): IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
+FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator), PolyDec / NodePolyDec: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
 
 
 class AcdspError(RuntimeError):
@@ -183,6 +183,8 @@ SYMBOLS = {
     "acdsp_polydec_run_host": (_i32, [_vp, _vp, _i64, _vp]),
     "acdsp_polydec_reset": (_i32, [_vp]),
     "acdsp_polydec_path": (_i32, [_vp]),
+    "acdsp_polydec_in_elem_bytes": (_i32, [_vp]),
+    "acdsp_polydec_ring_shape": (_i32, [_vp]),
     "acdsp_polydec_set_scratch_cap": (_i32, [_vp, C.c_uint64]),
     "acdsp_polydec_long_geometry": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(C.c_uint64)]),
     "acdsp_polyintr_create": (_i32, [C.POINTER(PolyIntrDesc), C.POINTER(_vp)]),

@@ -23,6 +23,7 @@ struct acdsp_polydec {
   uint64_t scratch_cap = (uint64_t)128 << 20;
   DevBuf d_lfrag, d_lcorr, d_scratch;
   int last_path = ACDSP_PATH_GENERIC;
+  int32_t last_ring = 0;   // ring-shape id of the last run(), 0 when no ring row ran
   Staging st;
 };
 
@@ -44,8 +45,9 @@ const char *polydec_long_refusal(const acdsp_polydec_desc_t &d) {
 // scratch of a long handle under `cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a
 // failure leaves cap, geometry and scratch as they were
 int polydec_size_scratch(acdsp_polydec *h, uint64_t cap) {
-  // phase rows of int16: df * 2 bytes per slab output, in front of them the reach of 32 (nb - 1) samples
-  const LongGeom geo = long_geometry((uint64_t)h->d.df * 2, 32 * (uint64_t)(long_blocks(h->d.n_taps) - 1), h->d.n_channels, cap);
+  // phase rows of IN containers (int16, or bytes under ACDSP_FLAG_IN_BYTES): df * in_eb bytes per slab output, in front of them the reach of
+  // 32 (nb - 1) samples
+  const LongGeom geo = long_geometry((uint64_t)h->d.df * (uint64_t)h->in_eb, 32 * (uint64_t)(long_blocks(h->d.n_taps) - 1), h->d.n_channels, cap);
   DevBuf fresh;
   const int rc = fresh.alloc(geo.bytes);
   if (rc) { return rc; }
@@ -71,6 +73,8 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
       (rc = check_fmt(desc->out, "OUT_TYPE"))) {
     return rc;
   }
+  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
+  if (in_bytes && desc->in.W > 8) { return fail(ACDSP_EINVAL, "poly_dec: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", desc->in.W); }
   const int fi = desc->in.W - desc->in.I, fc = desc->coeff.W - desc->coeff.I, fa = desc->acc.W - desc->acc.I;
   const int f = fi + fc > fa ? fi + fc : fa;
   if (desc->in.W + desc->coeff.W + 2 + (f - fi - fc) > 125 || desc->acc.W + (f - fa) > 125) {
@@ -85,7 +89,7 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_polydec> h(new acdsp_polydec());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
-  h->in_eb = elem_bytes(desc->in.W);
+  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
   h->out_eb = elem_bytes(desc->out.W);
   h->hl = round_up(desc->n_taps * desc->df + 15, 32);
   h->lossless_shape = fa >= fi + fc && fa - fi - fc < 64;
@@ -98,7 +102,9 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
   int g_off, g_nb;
   h->long_shape = !long_why && !fir_gen_window(desc->n_taps * desc->df, desc->df, (desc->df - 1) % 16, &g_off, &g_nb);
   if (h->long_shape) {
-    h->in_flip = !desc->in.S && desc->in.W == 16;   // unsigned 16-bit samples: read as x - 32768, 32768 * sum(c) rides in the correction constant
+    // unsigned 16-bit samples: read as x - 32768, 32768 * sum(c) rides in the correction constant; unsigned bytes (ACDSP_FLAG_IN_BYTES,
+    // polydec_s8.hip): read as x - 128, 128 * sum(c)
+    h->in_flip = !desc->in.S && (in_bytes || desc->in.W == 16);
     if ((rc = h->d_lfrag.alloc((size_t)2 * desc->df * long_blocks(desc->n_taps) * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc(sizeof(int64_t))) ||
         (rc = polydec_size_scratch(h.get(), h->scratch_cap))) {
       return rc;
@@ -138,12 +144,15 @@ int32_t acdsp_polydec_set_coeffs(acdsp_polydec_t h, const int64_t *coeffs) {
     h->lossless = h->lossless_shape && (d.acc.O == ACDSP_WRAP || sf);
   }
   static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
-  if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !no_gen && fits_container(d.in, h->in_eb)) {
+  const bool in_bytes = (d.flags & ACDSP_FLAG_IN_BYTES) != 0;   // (a byte container holds every IN_TYPE the flag admits, unsigned ones re-biased)
+  if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !no_gen && (in_bytes || fits_container(d.in, h->in_eb))) {
     // decimating FIR  y[g] = sum_k hh[k] x[g*DF + DF-1 - k],  hh[df + tp*DF] = c[tp + NTAPS*df]
     std::vector<int64_t> hh((size_t)n, 0);
     for (int df = 0; df < d.df; df++) { for (int tp = 0; tp < d.n_taps; tp++) { hh[df + tp * d.df] = coeffs[tp + d.n_taps * df]; } }
     std::vector<uint32_t> fr;
-    if (fir_gen_plan(hh.data(), n, d.df, (d.df - 1) % 16, &h->gplan, &fr)) {
+    // (unsigned bytes: the GenArgs kernels take the non-zero correction 128 * sum(c) as the sign of the re-bias -- a set whose sum is 0 mod 2^57
+    // keeps the exact-order kernel)
+    if (fir_gen_plan(hh.data(), n, d.df, (d.df - 1) % 16, &h->gplan, &fr) && !(in_bytes && !d.in.S && (uint64_t)h->gplan.sum_h * 128 == 0)) {
       if ((rc = h->d_gfrag.upload(fr.data(), fr.size() * sizeof(uint32_t)))) { return rc; }
       h->gen_ok = true;
     }
@@ -159,11 +168,10 @@ int32_t acdsp_polydec_set_coeffs(acdsp_polydec_t h, const int64_t *coeffs) {
         return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", n);
       }
     } else if (polydec_long_plan(coeffs, d.n_taps, d.df, &h->lplan, &fr)) {
-      if (h->in_flip) {
-        int64_t sc = 0;
-        for (int i = 0; i < n; i++) { sc += coeffs[i]; }
-        h->lplan.corr += 32768 * sc;
-      }
+      int64_t sc = 0;
+      for (int i = 0; i < n; i++) { sc += coeffs[i]; }
+      if (in_bytes) { h->lplan.corr = h->in_flip ? 128 * sc : 0; }   // one sample plane: no low plane to re-bias
+      else if (h->in_flip) { h->lplan.corr += 32768 * sc; }
       if ((rc = h->d_lfrag.upload(fr.data(), fr.size() * sizeof(uint32_t))) || (rc = h->d_lcorr.upload(&h->lplan.corr, sizeof(int64_t)))) { return rc; }
       h->long_ok = true;
     } else if (n > 2048) {
@@ -176,6 +184,8 @@ int32_t acdsp_polydec_set_coeffs(acdsp_polydec_t h, const int64_t *coeffs) {
 }
 
 int32_t acdsp_polydec_path(acdsp_polydec_t h) { return h ? h->last_path : -1; }
+int32_t acdsp_polydec_in_elem_bytes(acdsp_polydec_t h) { return h ? h->in_eb : -1; }
+int32_t acdsp_polydec_ring_shape(acdsp_polydec_t h) { return h ? h->last_ring : -1; }
 
 int32_t acdsp_polydec_set_scratch_cap(acdsp_polydec_t h, uint64_t bytes) {
   if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
@@ -217,13 +227,19 @@ int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride
   k.x = d_in; k.y = d_out; k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>();
   const bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && in_stride >= (n_in + 15) / 16 * 16;
   hipError_t e;
+  h->last_ring = 0;
   if (h->long_ok) {   // every call, whatever its length or alignment
-    h->last_path = ACDSP_PATH_MFMA_LONG;
     k.in_flip = h->in_flip;
-    e = launch_polydec_long(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_scratch.get(), n_out, s);
+    if (h->in_eb == 1) {
+      h->last_path = ACDSP_PATH_MFMA_S8;
+      e = launch_polydec_s8(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_scratch.get(), n_out, s);
+    } else {
+      h->last_path = ACDSP_PATH_MFMA_LONG;
+      e = launch_polydec_long(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_scratch.get(), n_out, s);
+    }
   } else if (h->gen_ok && aligned) {
     h->last_path = ACDSP_PATH_MFMA_GEN;
-    e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, d.df - 1, n_out, s);
+    e = launch_fir_gen(k, h->gplan, h->d_gfrag.get<uint32_t>(), 0, 0, d.df - 1, n_out, s, nullptr, nullptr, &h->last_ring);
   } else {
     h->last_path = ACDSP_PATH_GENERIC;
     e = launch_polydec_generic(k, d.n_taps, d.df, n_out, s);
@@ -272,11 +288,13 @@ int32_t acdsp_polydec_clone(acdsp_polydec_t h, acdsp_polydec_t *out) {
   }
   if ((rc = c->hist.copy_from(h->hist))) { return rc; }
   c->last_path = h->last_path;
+  c->last_ring = h->last_ring;
   *out = guard.release();
   return ACDSP_OK;
 }
 
-// State blob, kind 6: the newest `hl` input samples of every channel, oldest first, in IN containers (the reference's taps[NTAPS*DF]; acc and
+// State blob, kind 6: the newest `hl` input samples of every channel, oldest first, in IN containers (1-byte ones under ACDSP_FLAG_IN_BYTES:
+// elem_bytes 1, so a flagged blob and an unflagged handle refuse each other; the reference's taps[NTAPS*DF]; acc and
 // acc1[] are rebuilt by every group).  A call consumes whole groups of DF, so there is no phase to carry.
 static StateHdr polydec_state_hdr(const acdsp_polydec *h) {
   StateHdr s = state_hdr(6, (uint32_t)h->d.n_channels, (uint32_t)h->in_eb, (uint64_t)h->hl);

@@ -140,7 +140,9 @@ static hipError_t launch_px(int px, dim3 grid, size_t lds_bytes, hipStream_t s, 
   }
   // byte planes never exceed the container (launch_fir_gen checks px <= in_eb): only those instantiations exist
   if (px > (int)sizeof(TIN)) { return hipErrorInvalidValue; }
-  if constexpr (sizeof(TIN) == 2) {
+  if constexpr (sizeof(TIN) == 1) {   // byte samples (ACDSP_FLAG_IN_BYTES): one plane
+    switch (px) { ACDSP_GEN_CASE(1) default: return hipErrorInvalidValue; }
+  } else if constexpr (sizeof(TIN) == 2) {
     switch (px) { ACDSP_GEN_CASE(1) ACDSP_GEN_CASE(2) default: return hipErrorInvalidValue; }
   } else if constexpr (sizeof(TIN) == 4) {
     switch (px) { ACDSP_GEN_CASE(1) ACDSP_GEN_CASE(2) ACDSP_GEN_CASE(3) ACDSP_GEN_CASE(4) default: return hipErrorInvalidValue; }
@@ -281,7 +283,9 @@ static bool gen_fill_args(const FirParams &p, const FirGenPlan &pl, int out_mode
   a.ring_delta = 0;
   const int in_bits = p.in.W + (p.in.S ? 0 : 1);
   a.px = (in_bits + 7) / 8;
-  if (a.px > p.in_eb) { return false; }
+  const bool bytes = p.in_eb == 1;   // ACDSP_FLAG_IN_BYTES: one plane whatever the sign -- unsigned bytes are re-biased on the way into LDS
+  if (bytes) { a.px = 1; }
+  if (a.px > p.in_eb || (bytes && (lz || out_mode != 0))) { return false; }
   if (lz) {
     a.px = p.in_eb;                    // the containers are sign-extended: every byte of them is a plane (the ring shapes are compiled for that)
     a.lz_s = lz->s; a.lz_neg = lz->neg; a.lz_var_y = lz->var_y; a.lz_p_n = lz->p_n; a.lz_p_woff = lz->p_woff; a.lz_p_voff = lz->p_voff;
@@ -314,6 +318,10 @@ static bool gen_fill_args(const FirParams &p, const FirGenPlan &pl, int out_mode
   const GenSelect sel = fir_gen_select(p.in_eb, a.px, pl.pc, pl.nb, p.out_eb, pl.R, lz != nullptr, conv_ok, a.out_vec_ok != 0, ring_env);
   a.px = sel.px;
   a.corr = gen_rebias_corr(a.px, pl.sum_h);
+  if (bytes && !p.in.S) {   // x = (x ^ 0x80 as a signed byte) + 128; the kernels take corr != 0 as the flag of that re-bias
+    a.corr = (int64_t)((uint64_t)pl.sum_h * 128);
+    if (a.corr == 0) { return false; }
+  }
   {
     // plane accumulator w sums the products of (input plane pp, coefficient digit q), pp + q = w, |plane byte| <= 128
     int64_t bw[kGenMaxPX + kGenMaxPC] = {0};
@@ -346,9 +354,10 @@ static bool gen_fill_args(const FirParams &p, const FirGenPlan &pl, int out_mode
 
 // p.n = inputs of this call; outputs m with first + m*R < n.  hist must hold >= off + 16 samples.
 hipError_t launch_fir_gen(const FirParams &p_in, const FirGenPlan &pl, const uint32_t *d_frag, int out_mode, int w_int,
-                          int64_t first, int64_t n_out, hipStream_t s, const FirLossyPlan *lz, int64_t *covered) {
+                          int64_t first, int64_t n_out, hipStream_t s, const FirLossyPlan *lz, int64_t *covered, int32_t *ring_id) {
   FirParams p = p_in;
   if (covered) { *covered = 0; }
+  if (ring_id) { *ring_id = 0; }
   if (lz) { p.lossless_shift = 0; }   // class B: the exact sum is shifted RIGHT by lz->s in front of the ACC_TYPE wrap
   if (n_out <= 0) { return hipSuccess; }
   GenArgs a;
@@ -374,7 +383,10 @@ hipError_t launch_fir_gen(const FirParams &p_in, const FirGenPlan &pl, const uin
     // int32 decimator shape only.  ACDSP_XCD_MAP=0 / 1 forces it off / on for every shape (A/B knob).
     a.xcd_map = (xcd_map_wanted(out_mode == 1 && in_eb == 4) && ((int64_t)grid.x * grid.y) % 8 == 0) ? 1 : 0;
     hipError_t e;
-    if (sel.row) { e = sel.row->launch(sel.spw, sel.pf, sel.nt, sel.fb, grid, s, p, fr, a); }
+    if (sel.row) {
+      e = sel.row->launch(sel.spw, sel.pf, sel.nt, sel.fb, grid, s, p, fr, a);
+      if (ring_id) { *ring_id = sel.row->id; }
+    }
     else if (in_eb == 4) { e = launch_fast<int32_t, 4, 2, 3, 9, 8>(grid, lds_bytes, s, p, fr, a); }
     else if (in_eb == 8) { e = launch_fast<int64_t, 5, 2, 3, 1, 4>(grid, lds_bytes, s, p, fr, a); }
     else if (oeb == 8) { e = launch_fast<int16_t, 2, 3, 6, 9, 8>(grid, lds_bytes, s, p, fr, a); }
@@ -390,6 +402,7 @@ hipError_t launch_fir_gen(const FirParams &p_in, const FirGenPlan &pl, const uin
   a.chunk0 = (int32_t)fast_chunks;                                    // ragged tail (and every unlisted shape): general kernel
   dim3 grid((unsigned)(n_chunks - fast_chunks), (unsigned)p.n_ch);
   switch (p.in_eb) {
+    case 1: return launch_px<int8_t>(a.px, grid, lds_bytes, s, p, fr, a);
     case 2: return launch_px<int16_t>(a.px, grid, lds_bytes, s, p, fr, a);
     case 4: return launch_px<int32_t>(a.px, grid, lds_bytes, s, p, fr, a);
     default: return launch_px<int64_t>(a.px, grid, lds_bytes, s, p, fr, a);

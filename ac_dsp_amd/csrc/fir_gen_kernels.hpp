@@ -106,7 +106,9 @@ __global__ void __launch_bounds__(64, (SMALL && PX <= 5) ? 3 : 2) fir_gen_kernel
   // (not for six and more planes of 8-byte samples: 96 VGPRs of A fragments + 40 of accumulators + 32 of X fragments leave no room
   // for 64 of prefetch -- those instantiations spilled 2 - 27 registers; they load each slot right before staging it)
   constexpr bool CAN_PF = !(sizeof(TIN) == 8 && PX >= 6);
-  constexpr int SPLMAX = CAN_PF ? 16 / (int)sizeof(TIN) : 1;            // 64 VGPRs of prefetch
+  // (byte samples: a slot is one 16-byte load, and 16 of them per lane beside 96 VGPRs of A fragments spilled: 32 VGPRs of prefetch, windows of
+  // more than 512 slots -- DF above 32 -- load each slot right before staging it)
+  constexpr int SPLMAX = CAN_PF ? (sizeof(TIN) == 1 ? 8 : 16 / (int)sizeof(TIN)) : 1;            // 64 VGPRs of prefetch
   const int spl = (a.n_slots + 63) / 64;
   const bool prefetch = CAN_PF && spl <= SPLMAX;
   v4i pre[SPLMAX][sizeof(TIN)];
@@ -128,6 +130,13 @@ __global__ void __launch_bounds__(64, (SMALL && PX <= 5) ? 3 : 2) fir_gen_kernel
   };
   // split one slot (16 samples) into its byte planes and store them
   auto stage_slot = [&](const v4i (&raw)[sizeof(TIN)], int sl) {
+    if constexpr (sizeof(TIN) == 1) {
+      // byte samples (ACDSP_FLAG_IN_BYTES): the 16-byte load IS the slot of the only plane.  Unsigned bytes become x - 128; 128 * sum(h)
+      // rides in a.corr, which is non-zero for nothing else with one plane and doubles as the flag (as in cic2_kernel)
+      static_assert(PX == 1, "byte samples are one plane");
+      const int fx = a.corr != 0 ? (int)0x80808080u : 0;
+      *(v4i *)(lds + phys_slot(sl, a) * 16) = raw[0] ^ (v4i){fx, fx, fx, fx};
+    } else {
     union { v4i v[sizeof(TIN)]; unsigned d[4 * sizeof(TIN)]; } u;
 #pragma unroll
     for (int q = 0; q < (int)sizeof(TIN); q++) { u.v[q] = raw[q]; }
@@ -152,6 +161,7 @@ __global__ void __launch_bounds__(64, (SMALL && PX <= 5) ? 3 : 2) fir_gen_kernel
       if (pp < PX - 1) { o ^= (v4i){(int)0x80808080u, (int)0x80808080u, (int)0x80808080u, (int)0x80808080u}; }  // unsigned plane -> signed
       *(v4i *)(lds + pp * plane_bytes + ps * 16) = o;
     }
+    }   // (sizeof(TIN) > 1)
   };
 
   if (prefetch) { fetch(s0); }
@@ -464,7 +474,7 @@ __global__ void __launch_bounds__(64, 2) fir_gen_ring_kernel(FirParams p, const 
   constexpr int S = (int)sizeof(TIN);
   typedef RingGeom<S, R, NBT> RG;
   constexpr int ADV = RG::ADV, H = RG::H, M = RG::M, NLD = RG::NLD, PPB = RG::PPB, SPK = RG::SPK;
-  static_assert(S == 2 || S == 4, "ring kernel: 2- and 4-byte samples");
+  static_assert(S == 2 || S == 4 || (S == 1 && PX == 1 && !LZ), "ring kernel: 2- and 4-byte samples; 1-byte ones (ACDSP_FLAG_IN_BYTES) as one plane");
   // odd factors above 1 (R = 7: the reference's CIC testbench) and even ones that do not divide the slots of a 1 KB load (R = 10) keep the identity
   // slot map -- gen_slot_map leaves odd factors alone too: one or two extra LDS cycles per fragment read -- so a load need not hold whole groups of R slots
   constexpr bool HOLES = (R % 2 == 0 && SPK % R == 0) || R == 1;   // (even factors that do not divide a 1 KB load -- R = 10: R = 2 mod 4 is conflict-free without holes anyway)
@@ -579,8 +589,15 @@ __global__ void __launch_bounds__(64, 2) fir_gen_ring_kernel(FirParams p, const 
         }
       }
     }
+    if constexpr (S == 1) {
+      // byte samples: a 16-byte piece is one whole slot of the only plane -- no gather.  Unsigned bytes become x - 128; 128 * sum(h) rides in
+      // a.corr, which is non-zero for nothing else with one plane and doubles as the flag (as in cic2_kernel)
+      const int fx = a.corr != 0 ? (int)0x80808080u : 0;
+      *(v4i *)(lds + off) = v ^ (v4i){fx, fx, fx, fx};
+    } else {
 #pragma unroll
-    for (int pp = 0; pp < PX; pp++) { put_piece_plane<S, PX>(v, pp, lds, PLANE, off); }
+      for (int pp = 0; pp < PX; pp++) { put_piece_plane<S, PX>(v, pp, lds, PLANE, off); }
+    }
   };
   unsigned char *ob0 = lds + PX * PLANE;
   char *yrow = (char *)p.y + (int64_t)ch * p.out_stride * OEB;
@@ -1111,6 +1128,14 @@ struct RingRow {
   RingLaunch launch;
 };
 const RingRow *fir_gen_ring_rows(int *n_rows);
+// fir_gen_ring_s8.hip: the byte-sample rows (ACDSP_FLAG_IN_BYTES: fir_gen_ring_kernel<int8_t, 1, 2, ...>, one sample plane), the siblings of
+// the ac_poly_dec rows 10 - 16 at the same input bytes per wave (about 8 KB, every load up front).  One list names them for the table of
+// fir_gen_ring.hip and for the instantiations of fir_gen_ring_s8.hip: X(id, NBT, R, OEB, SPW, PF, FB)
+#define ACDSP_RING_S8_ROWS(X) \
+  X(50, 2, 2, 2, 16, 8, 1) X(51, 2, 2, 8, 16, 8, 0) X(52, 3, 4, 2, 8, 8, 1) X(53, 3, 4, 8, 8, 8, 0) \
+  X(54, 4, 8, 2, 4, 4, 1) X(55, 4, 8, 8, 4, 4, 0) X(56, 8, 16, 2, 2, 2, 1) X(57, 8, 16, 8, 2, 2, 0)
+template <int NBT, int R, int OEB, int SPW, int PF, bool FB>
+hipError_t ring_s8_row_launch(int spw, int pf, int nt, int fb, dim3 grid, hipStream_t s, const FirParams &p, const v4i *frag, const GenArgs &a);
 // fir_gen.hip: what takes a plan (fir_gen_select)
 struct GenSelect {
   const RingRow *row;                          // the ring shape, or nullptr

@@ -81,6 +81,10 @@ static const RingRow kRingRows[] = {
   ACDSP_RING_ROW(43, int32_t, 4, 2, 3, 5, 8, 2, 2, 1, 0, 0, false, false)
   ACDSP_RING_ROW(44, int16_t, 2, 2, 4, 7, 4, 4, 2, 1, 0, 0, false, false)
   ACDSP_RING_ROW(45, int16_t, 2, 2, 4, 7, 8, 4, 2, 1, 0, 0, false, false)
+  // byte samples (ACDSP_FLAG_IN_BYTES): ac_poly_dec at DF = 2, 4, 8, 16 on one sample plane; instantiated in fir_gen_ring_s8.hip
+#define ACDSP_RING_S8_ROW(ID, NBT, R, OEB, SPW, PF, FB) {ID, 1, 1, 2, NBT, R, OEB, SPW, PF, 1, FB, 0, false, false, ring_s8_row_launch<NBT, R, OEB, SPW, PF, (FB != 0)>},
+  ACDSP_RING_S8_ROWS(ACDSP_RING_S8_ROW)
+#undef ACDSP_RING_S8_ROW
   ACDSP_RING_ROW(6, int32_t, 4, 3, 6, 16, 8, 1, 1, 1, 0, 0, true, false)    // CIC R16 N5 on int32: 16 KB per step = one step per wave (LDS: 18 KB of planes per step)
   // class B: the R = 1 shapes 23 / 24 / 25 / 20 / 21 with the residue loop compiled in (the selection ignores ACDSP_GEN_RING for them)
   ACDSP_RING_ROW(23, int16_t, 2, 3, 1, 1, 8, 16, 8, 1, 0, 1, true, false)

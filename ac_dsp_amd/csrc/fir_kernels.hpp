@@ -153,8 +153,11 @@ bool fir_gen_lossy_table(const FirGenPlan &pl, const int64_t *coeffs, int n_taps
 // are this handle's (formats, plan) compiled as a class-B ring shape?  (decided at set_coeffs time: acdsp_fir_path reports it)
 bool fir_gen_lossy_shape_ok(const FirParams &p, const FirGenPlan &pl, int acc_bits);   // acc_bits: FirLossyPlan::acc_bits
 // lz != nullptr: class B -- only complete chunks run here; *covered = outputs written (the caller runs the exact-order kernel on the rest)
+// p.in_eb == 1 (ACDSP_FLAG_IN_BYTES, out_mode 0): one sample plane, unsigned bytes re-biased by 128 (the correction 128 * sum(h) must not be 0 mod 2^64)
+// ring_id: the shape id of the ring row that ran complete chunks of this call, 0 when none did
 hipError_t launch_fir_gen(const FirParams &p, const FirGenPlan &pl, const uint32_t *d_frag, int out_mode, int w_int,
-                          int64_t first, int64_t n_out, hipStream_t s, const FirLossyPlan *lz = nullptr, int64_t *covered = nullptr);
+                          int64_t first, int64_t n_out, hipStream_t s, const FirLossyPlan *lz = nullptr, int64_t *covered = nullptr,
+                          int32_t *ring_id = nullptr);
 
 // Fused decimator -> FIR cascade on the matrix cores (fir_gen_cascade.hip).  pa = stage A as for launch_fir_gen with
 // out_mode 1 (history of >= 256*R + off + 16 samples), pb = stage B formats + output buffer (int32 containers).
@@ -300,6 +303,10 @@ bool polydec_long_plan(const int64_t *coeffs, int ntaps, int df, PolyDecLongPlan
 // with df * 2 bytes per slab output and a head of 32 (nb - 1) samples; two launches per slab of a group, no allocation and no synchronisation
 hipError_t launch_polydec_long(const FirParams &p, const PolyDecLongPlan &plan, const LongGeom &geo, const uint32_t *d_frag,
                                const int64_t *d_corr, void *d_scratch, int64_t n_out, hipStream_t s);
+// ... on 1-byte IN containers (ACDSP_FLAG_IN_BYTES, polydec_s8.hip): ONE sample plane, two accumulator sets.  plan / d_frag as above; d_corr =
+// 128 * sum(c) for unsigned samples (p.in_flip), 0 for signed ones; geo = long_geometry with df bytes per slab output
+hipError_t launch_polydec_s8(const FirParams &p, const PolyDecLongPlan &plan, const LongGeom &geo, const uint32_t *d_frag,
+                             const int64_t *d_corr, void *d_scratch, int64_t n_out, hipStream_t s);
 
 // Long polyphase interpolators (polyintr_long.hip): 65 .. 16384 taps per phase, IF up to 255, as IF Toeplitz products of fir_long.hip's int8
 // split on ONE input stream; the phase rows go to a scratch of the handle and a second kernel interleaves them into the caller's rows

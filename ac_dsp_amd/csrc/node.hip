@@ -434,6 +434,7 @@ int32_t acdsp_node_polydec_create(const acdsp_polydec_desc_t *desc, int32_t n_de
   if (rc) { return rc; }
   h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   if ((rc = create_shards<acdsp_polydec_desc_t, acdsp_polydec_t>(h, *desc, &acdsp_polydec_desc_t::n_channels, acdsp_polydec_create))) { return rc; }
+  h->in_eb = acdsp_polydec_in_elem_bytes((acdsp_polydec_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES
   *out = h;
   return ACDSP_OK;
 }

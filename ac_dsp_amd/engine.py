@@ -403,10 +403,13 @@ class Cic:
 class PolyDec:
     """n_channels independent ac_poly_dec objects (NTAPS taps per branch, decimation DF)."""
 
-    def __init__(self, n_taps, df, fin, fcoeff, facc, fout, n_channels=1, device=0, force_generic=False):
+    def __init__(self, n_taps, df, fin, fcoeff, facc, fout, n_channels=1, device=0, force_generic=False, in_bytes=False):
+        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
         self.n_taps, self.df, self.n_channels = n_taps, df, n_channels
         self.fin, self.fcoeff, self.facc, self.fout = fin, fcoeff, facc, fout
-        d = PolyDecDesc(n_taps, df, n_channels, fin, fcoeff, facc, fout, device, _lib.FLAG_FORCE_GENERIC if force_generic else 0)
+        self.in_bytes = bool(in_bytes)
+        d = PolyDecDesc(n_taps, df, n_channels, fin, fcoeff, facc, fout, device,
+                        (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0))
         self._h = C.c_void_p()
         check(lib.acdsp_polydec_create(C.byref(d), C.byref(self._h)))
 
@@ -416,18 +419,38 @@ class PolyDec:
         check(lib.acdsp_polydec_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
 
     @property
+    def in_dtype(self):
+        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
+        if self.in_bytes:
+            return torch.int8 if self.fin.S else torch.uint8
+        return torch_dtype_for(self.fin)
+
+    @property
     def path(self):
         return PATHS[lib.acdsp_polydec_path(self._h)]
 
+    @property
+    def ring_shape(self):
+        """ring-shape id of the last run(), 0 when no ring row ran (acdsp_polydec_ring_shape)"""
+        return lib.acdsp_polydec_ring_shape(self._h)
+
     def run(self, x, out=None):
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_channels and x.stride(1) == 1
-        assert x.dtype == torch_dtype_for(self.fin) and x.shape[1] % self.df == 0
+        assert x.dtype == self.in_dtype and x.shape[1] % self.df == 0, (x.dtype, self.fin, x.shape)
         n_out = x.shape[1] // self.df
         if out is None:
             out = torch.empty((self.n_channels, max(n_out, 1)), dtype=torch_dtype_for(self.fout), device=x.device)
         check(lib.acdsp_polydec_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), x.shape[1], C.c_void_p(out.data_ptr()),
                                     out.stride(0), _stream_ptr(x)))
         return out[:, :n_out]
+
+    def run_host(self, x):
+        """x: [n_channels][groups * DF] host array of IN raw words -> [n_channels][groups] OUT containers (acdsp_polydec_run_host)"""
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_in_dtype(self.fin, self.in_bytes))
+        assert x.shape[0] == self.n_channels and x.shape[1] % self.df == 0
+        y = _alloc_out_host(self.fout, self.n_channels, x.shape[1] // self.df)
+        check(lib.acdsp_polydec_run_host(self._h, x.ctypes.data_as(C.c_void_p), x.shape[1], y.ctypes.data_as(C.c_void_p)))
+        return y
 
     def set_scratch_cap(self, n_bytes):
         """long prototypes: bound the scratch of the phase streams (re-derives the slab / group geometry, reallocates, synchronises)"""
@@ -886,9 +909,10 @@ class NodeDdc(_Node):
 class NodePolyDec(_Node):
     """A PolyDec bank sharded over `devices` (acdsp_node_polydec_*)."""
 
-    def __init__(self, n_taps, df, fin, fcoeff, facc, fout, n_channels, devices):
+    def __init__(self, n_taps, df, fin, fcoeff, facc, fout, n_channels, devices, in_bytes=False):
         self.fin, self.fout, self.n_channels, self.n_taps, self.df = fin, fout, n_channels, n_taps, df
-        d = PolyDecDesc(n_taps, df, n_channels, fin, fcoeff, facc, fout, 0, 0)
+        self.in_bytes = bool(in_bytes)
+        d = PolyDecDesc(n_taps, df, n_channels, fin, fcoeff, facc, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
         self._h = C.c_void_p()
         check(lib.acdsp_node_polydec_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -903,7 +927,7 @@ class NodePolyDec(_Node):
         assert n_in % self.df == 0
         if outs is None:
             outs = self.alloc(self.fout, n_in // self.df + 8)
-        pin, sin = self._ptrs(xs, self.fin)
+        pin, sin = self._ptrs(xs, self.fin, (torch.int8 if self.fin.S else torch.uint8) if self.in_bytes else None)
         pout, sout = self._ptrs(outs, self.fout)
         check(lib.acdsp_node_polydec_run(self._h, pin, sin, n_in, pout, sout))
         return [o[:, :n_in // self.df] for o in outs]

@@ -489,11 +489,12 @@ private:
 template <class IN_TYPE, class COEFF_TYPE, class ACC_TYPE, class OUT_TYPE>
 class polydec_engine {
 public:
+  // flags: ACDSP_FLAG_* of acdsp_polydec_desc_t (ACDSP_FLAG_IN_BYTES: in_bytes() == 1, rows of 1-byte containers)
   polydec_engine(int n_taps, int df, int n_channels = 1, int device = -1, int flags = 0)
       : n_taps_(n_taps), df_(df), n_ch_(n_channels), device_(device < 0 ? default_device() : device), flags_(flags) {}
 
   int n_channels() const { return n_ch_; }
-  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int in_bytes() const { return (flags_ & ACDSP_FLAG_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
   int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
   acdsp_polydec_t handle() { ensure(); return h_.get(); }
   // raw STR_COEFF_TYPE words [n_taps * df]; uploaded only when they changed
@@ -516,6 +517,16 @@ public:
   void run_host(const void *h_in, int64_t n_in, void *h_out) {
     ensure();
     check(acdsp_polydec_run_host(h_.get(), h_in, n_in, h_out), "acdsp_polydec_run_host");
+  }
+  // typed dense host rows [n_channels][n_in], packed into containers of in_bytes() / unpacked from out_bytes()
+  std::vector<OUT_TYPE> run_host(const std::vector<IN_TYPE> &x) {
+    const size_t n_in = x.size() / (size_t)n_ch_, n_out = n_in / (size_t)df_, ib = (size_t)in_bytes(), ob = (size_t)out_bytes();
+    std::vector<unsigned char> bi(x.size() * ib), bo((size_t)n_ch_ * n_out * ob);
+    for (size_t i = 0; i < x.size(); i++) { container_io<IN_TYPE>::store(x[i], &bi[i * ib], (int)ib); }
+    run_host(bi.data(), (int64_t)n_in, bo.data());
+    std::vector<OUT_TYPE> y((size_t)n_ch_ * n_out);
+    for (size_t i = 0; i < y.size(); i++) { y[i] = container_io<OUT_TYPE>::load(&bo[i * ob], (int)ob); }
+    return y;
   }
   void reset() { if (h_.get()) { check(acdsp_polydec_reset(h_.get()), "acdsp_polydec_reset"); } }
   int path() { ensure(); return acdsp_polydec_path(h_.get()); }

@@ -61,9 +61,11 @@ enum {
 
 /* flags */
 #define ACDSP_FLAG_FORCE_GENERIC 1 /* never pick the MFMA / fast kernels (parity tests) */
-/* acdsp_fir_desc_t::flags, and acdsp_cic_desc_t::flags of a decimator (interp == 0).  IN_TYPE has W <= 8 (signed or unsigned) and travels in
- * 1-BYTE containers: the caller's input rows, the handle's history and the FIR / CIC state blob hold int8_t / uint8_t raw words
- * (acdsp_fir_in_elem_bytes() / acdsp_cic_in_elem_bytes() == 1; acdsp_elem_bytes() is not asked for the input).  in_stride stays in elements;
+/* acdsp_fir_desc_t::flags, acdsp_polydec_desc_t::flags, and acdsp_cic_desc_t::flags of a decimator (interp == 0).  IN_TYPE has W <= 8 (signed
+ * or unsigned) and travels in 1-BYTE containers: the caller's input rows, the handle's history and the FIR / CIC / poly_dec state blob hold
+ * int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() / acdsp_cic_in_elem_bytes() / acdsp_polydec_in_elem_bytes() == 1; acdsp_elem_bytes()
+ * is not asked for the input).  A flagged ac_poly_dec handle resolves as an unflagged one does: ACDSP_PATH_MFMA_GEN on one sample plane where
+ * the ring / window kernels plan the shape, ACDSP_PATH_MFMA_S8 (polydec_s8.hip) on long prototypes, the exact-order kernel elsewhere.  in_stride stays in elements;
  * the output containers are unchanged.  W > 8: ACDSP_EINVAL; ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its
  * input stream is the thin one) and either stage of acdsp_ddc_create / acdsp_node_ddc_create: ACDSP_EUNSUPPORTED, all before any device
  * use.  INTEGRATION.md "Byte samples". */
@@ -306,7 +308,11 @@ int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride
 int32_t acdsp_polydec_run_host(acdsp_polydec_t h, const void *h_in, int64_t n_in, void *h_out);
 int32_t acdsp_polydec_reset(acdsp_polydec_t h);
 int32_t acdsp_polydec_clone(acdsp_polydec_t h, acdsp_polydec_t *out);   /* deep copy, stream state included: "clone" below */
-int32_t acdsp_polydec_path(acdsp_polydec_t h);  /* last run(): ACDSP_PATH_GENERIC, ACDSP_PATH_MFMA_GEN (ring kernel) or ACDSP_PATH_MFMA_LONG (long prototypes) */
+int32_t acdsp_polydec_path(acdsp_polydec_t h);  /* last run(): ACDSP_PATH_GENERIC, ACDSP_PATH_MFMA_GEN (ring kernel), ACDSP_PATH_MFMA_LONG (long prototypes) or, with ACDSP_FLAG_IN_BYTES on long prototypes, ACDSP_PATH_MFMA_S8 */
+/* bytes of one INPUT container of the handle: 1 under ACDSP_FLAG_IN_BYTES, else acdsp_elem_bytes(in.W) */
+int32_t acdsp_polydec_in_elem_bytes(acdsp_polydec_t h);
+/* the ring-shape id (the number ACDSP_GEN_TRACE prints) of the compiled ring row that ran in the last run(), 0 when no ring row ran */
+int32_t acdsp_polydec_ring_shape(acdsp_polydec_t h);
 /* Long prototypes (NTAPS*DF up to 16384, DF up to 256; exact-sum types of up to 16 bits whose shape the ring kernel cannot plan) run as DF
  * matrix-core FIRs on the phase streams, which a first kernel writes into a scratch buffer owned by the handle.  A call is walked as channel
  * groups x time slabs sized so that the scratch stays within a cap (default 128 MiB; at least 8 channels x 1024 outputs).  set_scratch_cap
