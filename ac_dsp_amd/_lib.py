@@ -14,7 +14,7 @@ KINDS = {"const": 0, "load": 1, "prog": 2, "reg_share": 3}
 PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 5: "mfma_lossy", 8: "mfma_long", 9: "mfma_s8"}   # (6 = ACDSP_PATH_CIC_2STAGE: Cic.path only)
 KCLASSES = {**PATHS, 6: "lossy16", 7: "satacc16"}
 FLAG_FORCE_GENERIC = 1
-FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator), PolyDec / NodePolyDec: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
+FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator), PolyDec / NodePolyDec, IntgDump / NodeIntgDump: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
 
 
 class AcdspError(RuntimeError):
@@ -204,6 +204,7 @@ SYMBOLS = {
     "acdsp_intgdump_run_host": (_i32, [_vp, _vp, C.POINTER(_i64), _i64, _vp, _i64, C.POINTER(_i64)]),
     "acdsp_intgdump_reset": (_i32, [_vp]),
     "acdsp_intgdump_path": (_i32, [_vp]),
+    "acdsp_intgdump_in_elem_bytes": (_i32, [_vp]),
     "acdsp_mvavg_create": (_i32, [C.POINTER(MvAvgDesc), C.POINTER(_vp)]),
     "acdsp_mvavg_destroy": (_i32, [_vp]),
     "acdsp_mvavg_set_coeffs": (_i32, [_vp, C.POINTER(_i64)]),

@@ -55,10 +55,12 @@ int32_t acdsp_intgdump_create(const acdsp_intgdump_desc_t *desc, acdsp_intgdump_
   if (d.n_objects > 65535) { return fail(ACDSP_EUNSUPPORTED, "n_objects=%d outside 1..65535", d.n_objects); }
   int rc;
   if ((rc = check_fmt(d.in, "IN_TYPE")) || (rc = check_fmt(d.acc, "ACC_TYPE")) || (rc = check_fmt(d.out, "OUT_TYPE"))) { return rc; }
+  const bool in_bytes = (d.flags & ACDSP_FLAG_IN_BYTES) != 0;
+  if (in_bytes && d.in.W > 8) { return fail(ACDSP_EINVAL, "intg_dump: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
   if ((rc = check_device(d.device))) { return rc; }
   std::unique_ptr<acdsp_intgdump> h(new acdsp_intgdump());   // (check_device has made the device current: a failure below frees there)
   h->d = d;
-  h->in_eb = elem_bytes(d.in.W); h->out_eb = elem_bytes(d.out.W);
+  h->in_eb = in_bytes ? 1 : elem_bytes(d.in.W); h->out_eb = elem_bytes(d.out.W);
   if ((rc = h->temp.init(d.n_objects, d.chn, sizeof(int64_t)))) { return rc; }   // temp[i] = 0.0 (ac_intg_dump.h:86-89)
   *out = h.release();
   return ACDSP_OK;
@@ -187,6 +189,7 @@ int32_t acdsp_intgdump_run(acdsp_intgdump_t h, const void *d_in, int64_t in_stri
 }
 
 int32_t acdsp_intgdump_path(acdsp_intgdump_t h) { return h ? h->last_path : -1; }
+int32_t acdsp_intgdump_in_elem_bytes(acdsp_intgdump_t h) { return h ? h->in_eb : -1; }
 
 int32_t acdsp_intgdump_run_host(acdsp_intgdump_t h, const void *h_in, const int64_t *n_sample, int64_t n_blocks, void *h_out,
                                 int64_t out_cap, int64_t *n_out) {
@@ -231,7 +234,8 @@ int32_t acdsp_intgdump_clone(acdsp_intgdump_t h, acdsp_intgdump_t *out) {
 }
 
 // State blob, kind 8: temp[] of every object, [n_objects][CHN] int64 ACC raw words; bit 0 of the header's `reserved` = the stream stands
-// behind a block that did not dump (its sums sit in temp[]).
+// behind a block that did not dump (its sums sit in temp[]).  Nothing in it depends on the input container: a blob moves both ways between a
+// handle with ACDSP_FLAG_IN_BYTES and one without.
 static StateHdr intgdump_state_hdr(const acdsp_intgdump *h) {
   StateHdr s = state_hdr(8, (uint32_t)h->d.n_objects, (uint32_t)sizeof(int64_t), (uint64_t)h->d.chn);
   s.p0 = (uint32_t)h->d.ns; s.p1 = (uint32_t)h->d.chn;

@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(256) intg_dump_tile_kernel(IntgDumpParams p, i
   // LDS image padded by one dword per 512 bytes: the per-thread walks below start a block length apart (a power of two
   // in the common case) and would otherwise all sit on one bank
   constexpr int kPerDw = 4 / (int)sizeof(TIN) > 0 ? 4 / (int)sizeof(TIN) : 1;      // elements per pad
-  constexpr int kShift = sizeof(TIN) == 2 ? 8 : (sizeof(TIN) == 4 ? 7 : 6);        // log2(elements per 512 bytes)
+  constexpr int kShift = sizeof(TIN) == 1 ? 9 : (sizeof(TIN) == 2 ? 8 : (sizeof(TIN) == 4 ? 7 : 6));   // log2(elements per 512 bytes)
   auto pe = [&](int64_t e) -> int64_t { return e + (e >> kShift) * kPerDw; };
   if (staged) {
     const int64_t n_e = e1 - e0;
@@ -610,6 +610,167 @@ static bool try_mfma(const IntgDumpParams &p, hipStream_t s) {
   return p.in_eb == 2 ? launch_mfma_t<int16_t>(p, (int)tpw, n_tiles, grid, s) : launch_mfma_t<int32_t>(p, (int)tpw, n_tiles, grid, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Byte rows (ACDSP_FLAG_IN_BYTES): the selection-matrix product above on ONE plane, for the shape classes of the streaming and the matrix-core
+// kernels together (CHN 1 .. 16).  The 16 bytes a lane loads ARE its B operand (no plane split, no v_perm); signed bytes go in as they are,
+// unsigned ones are XORed with 0x80 and 128 x rounds is added back per sum.  A kernel that is nothing but a stream has to cover the HBM latency
+// with loads in flight, so a wave walks its tiles as one flat sequence of steps (tile, 64-sample segment) and issues the loads of eight steps --
+// 8 KB, across tile boundaries where blocks are short -- before the first MFMA of the batch.  Four waves per workgroup, each with its own run of
+// tiles.  CHN is a run-time value here: the selection fragment of segment j is fragment j mod P, P = CHN / gcd(64, CHN); P = 1 (CHN 1, 2, 4, 8,
+// 16) keeps it in registers, P > 1 reads it from a P KB table in LDS that the workgroup fills once.  A tile's 16 CHN sums leave the accumulator
+// through a slot of LDS that the wave owns (as many slots as tiles can end inside one batch), and behind the batch's MFMAs the lanes convert
+// and store them in output order, 64 consecutive outputs per store: ACC -> OUT with the IdConv constants where make_conv allows them, the
+// general requant64 elsewhere -- one copy of that code, not one per step of the unrolled batch.
+template <bool BIAS>
+__global__ void __launch_bounds__(256) intg_dump_s8_kernel(IntgDumpParams p, IdConv cv, int tiles_per_wave, int n_tiles, int np, int slots, int pack) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char id_lds[];
+  constexpr int NB = 8;                                  // loads in flight per lane
+  v4i_t *frag = (v4i_t *)id_lds;
+  // pack > 1 (blocks of 16 or 32 bytes, at least 4 rounds): a column is `pack` consecutive blocks, 64 bytes, and row (block in the column) x CHN +
+  // channel of the selection matrix picks its sums, which is the output order again -- one "block" of pack x CHN "channels" from here on
+  const int lane = threadIdx.x & 63, n = lane & 15, kg = lane >> 4, obj = blockIdx.y, chn = pack * p.chn;
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  int *stage = (int *)(id_lds + (np > 1 ? np * 1024 : 0)) + wid * slots * 16 * chn;
+  const int64_t B1 = p.uni_rounds * p.chn, B = pack * B1;   // bytes per block (a multiple of 16) and per column
+  const int nseg = (int)((B + 63) / 64), rem = (int)(B - 64 * (int64_t)(nseg - 1));
+  // lane (row c = lane & 15, kg) holds A[c][16 kg .. 16 kg + 15] of phase (64 q) mod CHN
+  // (one division per fragment, the channel counted up from there: a wave lives for a few batches only, and sixteen would show)
+  auto make_frag = [&](int q) {
+    // pack > 1: the lane's 16 samples lie in one block (16 | B1), a block starts on channel 0 and CHN divides 16, so they start on channel 0
+    int c = pack > 1 ? (B1 == 32 ? kg >> 1 : kg) * p.chn : (np > 1 ? (16 * kg + 64 * q) % chn : 0);   // (np == 1: CHN divides 16)
+    const int c_wrap = pack > 1 ? c + p.chn : chn, c_first = pack > 1 ? c : 0;
+    unsigned w[4];
+#pragma unroll
+    for (int dw = 0; dw < 4; dw++) {
+      w[dw] = 0;
+#pragma unroll
+      for (int bj = 0; bj < 4; bj++) {
+        w[dw] |= (unsigned)((c == n && n < chn) ? 1u : 0u) << (8 * bj);
+        c = c + 1 == c_wrap ? c_first : c + 1;
+      }
+    }
+    return (v4i_t){(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+  };
+  const v4i_t a0 = make_frag(0);
+  if (np > 1) {
+    for (int q = wid; q < np; q += 4) { frag[q * 64 + lane] = make_frag(q); }
+    __syncthreads();
+  }
+  const int wave = (int)blockIdx.x * 4 + wid;
+  const int t0 = wave * tiles_per_wave, t1 = t0 + tiles_per_wave < n_tiles ? t0 + tiles_per_wave : n_tiles;
+  if (t0 >= t1) { return; }
+  const v4i_t zero4 = {0, 0, 0, 0};
+  const bool tail_lane = 16 * kg >= rem;                 // beyond the block in its last segment: the fragment is zero there
+  const v4i_t a0_tail = tail_lane ? zero4 : a0;
+  const char *row = (const char *)p.x + (int64_t)obj * p.in_stride;
+  const unsigned lane_off = (unsigned)n * (unsigned)B + 16u * kg;   // (15 B + 48 < 2^31: fewer than 2^23 rounds of at most 16 channels)
+  const int64_t lane_lim = (int64_t)p.n_blocks * B1 - lane_off;   // the lane has samples while the step's offset is below this
+  const int sh = p.acc.F - p.in.F;
+  const int64_t bias = BIAS ? 128 * p.uni_rounds : 0;
+  const int64_t n_out = (int64_t)p.n_blocks * p.chn, ybase = (int64_t)obj * p.out_stride;
+  const int nsteps = (t1 - t0) * nseg;
+  int ji = 0;                                            // segment of the next load, its tile's and its own offset in the row
+  int64_t tile_i = (int64_t)t0 * 16 * B, off_i = tile_i;
+  int tc = t0, jc = 0, qc = 0;                           // ... of the next MFMA, and its fragment
+  v4i_t acc = zero4;
+  for (int s0 = 0; s0 < nsteps; s0 += NB) {
+    v4i_t v[NB];
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+      // lanes without samples (past the block's end, past the call's last block, past the wave's last step) read the row's first bytes: any
+      // address behind the consumed samples may lie outside the allocation.  (Their sums belong to outputs that do not exist, the fragment
+      // is zero, or there is no MFMA.)  No branch between the loads: the waits in front of the MFMAs then count them down one by one.
+      // (The step's own first 16 bytes always exist: that is where such a lane reads, so that the address is one scalar base + a 32-bit lane offset.)
+      const bool live = s0 + k < nsteps;
+      const int64_t off = live ? off_i : 0;
+      const bool dead = (ji == nseg - 1 && tail_lane) || off >= lane_lim || !live;
+      v[k] = __builtin_nontemporal_load((const v4i_t *)(row + off + (dead ? 0u : lane_off)));
+      const bool last = ji + 1 == nseg;
+      ji = last ? 0 : ji + 1;
+      tile_i += last ? 16 * B : 0;
+      off_i = last ? tile_i : off_i + 64;
+    }
+    asm volatile("" ::: "memory");   // keep the loads in front of the batch's arithmetic (see cascade_kernel)
+    const int tf = tc;               // first tile that ends in this batch
+    int nf = 0;                      // tiles that end in it (<= slots)
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+      if (s0 + k >= nsteps) { break; }
+      v4i_t a = a0;
+      if (np > 1) {
+        a = frag[qc * 64 + lane];
+        if (jc == nseg - 1 && tail_lane) { a = zero4; }
+      } else if (rem < 64 && jc == nseg - 1) { a = a0_tail; }
+      v4i_t o = v[k];
+      if (BIAS) { o ^= (v4i_t){(int)0x80808080u, (int)0x80808080u, (int)0x80808080u, (int)0x80808080u}; }
+      acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, o, acc, 0, 0, 0);
+      if (++qc == np) { qc = 0; }
+      if (++jc == nseg) {
+        // lane (n, kg) holds channels 4 kg + r of the tile's block n: into the slot in output order
+        int *slot = stage + nf * 16 * chn + n * chn + 4 * kg;
+#pragma unroll
+        for (int r = 0; r < 4; r++) { if (4 * kg + r < chn) { slot[r] = acc[r]; } }
+        acc = zero4; jc = 0; qc = 0; tc++; nf++;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int f = 0; f < nf; f++) {
+      const int64_t o0 = (int64_t)(tf + f) * 16 * chn;   // first output of the tile
+      for (int i = lane; i < 16 * chn; i += 64) {
+        if (o0 + i >= n_out) { break; }
+        const int64_t sum = (int64_t)stage[f * 16 * chn + i] + bias;
+        int64_t o;
+        if (cv.ok) {
+          const int64_t a = (int64_t)(((uint64_t)((int64_t)((uint64_t)sum << (cv.sh + cv.ka)) >> cv.ka)) & cv.am);   // wrap to ACC_TYPE
+          int64_t qv = (int64_t)((uint64_t)((a + cv.rnd) >> cv.rs) << cv.ls2);
+          qv = qv < cv.lo ? cv.lo : (qv > cv.hi ? cv.hi : qv);
+          o = (int64_t)(((uint64_t)((int64_t)((uint64_t)qv << cv.ko) >> cv.ko)) & cv.om);
+        } else {
+          o = requant64(wrap64((int64_t)((uint64_t)sum << sh), p.acc.W, p.acc.S), p.acc.F, p.out);
+        }
+        store_raw(p.y, ybase + o0 + i, p.out_eb, o);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // the slots are written again by the next batch
+  }
+}
+
+// true: launched
+static bool try_s8(const IntgDumpParams &p, hipStream_t s) {
+  static const bool off = getenv("ACDSP_NO_INTG_MFMA") != nullptr;   // A/B knob: the LDS-tiled kernel
+  if (off || p.in_eb != 1 || !p.tile_ok || p.uni_rounds <= 0 || p.uni_rounds >= (1 << 23) || p.chn < 1 || p.chn > 16) { return false; }
+  const int64_t B1 = p.uni_rounds * p.chn;
+  if (B1 % 16 != 0 || ((uintptr_t)p.x % 16) != 0 || p.in_stride % 16 != 0 || p.acc.F < p.in.F || p.acc.F - p.in.F >= 32) { return false; }
+  IdConv cv;
+  (void)make_conv(p, cv);   // cv.ok == 0: the kernel converts with the general requant64
+  // blocks of 16 / 32 bytes would leave three quarters / half of every 64-byte segment empty: 4 / 2 of them make one column where the
+  // selection matrix has the rows for it (64 / rounds <= 16)
+  const int pack = ((B1 == 16 || B1 == 32) && p.uni_rounds >= 4) ? (int)(64 / B1) : 1;
+  const int64_t B = pack * B1;
+  const int chn = pack * p.chn;
+  const int n_tiles = (int)(((p.n_blocks + pack - 1) / pack + 15) / 16);
+  // ~16 KB per wave, two batches (8 and 16 KB measured alike on the bench geometry, 64 KB 9 % slower: 4096 workgroups are 2.3 rounds of the 7 a
+  // CU holds), at least ~16 K waves when the problem allows it
+  int64_t tpw = (16384 + 16 * B - 1) / (16 * B);
+  while (tpw > 1 && ((n_tiles + tpw - 1) / tpw) * (int64_t)p.n_obj < 16384) { tpw /= 2; }
+  const int64_t waves = (n_tiles + tpw - 1) / tpw;
+  int g64 = 16;
+  while (p.chn % g64) { g64 /= 2; }                     // gcd(64, CHN), CHN <= 16
+  const int np = pack > 1 ? 1 : p.chn / g64;
+  dim3 grid((unsigned)((waves + 3) / 4), (unsigned)p.n_obj);
+  // LDS: np fragments of 1 KB where the pattern has a period, and per wave one slot of 16 CHN sums for every tile that can end inside a batch
+  // of 8 segments (at most 15 KB + 4 x 8 KB)
+  const int64_t nseg = (B + 63) / 64;
+  const int slots = nseg >= 8 ? 1 : (int)((8 + nseg - 1) / nseg);
+  const size_t lds = (np > 1 ? (size_t)np * 64 * sizeof(v4i_t) : 0) + (size_t)4 * slots * 16 * chn * sizeof(int);
+  if (!p.in.S) { hipLaunchKernelGGL(intg_dump_s8_kernel<true>, grid, dim3(256), lds, s, p, cv, (int)tpw, n_tiles, np, slots, pack); }
+  else { hipLaunchKernelGGL(intg_dump_s8_kernel<false>, grid, dim3(256), lds, s, p, cv, (int)tpw, n_tiles, np, slots, pack); }
+  return true;
+}
+
 // true: launched.  Shape conditions of the streaming kernel (see above); rows must start on 16-byte boundaries.
 static bool try_stream(const IntgDumpParams &p, hipStream_t s) {
   if (!p.tile_ok || p.uni_rounds <= 0 || p.uni_rounds >= 32768 || (p.in_eb != 2 && p.in_eb != 4)) { return false; }
@@ -679,7 +840,7 @@ hipError_t launch_intg_dump(const IntgDumpParams &p, int64_t *temp_next, hipStre
     *temp_written = false;   // every block dumped and nothing was carried in (tile_ok): temp[] was zero and is zero
     return hipGetLastError();
   }
-  if (try_mfma(p, s)) {
+  if (try_mfma(p, s) || try_s8(p, s)) {
     *path = 3;
     *temp_written = false;
     return hipGetLastError();
@@ -689,6 +850,7 @@ hipError_t launch_intg_dump(const IntgDumpParams &p, int64_t *temp_next, hipStre
     const int lds_elems = (47 * 1024) / p.in_eb;   // + one pad dword per 512 bytes stays inside the 48 KB
     dim3 grid((unsigned)((p.n_blocks + bpw - 1) / bpw), (unsigned)p.n_obj);
     switch (p.in_eb) {
+      case 1: hipLaunchKernelGGL(intg_dump_tile_kernel<int8_t>, grid, dim3(256), 48 * 1024, s, p, bpw, lds_elems); break;   // ACDSP_FLAG_IN_BYTES
       case 2: hipLaunchKernelGGL(intg_dump_tile_kernel<int16_t>, grid, dim3(256), 48 * 1024, s, p, bpw, lds_elems); break;
       case 4: hipLaunchKernelGGL(intg_dump_tile_kernel<int32_t>, grid, dim3(256), 48 * 1024, s, p, bpw, lds_elems); break;
       default: hipLaunchKernelGGL(intg_dump_tile_kernel<int64_t>, grid, dim3(256), 48 * 1024, s, p, bpw, lds_elems); break;

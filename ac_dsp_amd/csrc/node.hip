@@ -493,6 +493,7 @@ int32_t acdsp_node_intgdump_create(const acdsp_intgdump_desc_t *desc, int32_t n_
   if (rc) { return rc; }
   h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   if ((rc = create_shards<acdsp_intgdump_desc_t, acdsp_intgdump_t>(h, *desc, &acdsp_intgdump_desc_t::n_objects, acdsp_intgdump_create))) { return rc; }
+  h->in_eb = acdsp_intgdump_in_elem_bytes((acdsp_intgdump_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES
   *out = h;
   return ACDSP_OK;
 }

@@ -635,11 +635,20 @@ class IntgDump:
     """n_objects independent ac_intg_dump<IN, ACC, OUT, N_TYPE, NS, CHN> objects (C ABI acdsp_intgdump_*); rows are the
     interleaved streams, n_sample the per-block N_TYPE words (shared by the objects)."""
 
-    def __init__(self, ns, chn, fin, facc, fout, n_objects=1, device=0):
+    def __init__(self, ns, chn, fin, facc, fout, n_objects=1, device=0, in_bytes=False):
+        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
         self.fin, self.fout, self.n_objects, self.chn = fin, fout, n_objects, chn
-        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, device, 0)
+        self.in_bytes = bool(in_bytes)
+        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, device, _lib.FLAG_IN_BYTES if in_bytes else 0)
         self._h = C.c_void_p()
         check(lib.acdsp_intgdump_create(C.byref(d), C.byref(self._h)))
+
+    @property
+    def in_dtype(self):
+        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
+        if self.in_bytes:
+            return torch.int8 if self.fin.S else torch.uint8
+        return torch_dtype_for(self.fin)
 
     def counts(self, n_sample):
         ns = np.ascontiguousarray(n_sample, dtype=np.int64)
@@ -651,12 +660,25 @@ class IntgDump:
         ns = np.ascontiguousarray(n_sample, dtype=np.int64)
         ni, no = self.counts(ns)
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_objects and x.stride(1) == 1 and x.shape[1] >= ni
-        assert x.dtype == torch_dtype_for(self.fin), (x.dtype, self.fin)
+        assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         out = torch.empty((self.n_objects, max(no, 1)), dtype=torch_dtype_for(self.fout), device=x.device)
         n_out = C.c_int64()
         check(lib.acdsp_intgdump_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), ns.ctypes.data_as(C.POINTER(C.c_int64)), len(ns),
                                      C.c_void_p(out.data_ptr()), out.stride(0), C.byref(n_out), _stream_ptr(x)))
         return out[:, :n_out.value]
+
+    def run_host(self, x, n_sample):
+        """run() on host rows [n_objects][>= the samples n_sample consumes] (dense rows of exactly that many samples go to the device)"""
+        ns = np.ascontiguousarray(n_sample, dtype=np.int64)
+        ni, no = self.counts(ns)
+        x = np.atleast_2d(x)
+        assert x.shape[0] == self.n_objects and x.shape[1] >= ni
+        x = np.ascontiguousarray(x[:, :ni], dtype=_np_in_dtype(self.fin, self.in_bytes))
+        y = _alloc_out_host(self.fout, self.n_objects, max(no, 1))
+        n_out = C.c_int64()
+        check(lib.acdsp_intgdump_run_host(self._h, x.ctypes.data_as(C.c_void_p), ns.ctypes.data_as(C.POINTER(C.c_int64)), len(ns),
+                                          y.ctypes.data_as(C.c_void_p), y.shape[1], C.byref(n_out)))
+        return y[:, :n_out.value]
 
     @property
     def path(self):
@@ -968,19 +990,27 @@ class NodePolyIntr(_Node):
 class NodeIntgDump(_Node):
     """An IntgDump bank (rows = objects) sharded over `devices` (acdsp_node_intgdump_*)."""
 
-    def __init__(self, ns, chn, fin, facc, fout, n_objects, devices):
+    def __init__(self, ns, chn, fin, facc, fout, n_objects, devices, in_bytes=False):
         self.fin, self.fout, self.n_objects, self.ns, self.chn = fin, fout, n_objects, ns, chn
-        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, 0, 0)
+        self.in_bytes = bool(in_bytes)
+        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
         self._h = C.c_void_p()
         check(lib.acdsp_node_intgdump_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
+
+    @property
+    def in_dtype(self):
+        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
+        if self.in_bytes:
+            return torch.int8 if self.fin.S else torch.uint8
+        return torch_dtype_for(self.fin)
 
     def run(self, xs, n_sample, outs=None):
         ns = np.ascontiguousarray(n_sample, dtype=np.int64)
         n_dump = int(((ns >= 1) & (ns <= self.ns)).sum()) * self.chn
         if outs is None:
             outs = self.alloc(self.fout, (max(n_dump, 1) + 7) // 8 * 8)
-        pin, sin = self._ptrs(xs, self.fin)
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype if self.in_bytes else None)
         pout, sout = self._ptrs(outs, self.fout)
         n_out = C.c_int64()
         check(lib.acdsp_node_intgdump_run(self._h, pin, sin, ns.ctypes.data_as(C.POINTER(C.c_int64)), len(ns), pout, sout, C.byref(n_out)))

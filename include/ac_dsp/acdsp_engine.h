@@ -604,11 +604,12 @@ private:
 template <class IN_TYPE, class ACC_TYPE, class OUT_TYPE>
 class intgdump_engine {
 public:
-  intgdump_engine(int ns, int chn, int n_objects = 1, int device = -1)
-      : ns_(ns), chn_(chn), n_obj_(n_objects), device_(device < 0 ? default_device() : device) {}
+  // flags: ACDSP_FLAG_* of acdsp_intgdump_desc_t (ACDSP_FLAG_IN_BYTES: in_bytes() == 1, rows of 1-byte containers)
+  intgdump_engine(int ns, int chn, int n_objects = 1, int device = -1, int flags = 0)
+      : ns_(ns), chn_(chn), n_obj_(n_objects), device_(device < 0 ? default_device() : device), flags_(flags) {}
 
   int n_objects() const { return n_obj_; }
-  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
+  int in_bytes() const { return (flags_ & ACDSP_FLAG_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
   int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
   acdsp_intgdump_t handle() { ensure(); return h_.get(); }
   // samples a call with this block table consumes / outputs it yields, per object
@@ -639,11 +640,11 @@ private:
     acdsp_intgdump_desc_t d;
     d.ns = ns_; d.chn = chn_; d.n_objects = n_obj_;
     d.in = fmt_of<IN_TYPE>(); d.acc = fmt_of<ACC_TYPE>(); d.out = fmt_of<OUT_TYPE>();
-    d.device = device_; d.flags = 0;
+    d.device = device_; d.flags = flags_;
     check(acdsp_intgdump_create(&d, h_.slot()), "acdsp_intgdump_create");
   }
   cloned_handle<acdsp_intgdump_t, acdsp_intgdump_clone, acdsp_intgdump_destroy> h_;
-  int ns_, chn_, n_obj_, device_;
+  int ns_, chn_, n_obj_, device_, flags_;
 };
 
 // rows = objects; win_mode: ACDSP_WIN_PLAIN / _MIRROR / _CLIP.  ac_mv_avg keeps nothing between calls (the reference builds its core inside

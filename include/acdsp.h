@@ -61,14 +61,16 @@ enum {
 
 /* flags */
 #define ACDSP_FLAG_FORCE_GENERIC 1 /* never pick the MFMA / fast kernels (parity tests) */
-/* acdsp_fir_desc_t::flags, acdsp_polydec_desc_t::flags, and acdsp_cic_desc_t::flags of a decimator (interp == 0).  IN_TYPE has W <= 8 (signed
- * or unsigned) and travels in 1-BYTE containers: the caller's input rows, the handle's history and the FIR / CIC / poly_dec state blob hold
- * int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() / acdsp_cic_in_elem_bytes() / acdsp_polydec_in_elem_bytes() == 1; acdsp_elem_bytes()
- * is not asked for the input).  A flagged ac_poly_dec handle resolves as an unflagged one does: ACDSP_PATH_MFMA_GEN on one sample plane where
- * the ring / window kernels plan the shape, ACDSP_PATH_MFMA_S8 (polydec_s8.hip) on long prototypes, the exact-order kernel elsewhere.  in_stride stays in elements;
- * the output containers are unchanged.  W > 8: ACDSP_EINVAL; ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its
- * input stream is the thin one) and either stage of acdsp_ddc_create / acdsp_node_ddc_create: ACDSP_EUNSUPPORTED, all before any device
- * use.  INTEGRATION.md "Byte samples". */
+/* acdsp_fir_desc_t::flags, acdsp_polydec_desc_t::flags, acdsp_intgdump_desc_t::flags, and acdsp_cic_desc_t::flags of a decimator
+ * (interp == 0).  IN_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE containers: the caller's input rows, the handle's history and
+ * the FIR / CIC / poly_dec state blob hold int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() / acdsp_cic_in_elem_bytes() /
+ * acdsp_polydec_in_elem_bytes() / acdsp_intgdump_in_elem_bytes() == 1; acdsp_elem_bytes() is not asked for the input).  A flagged ac_poly_dec
+ * handle resolves as an unflagged one does: ACDSP_PATH_MFMA_GEN on one sample plane where the ring / window kernels plan the shape,
+ * ACDSP_PATH_MFMA_S8 (polydec_s8.hip) on long prototypes, the exact-order kernel elsewhere.  A flagged ac_intg_dump handle keeps no samples: its
+ * state blob (the ACC words of temp[]) is that of an unflagged handle and moves both ways; acdsp_intgdump_path below names its kernels.
+ * in_stride stays in elements; the output containers are unchanged.  W > 8: ACDSP_EINVAL (every family, ac_intg_dump included -- its only
+ * refusal); ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its input stream is the thin one) and either stage of
+ * acdsp_ddc_create / acdsp_node_ddc_create: ACDSP_EUNSUPPORTED, all before any device use.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_IN_BYTES 2
 
 /* which kernel family a FIR handle resolved to (acdsp_fir_path) */
@@ -379,7 +381,16 @@ int32_t acdsp_intgdump_run_host(acdsp_intgdump_t h, const void *h_in, const int6
                                 int64_t out_cap, int64_t *n_out);
 int32_t acdsp_intgdump_reset(acdsp_intgdump_t h);
 int32_t acdsp_intgdump_clone(acdsp_intgdump_t h, acdsp_intgdump_t *out);   /* deep copy, temp[] included: "clone" below */
-int32_t acdsp_intgdump_path(acdsp_intgdump_t h);   /* kernel family of the last run(): 0 exact order (ragged blocks / carried sums / saturating ACC), 1 LDS-tiled, 2 streaming, 3 matrix cores (selection-matrix product: CHN that does not divide a 16-byte load) */
+/* kernel family of the last run(): 0 exact order (ragged blocks / carried sums / saturating ACC), 1 LDS-tiled, 2 streaming, 3 matrix cores
+ * (selection-matrix product: CHN that does not divide a 16-byte load).  Under ACDSP_FLAG_IN_BYTES: 3 for the shapes of 2 and 3 together --
+ * wrapping or sat-free ACC_TYPE, every block dumps the same number of rounds (< 2^23), 1 <= CHN <= 16, blocks of a multiple of 16 samples,
+ * 16-byte aligned rows and row pitch, 0 <= acc.F - in.F < 32 -- on one sample plane (there is no byte form of 2); 1 for the other uniform
+ * lossless shapes up to CHN 256, and under ACDSP_NO_INTG_MFMA; 0 elsewhere. */
+int32_t acdsp_intgdump_path(acdsp_intgdump_t h);
+/* bytes of one INPUT container of the handle: 1 under ACDSP_FLAG_IN_BYTES, else acdsp_elem_bytes(in.W).  temp[] and its state blob (kind 8,
+ * int64 ACC words) do not depend on it: a blob of a flagged handle restores into an unflagged one of the same NS / CHN / object count and
+ * the other way round. */
+int32_t acdsp_intgdump_in_elem_bytes(acdsp_intgdump_t h);
 
 /* ---- moving average (reference ac_mv_avg.h:93-196) ----
  * One run() = one run() call of every object: n_frames frames of n_sample input samples each, back to back in the row (the

@@ -1,0 +1,25 @@
+"""GPU test of the C++ layer on byte samples of ac_intg_dump: tests/cpp/tb_intgdump_bytes.cpp runs acdsp::intgdump_engine with
+ACDSP_FLAG_IN_BYTES against an unflagged engine on the same values through run_host in two calls, and moves the state between a flagged and an
+unflagged engine, both ways, through state() / set_state()."""
+import os
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "tests", "_bin", "tb_intgdump_bytes")
+
+
+@pytest.fixture(scope="module")
+def built():
+    if not os.path.exists(EXE):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), EXE])   # the Makefile's pattern rule $(BIN)/%: %.cpp
+    return EXE
+
+
+def test_intgdump_engine_with_byte_containers_equals_the_int16_engine(built):
+    p = subprocess.run([built], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0 and "Test PASSED." in out, out
