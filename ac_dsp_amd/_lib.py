@@ -15,6 +15,7 @@ PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 
 KCLASSES = {**PATHS, 6: "lossy16", 7: "satacc16"}
 FLAG_FORCE_GENERIC = 1
 FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator), PolyDec / NodePolyDec, IntgDump / NodeIntgDump: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
+FLAG_OUT_BYTES = 4  # Fir / NodeFir together with FLAG_IN_BYTES: OUT_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_OUT_BYTES)
 
 
 class AcdspError(RuntimeError):
@@ -163,6 +164,7 @@ SYMBOLS = {
     "acdsp_fir_kernel_stats": (_i32, [_vp, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "acdsp_fir_mfma_issued": (_i32, [_vp, C.POINTER(C.c_int32)]),
     "acdsp_fir_in_elem_bytes": (_i32, [_vp]),
+    "acdsp_fir_out_elem_bytes": (_i32, [_vp]),
     "acdsp_cic_create": (_i32, [C.POINTER(CicDesc), C.POINTER(_vp)]),
     "acdsp_cic_destroy": (_i32, [_vp]),
     "acdsp_cic_clone": (_i32, [_vp, C.POINTER(_vp)]),

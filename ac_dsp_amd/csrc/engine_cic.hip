@@ -69,6 +69,7 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   if (desc->n_channels > 65535) { return fail(ACDSP_EUNSUPPORTED, "CIC: n_channels=%d outside 1..65535", desc->n_channels); }
   const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
   if (in_bytes && (rc = cic_bytes_refusal(*desc))) { return rc; }
+  if (desc->flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "CIC: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_cic> h(new acdsp_cic());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;

@@ -27,6 +27,7 @@ int32_t acdsp_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fi
   if (fir->coeffs_per_channel) { return fail(ACDSP_EUNSUPPORTED, "ddc: one shared coefficient set"); }
   if (fir->flags & ACDSP_FLAG_IN_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_IN_BYTES on the cascade's FIR (it reads the decimator's INT_TYPE words)"); }
   if (cic->flags & ACDSP_FLAG_IN_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_IN_BYTES on the cascade's CIC decimator (the cascade kernel reads int16 rows)"); }
+  if ((fir->flags | cic->flags) & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_OUT_BYTES on a stage of the cascade (1-byte output rows: the FIR under both byte flags only)"); }
   std::unique_ptr<acdsp_ddc, int32_t (*)(acdsp_ddc_t)> h(new acdsp_ddc(), acdsp_ddc_destroy);
   int rc;
   if ((rc = acdsp_cic_create(cic, &h->cic)) || (rc = acdsp_fir_create(fir, &h->fir))) { return rc; }

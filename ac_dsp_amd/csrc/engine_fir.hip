@@ -137,6 +137,13 @@ int fir_validate(const acdsp_fir_desc_t &d) {
     return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 256-bit intermediates");
   }
   if (wide && d.kind == ACDSP_FIR_REG_SHARE) { return fail(ACDSP_EUNSUPPORTED, "ac_fir_reg_share: ACC / OUT wider than 64 bits not supported"); }
+  if (d.flags & ACDSP_FLAG_OUT_BYTES) {
+    if (d.out.W > 8) { return fail(ACDSP_EINVAL, "ACDSP_FLAG_OUT_BYTES: OUT_TYPE W=%d does not fit a 1-byte container", d.out.W); }
+    // the int16-sample kernels have no 1-byte output tile: byte outputs of an unflagged input are the follow-up
+    if (!(d.flags & ACDSP_FLAG_IN_BYTES)) {
+      return fail(ACDSP_EUNSUPPORTED, "ACDSP_FLAG_OUT_BYTES without ACDSP_FLAG_IN_BYTES: only the byte-sample kernels write 1-byte output rows (the int16-sample kernels are not done yet)");
+    }
+  }
   if (d.flags & ACDSP_FLAG_IN_BYTES) {
     if (d.in.W > 8) { return fail(ACDSP_EINVAL, "ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
     if (wide) { return fail(ACDSP_EUNSUPPORTED, "ACDSP_FLAG_IN_BYTES: ACC_TYPE or OUT_TYPE wider than 64 bits not supported"); }
@@ -166,7 +173,7 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   h->d = *desc;
   const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
   h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
-  h->out_eb = elem_bytes(desc->out.W);
+  h->out_eb = (desc->flags & ACDSP_FLAG_OUT_BYTES) ? 1 : elem_bytes(desc->out.W);   // (fir_validate: W <= 8 and byte samples under the flag)
   h->wide = desc->acc.W > 64 || desc->out.W > 64;
   h->rt_eb = h->wide ? 16 : 8;
   h->hl = round_up(desc->n_taps + 15, 32);  // >= n_taps-1 for every kernel, >= n_taps+14 for the 16-aligned windows of fir_gen
@@ -758,6 +765,7 @@ int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples) {
 }
 
 int32_t acdsp_fir_in_elem_bytes(acdsp_fir_t h) { return h ? h->in_eb : -1; }
+int32_t acdsp_fir_out_elem_bytes(acdsp_fir_t h) { return h ? h->out_eb : -1; }
 
 }  // extern "C"
 

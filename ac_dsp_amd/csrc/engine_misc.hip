@@ -57,6 +57,7 @@ int32_t acdsp_intgdump_create(const acdsp_intgdump_desc_t *desc, acdsp_intgdump_
   if ((rc = check_fmt(d.in, "IN_TYPE")) || (rc = check_fmt(d.acc, "ACC_TYPE")) || (rc = check_fmt(d.out, "OUT_TYPE"))) { return rc; }
   const bool in_bytes = (d.flags & ACDSP_FLAG_IN_BYTES) != 0;
   if (in_bytes && d.in.W > 8) { return fail(ACDSP_EINVAL, "intg_dump: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
+  if (d.flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "intg_dump: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
   if ((rc = check_device(d.device))) { return rc; }
   std::unique_ptr<acdsp_intgdump> h(new acdsp_intgdump());   // (check_device has made the device current: a failure below frees there)
   h->d = d;
@@ -323,6 +324,7 @@ int32_t acdsp_mvavg_create(const acdsp_mvavg_desc_t *desc, acdsp_mvavg_t *out) {
   // 128-bit exact intermediates: ACC x COEFF product aligned with the accumulator
   const int fc = desc->coeff.W - desc->coeff.I;
   if (desc->acc.W + desc->coeff.W + 2 + (fc < 0 ? -fc : 0) > 125) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: type combination needs more than 128-bit intermediates"); }
+  if (desc->flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_mvavg> h(new acdsp_mvavg());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;

@@ -86,6 +86,7 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
     return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %lld: more than 2048 taps run on the long matrix-core kernel only, which does not take %s",
                 (long long)desc->n_taps * desc->df, long_why);
   }
+  if (desc->flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "poly_dec: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_polydec> h(new acdsp_polydec());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
@@ -505,6 +506,7 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
   if (d.n_taps > 2048 && long_why) {
     return fail(ACDSP_EUNSUPPORTED, "poly_intr: NTAPS=%d: more than 2048 taps run on the long matrix-core kernels only, which do not take %s", d.n_taps, long_why);
   }
+  if (d.flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "poly_intr: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
   if ((rc = check_device(d.device))) { return rc; }
   std::unique_ptr<acdsp_polyintr> h(new acdsp_polyintr());   // (check_device has made the device current: a failure below frees there)
   h->d = d;

@@ -20,7 +20,9 @@
 //     and the loop then runs without a barrier (each wave's window is its own; LDS serves one wave's accesses in order).  The LDS of a launch
 //     is sized for its form.
 //   * Epilogue: wrap64 / requant64 / store_raw as in fir_long_kernel, or -- where the host proves |V| < 2^30, no wrap of ACC_TYPE, AC_TRN /
-//     AC_RND into a 2-byte AC_SAT / signed AC_WRAP output -- the same value from 32-bit arithmetic, stored 16 bytes per lane.
+//     AC_RND into a 2-byte AC_SAT / signed AC_WRAP output -- the same value from 32-bit arithmetic, stored 16 bytes per lane.  Under
+//     ACDSP_FLAG_OUT_BYTES (OUT_TYPE of up to 8 bits in 1-byte containers) the 32-bit epilogue has a 1-byte form (OEB = 1: a step is 1 KB of
+//     outputs, 16 bytes per lane in ONE store); the 64-bit one stores through store_raw, which has a 1-byte case.
 //   * The K-blocks of a segment run as three loops (below, inside, above the high-byte range): no branch around an LDS read or a product.
 //
 // Barrier uniformity.  Every loop bound and every branch around a barrier is made of launch arguments and blockIdx only: NSEG (and with it
@@ -60,7 +62,7 @@ struct S8Args {
   uint32_t x_xor;           // unsigned samples: 0x80808080 turns every byte into x - 128; else 0
   int32_t a_words;          // v4i words of the A region of LDS: 2 nb 64 (one segment, resident) or 2 kLongAWords (double-buffered segments)
   int32_t np;               // window loads per segment: 2 (63 + nb) resident, 2 (63 + kLongSB) segmented
-  int32_t fast;             // 32-bit epilogue (launch_fir_s8): y = clamp / wrap((V + half) >> rs) into 2-byte containers
+  int32_t fast;             // 32-bit epilogue (launch_fir_s8): y = clamp / wrap((V + half) >> rs) into 2-byte (OEB = 1: 1-byte) containers
   int32_t rs, half, ylo, yhi, wrap_sh, vec;   // wrap_sh: 32 - W_out for a signed AC_WRAP output, else 0; vec: rows take 16-byte stores
   int32_t sat16;            // ... and OUT_TYPE is a signed 16-bit AC_SAT type (the bounds are those of the packing conversion)
   const int64_t *corr;      // [1] 128 * sum(c) for unsigned samples, else 0
@@ -72,7 +74,9 @@ struct S8Args {
 // there are: this instantiation has no branch around a global access -- three window loads (clamped, not skipped) and four stores per
 // iteration, an even number of iterations per workgroup -- where the general one has the ragged-step and unaligned-row branches.  The rest
 // of a call (fewer than 4096 samples per channel) is a second, general launch.
-template <bool FAST, bool STREAM>
+// OEB (with FAST): bytes of an output container of the 32-bit epilogue, 2 or 1 (ACDSP_FLAG_OUT_BYTES); there three window loads and TWO stores
+// per iteration of the STREAM form.  The 64-bit epilogue takes the container from p.out_eb.
+template <bool FAST, bool STREAM, int OEB>
 __global__ void __launch_bounds__(512, 2)
 fir_s8_kernel(FirParams p, const v4i *__restrict__ frag, S8Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
@@ -144,7 +148,61 @@ fir_s8_kernel(FirParams p, const v4i *__restrict__ frag, S8Args a) {
   // outputs [T0, T0 + 1024) of the channel from one step's accumulators
   // (ob: the wave's window buffer of this iteration, read to the end by now)
   auto epilogue = [&](const v16i &hi, const v16i &lo, int64_t T0, unsigned char *ob) __attribute__((always_inline)) {
-    if (FAST) {
+    if constexpr (FAST && OEB == 1) {
+      // the 32-bit epilogue into 1-byte containers: lane (n, h) holds outputs 32 n + 8 q + 4 h + rr, so quad q is one dword of the row
+      const int c32 = (int)corr;
+      unsigned P[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        unsigned w = 0;
+#pragma unroll
+        for (int rr = 0; rr < 4; rr++) {
+          const int r = 4 * q + rr;
+          const int v = (int)(((unsigned)hi[r] << 8) + (unsigned)lo[r] + (unsigned)c32);
+          int yy = (v + a.half) >> a.rs;
+          yy = yy < a.ylo ? a.ylo : (yy > a.yhi ? a.yhi : yy);                     // AC_SAT (AC_WRAP: the whole int32 range)
+          yy = (int)((unsigned)yy << a.wrap_sh) >> a.wrap_sh;                      // signed AC_WRAP: sign-extend from W_out
+          w |= ((unsigned)yy & 0xffu) << (8 * rr);
+        }
+        P[q] = w;
+      }
+      const int64_t tb = T0 + 32 * n_col;
+      unsigned char *yrow = (unsigned char *)p.y + (int64_t)ch * p.out_stride;
+      if (STREAM) {
+        // the step's 1 KB of outputs through the wave's own window buffer into memory order: the store writes one run of 1 KB, lane = 16-byte
+        // chunk of it.  Lane (n, h) holds, per q, the 4 bytes at 32 n + 8 q + 4 h; the 8-byte piece inside a block is XOR-ed with (n >> 3) & 3
+        // against bank conflicts of the writes (the 64 lanes of one q then cover 64 different dwords mod 64)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          *(unsigned *)(ob + 32 * n_col + 8 * (q ^ ((n_col >> 3) & 3)) + 4 * h) = P[q];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        {
+          // chunk `lane` = block lane >> 1, pieces 2 g and 2 g + 1 (g = lane & 1): they sit in granule g ^ (sw >> 1), swapped where sw is odd
+          const int blk = lane >> 1, sw = (blk >> 3) & 3;
+          const v4i t = *(const v4i *)(ob + 32 * blk + 16 * ((lane & 1) ^ (sw >> 1)));
+          const v4i o = (sw & 1) ? (v4i){t.z, t.w, t.x, t.y} : t;
+          *(v4i *)(yrow + T0 + 16 * lane) = o;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+      } else if (live && a.vec && T0 + 1024 <= p.n) {   // (wave-uniform: whole step inside the call)
+        // one exchange of two dwords: h = 0 then owns bytes 32 n .. + 15 (its own quads 0, 1 and the partner's), h = 1 bytes 32 n + 16 .. + 31
+        const unsigned R0 = (unsigned)__shfl_xor((int)(h ? P[0] : P[2]), 32);
+        const unsigned R1 = (unsigned)__shfl_xor((int)(h ? P[1] : P[3]), 32);
+        const v4i o = h ? (v4i){(int)R0, (int)P[2], (int)R1, (int)P[3]} : (v4i){(int)P[0], (int)R0, (int)P[1], (int)R1};
+        *(v4i *)(yrow + tb + 16 * h) = o;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int64_t t0 = tb + 8 * q + 4 * h;
+#pragma unroll
+          for (int rr = 0; rr < 4; rr++) {
+            if (live && t0 + rr < p.n) { yrow[t0 + rr] = (unsigned char)(P[q] >> (8 * rr)); }
+          }
+        }
+      }
+    } else if (FAST) {
       // |V| < 2^30 and ACC_TYPE neither wraps nor rounds (launch_fir_s8): V, the rounding add and the shift in 32 bits
       const int c32 = (int)corr;
       unsigned P[4][2];
@@ -365,7 +423,8 @@ hipError_t launch_fir_s8(const FirParams &p, const FirLongPlan &plan, int64_t su
   const bool small_v = sum_abs >= 0 && sum_abs < ((int64_t)1 << 30) / xmax;
   const int sh = p.lossless_shift;
   const bool acc_exact = p.acc.S && p.acc.O == ACDSP_WRAP && sh >= 0 && p.acc.W >= 2 && p.acc.W <= 64 && 31 + sh <= p.acc.W - 1;
-  const bool out_ok = p.out_eb == 2 && p.out.W >= 2 && p.out.W <= 16 && (p.out.Q == ACDSP_TRN || p.out.Q == ACDSP_RND) &&
+  if (p.out_eb == 1 && p.out.W > 8) { return hipErrorInvalidValue; }
+  const bool out_ok = ((p.out_eb == 2 && p.out.W <= 16) || (p.out_eb == 1 && p.out.W <= 8)) && p.out.W >= 2 && (p.out.Q == ACDSP_TRN || p.out.Q == ACDSP_RND) &&
                       (p.out.O == ACDSP_SAT || (p.out.O == ACDSP_WRAP && p.out.S)) && rs >= 1 && rs <= 29;
   if (small_v && acc_exact && out_ok) {
     a.fast = 1;
@@ -376,7 +435,7 @@ hipError_t launch_fir_s8(const FirParams &p, const FirLongPlan &plan, int64_t su
     a.yhi = sat ? (int32_t)p.out.hi : INT32_MAX;
     a.wrap_sh = sat ? 0 : 32 - p.out.W;
     a.sat16 = (sat && p.out.S && p.out.W == 16) ? 1 : 0;
-    a.vec = ((uintptr_t)p.y % 16 == 0 && p.out_stride % 8 == 0) ? 1 : 0;
+    a.vec = ((uintptr_t)p.y % 16 == 0 && p.out_stride * p.out_eb % 16 == 0) ? 1 : 0;   // (out_stride in elements: % 8 of 2-byte, % 16 of 1-byte ones)
   }
   const size_t lds = (size_t)a.a_words * 16 + (size_t)8 * 2 * kS8XBytes;
   // one constant limit for every instantiation and form (the larger form's): handles of different forms never lower it under each other
@@ -390,14 +449,15 @@ hipError_t launch_fir_s8(const FirParams &p, const FirLongPlan &plan, int64_t su
     const LongGrid lf = long_grid(n_full, p.n_ch, 4);
     f.pairs_per_wave = lf.steps_per_wave + (lf.steps_per_wave & 1);
     const unsigned gxf = (unsigned)((n_full + f.pairs_per_wave - 1) / f.pairs_per_wave);
-    if ((e = hipFuncSetAttribute((const void *)fir_s8_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax)) != hipSuccess) { return e; }
-    hipLaunchKernelGGL((fir_s8_kernel<true, true>), dim3(gxf, lf.gy), dim3(512), lds, s, p, (const v4i *)d_frag, f);
+    auto kf = p.out_eb == 1 ? fir_s8_kernel<true, true, 1> : fir_s8_kernel<true, true, 2>;
+    if ((e = hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax)) != hipSuccess) { return e; }
+    hipLaunchKernelGGL(kf, dim3(gxf, lf.gy), dim3(512), lds, s, p, (const v4i *)d_frag, f);
     if ((e = hipGetLastError()) != hipSuccess || n_full == n_all) { return e; }
     a.s_begin = n_full;
   }
   const LongGrid lr = long_grid(n_all - a.s_begin, p.n_ch, 4);
   a.pairs_per_wave = lr.steps_per_wave;
-  auto kern = a.fast ? fir_s8_kernel<true, false> : fir_s8_kernel<false, false>;
+  auto kern = !a.fast ? fir_s8_kernel<false, false, 2> : (p.out_eb == 1 ? fir_s8_kernel<true, false, 1> : fir_s8_kernel<true, false, 2>);
   if ((e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax)) != hipSuccess) { return e; }
   hipLaunchKernelGGL(kern, dim3(lr.gx, lr.gy), dim3(512), lds, s, p, (const v4i *)d_frag, a);
   return hipGetLastError();

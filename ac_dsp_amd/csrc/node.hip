@@ -295,6 +295,7 @@ int32_t acdsp_node_fir_create(const acdsp_fir_desc_t *desc, int32_t n_devices, c
   });
   if (rc) { const std::string keep = acdsp_last_error(); free_node(h); return set_error(rc, keep.c_str()); }
   h->in_eb = acdsp_fir_in_elem_bytes((acdsp_fir_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES: run_host slices byte rows
+  h->out_eb = acdsp_fir_out_elem_bytes((acdsp_fir_t)h->shards[0].handle);  // 1 under ACDSP_FLAG_OUT_BYTES
   *out = h;
   return ACDSP_OK;
 }

@@ -38,8 +38,11 @@ def _alloc_out(fmt, n_ch, n, device):
     return torch.empty(shape, dtype=torch_dtype_for(fmt), device=device)
 
 
-def _alloc_out_host(fmt, n_ch, n):
-    """Host twin of _alloc_out: the C side writes n containers of acdsp_elem_bytes(W) bytes per row, 16 for formats wider than 64 bits."""
+def _alloc_out_host(fmt, n_ch, n, out_bytes=False):
+    """Host twin of _alloc_out: the C side writes n containers of acdsp_elem_bytes(W) bytes per row, 16 for formats wider than 64 bits;
+    1-byte containers under out_bytes (ACDSP_FLAG_OUT_BYTES)."""
+    if out_bytes:
+        return np.empty((n_ch, n), dtype=np.int8 if fmt.S else np.uint8)
     shape = (n_ch, n, 2) if is_wide(fmt) else (n_ch, n)
     return np.empty(shape, dtype=_np_dtype_for(fmt))
 
@@ -200,15 +203,18 @@ class Fir:
     """n_channels independent reference FIR objects (ac_fir_{const,load,prog}_coeffs) behind one handle."""
 
     def __init__(self, n_taps, ftype, fin, fcoeff, facc, fout, n_channels=1, kind="load", coeffs_per_channel=False,
-                 device=0, force_generic=False, in_bytes=False):
-        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
+                 device=0, force_generic=False, in_bytes=False, out_bytes=False):
+        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8
+        out_bytes (with in_bytes): OUT_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_OUT_BYTES): output rows are torch.int8 / torch.uint8"""
         self.fin, self.fcoeff, self.facc, self.fout = fin, fcoeff, facc, fout
         self.n_taps, self.n_channels, self.device = n_taps, n_channels, device
         self.coeffs_per_channel = bool(coeffs_per_channel)
         self.in_bytes = bool(in_bytes)
+        self.out_bytes = bool(out_bytes)
         d = FirDesc(KINDS[kind] if isinstance(kind, str) else kind, FTYPES[ftype] if isinstance(ftype, str) else ftype,
                     n_taps, n_channels, int(self.coeffs_per_channel), fin, fcoeff, facc, fout, device,
-                    (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0))
+                    (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0) |
+                    (_lib.FLAG_OUT_BYTES if out_bytes else 0))
         self._h = C.c_void_p()
         check(lib.acdsp_fir_create(C.byref(d), C.byref(self._h)))
 
@@ -224,6 +230,13 @@ class Fir:
         if self.in_bytes:
             return torch.int8 if self.fin.S else torch.uint8
         return torch_dtype_for(self.fin)
+
+    @property
+    def out_dtype(self):
+        """torch dtype of the output rows: int8 / uint8 containers under out_bytes, else the container of OUT_TYPE"""
+        if self.out_bytes:
+            return torch.int8 if self.fout.S else torch.uint8
+        return torch_dtype_for(self.fout)
 
     @property
     def path(self):
@@ -245,8 +258,8 @@ class Fir:
         assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         n = x.shape[1]
         if out is None:
-            out = _alloc_out(self.fout, self.n_channels, n, x.device)
-        assert out.dtype == torch_dtype_for(self.fout) and out.shape[1] >= n
+            out = torch.empty((self.n_channels, n), dtype=self.out_dtype, device=x.device) if self.out_bytes else _alloc_out(self.fout, self.n_channels, n, x.device)
+        assert out.dtype == self.out_dtype and out.shape[1] >= n
         check(lib.acdsp_fir_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), n, C.c_void_p(out.data_ptr()),
                                 _row_stride(out, self.fout), _stream_ptr(x)))
         return out
@@ -254,7 +267,7 @@ class Fir:
     def run_host(self, x):
         x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_in_dtype(self.fin, self.in_bytes))
         assert x.shape[0] == self.n_channels
-        y = _alloc_out_host(self.fout, self.n_channels, x.shape[1])
+        y = _alloc_out_host(self.fout, self.n_channels, x.shape[1], self.out_bytes)
         check(lib.acdsp_fir_run_host(self._h, x.ctypes.data_as(C.c_void_p), x.shape[1], y.ctypes.data_as(C.c_void_p)))
         return y
 
@@ -832,15 +845,25 @@ class _Node:
 class NodeFir(_Node):
     """A Fir bank sharded over `devices` (acdsp_node_fir_*): no collective, coefficients replicated (or sliced when per channel)."""
 
-    def __init__(self, n_taps, ftype, fin, fcoeff, facc, fout, n_channels, devices, kind="load", coeffs_per_channel=False, in_bytes=False):
+    def __init__(self, n_taps, ftype, fin, fcoeff, facc, fout, n_channels, devices, kind="load", coeffs_per_channel=False, in_bytes=False,
+                 out_bytes=False):
+        """in_bytes / out_bytes: as for Fir (ACDSP_FLAG_IN_BYTES, ACDSP_FLAG_OUT_BYTES)"""
         self.fin, self.fout, self.n_taps, self.n_channels = fin, fout, n_taps, n_channels
         self.coeffs_per_channel = bool(coeffs_per_channel)
         self.in_bytes = bool(in_bytes)
+        self.out_bytes = bool(out_bytes)
         d = FirDesc(KINDS[kind], FTYPES[ftype] if isinstance(ftype, str) else ftype, n_taps, n_channels, int(self.coeffs_per_channel),
-                    fin, fcoeff, facc, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
+                    fin, fcoeff, facc, fout, 0, (_lib.FLAG_IN_BYTES if in_bytes else 0) | (_lib.FLAG_OUT_BYTES if out_bytes else 0))
         self._h = C.c_void_p()
         check(lib.acdsp_node_fir_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
+
+    @property
+    def out_dtype(self):
+        """torch dtype of the output rows: int8 / uint8 containers under out_bytes, else the container of OUT_TYPE"""
+        if self.out_bytes:
+            return torch.int8 if self.fout.S else torch.uint8
+        return torch_dtype_for(self.fout)
 
     def set_coeffs(self, coeffs):
         c = np.ascontiguousarray(coeffs, dtype=np.int64)
@@ -852,16 +875,17 @@ class NodeFir(_Node):
         n = xs[0].shape[1]
         assert all(x.shape[1] == n for x in xs)
         if outs is None:
-            outs = self.alloc(self.fout, n)
+            outs = ([torch.empty((hi - lo, n), dtype=self.out_dtype, device=torch.device("cuda", d)) for (lo, hi), d in zip(self.slices, self.devices)]
+                    if self.out_bytes else self.alloc(self.fout, n))
         pin, sin = self._ptrs(xs, self.fin, (torch.int8 if self.fin.S else torch.uint8) if self.in_bytes else None)
-        pout, sout = self._ptrs(outs, self.fout)
+        pout, sout = self._ptrs(outs, self.fout, self.out_dtype if self.out_bytes else None)
         check(lib.acdsp_node_fir_run(self._h, pin, sin, n, pout, sout))
         return outs
 
     def run_host(self, x):
         x = np.ascontiguousarray(x, dtype=_np_in_dtype(self.fin, self.in_bytes))
         assert x.shape[0] == self.n_channels
-        y = _alloc_out_host(self.fout, self.n_channels, x.shape[1])
+        y = _alloc_out_host(self.fout, self.n_channels, x.shape[1], self.out_bytes)
         check(lib.acdsp_node_fir_run_host(self._h, x.ctypes.data_as(C.c_void_p), x.shape[1], y.ctypes.data_as(C.c_void_p)))
         return y
 

@@ -93,7 +93,7 @@ template <class T> inline T from_raw(int64_t r) {
 template <class T, bool WIDE = (T::width > 64)> struct container_io {
   static void store(const T &v, unsigned char *p, int eb) {
     const int64_t r = raw_of(v);
-    if (eb == 1) { p[0] = (unsigned char)r; }   // ACDSP_FLAG_IN_BYTES
+    if (eb == 1) { p[0] = (unsigned char)r; }   // ACDSP_FLAG_IN_BYTES / ACDSP_FLAG_OUT_BYTES
     else if (eb == 2) { int16_t t = (int16_t)r; memcpy(p, &t, 2); }
     else if (eb == 4) { int32_t t = (int32_t)r; memcpy(p, &t, 4); }
     else { memcpy(p, &r, 8); }
@@ -181,7 +181,8 @@ inline std::vector<unsigned char> state_of(H h, int64_t (*size)(H), int32_t (*ge
 template <class IN_TYPE, class OUT_TYPE, class COEFF_TYPE, class ACC_TYPE>
 class fir_engine {
 public:
-  // flags: ACDSP_FLAG_* of acdsp_fir_desc_t (ACDSP_FLAG_IN_BYTES: in_bytes() == 1, rows of 1-byte containers)
+  // flags: ACDSP_FLAG_* of acdsp_fir_desc_t (ACDSP_FLAG_IN_BYTES: in_bytes() == 1, rows of 1-byte containers; with it ACDSP_FLAG_OUT_BYTES:
+  // out_bytes() == 1, output rows of 1-byte containers)
   fir_engine(int kind, int ftype, int n_taps, int n_channels = 1, bool coeffs_per_channel = false, int device = -1, int flags = 0)
       : h_(0), kind_(kind), ftype_(ftype), n_taps_(n_taps), n_ch_(n_channels), per_ch_(coeffs_per_channel),
         device_(device < 0 ? default_device() : device), flags_(flags), head_(0), host_valid_(true), host_ahead_(false) {}
@@ -205,7 +206,7 @@ public:
 
   int n_channels() const { return n_ch_; }
   int in_bytes() const { return (flags_ & ACDSP_FLAG_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
-  int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
+  int out_bytes() const { return (flags_ & ACDSP_FLAG_OUT_BYTES) ? 1 : acdsp_elem_bytes(OUT_TYPE::width); }
   // the raw engine handle (state blobs, kernel statistics ...): the device becomes the authority on the filter state
   acdsp_fir_t handle() { ensure(); to_device(); host_valid_ = false; return h_; }
 

@@ -72,6 +72,15 @@ enum {
  * refusal); ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its input stream is the thin one) and either stage of
  * acdsp_ddc_create / acdsp_node_ddc_create: ACDSP_EUNSUPPORTED, all before any device use.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_IN_BYTES 2
+/* acdsp_fir_desc_t::flags only, and only together with ACDSP_FLAG_IN_BYTES.  OUT_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE
+ * containers: the rows acdsp_fir_run / acdsp_node_fir_run write and the output of acdsp_fir_run_host / acdsp_node_fir_run_host hold int8_t /
+ * uint8_t raw words (acdsp_fir_out_elem_bytes() == 1), so a flagged FIR's output row feeds a second handle under ACDSP_FLAG_IN_BYTES as it
+ * is.  out_stride stays in elements; rows take 16-byte stores where d_out % 16 == 0 and out_stride % 16 == 0, element stores elsewhere.  The
+ * handle resolves exactly as under ACDSP_FLAG_IN_BYTES alone (path, acdsp_fir_mfma_issued); the state blob holds input history only and moves
+ * both ways between handles with and without this flag.  out.W > 8: ACDSP_EINVAL.  The flag without ACDSP_FLAG_IN_BYTES (the int16-sample
+ * kernels have no 1-byte output tile yet), and the flag on any other family's descriptor -- acdsp_{cic,polydec,polyintr,intgdump,mvavg}_create,
+ * either stage of acdsp_ddc_create: ACDSP_EUNSUPPORTED, all before any device use.  INTEGRATION.md "Byte samples". */
+#define ACDSP_FLAG_OUT_BYTES 4
 
 /* which kernel family a FIR handle resolved to (acdsp_fir_path) */
 enum { ACDSP_PATH_GENERIC = 0, ACDSP_PATH_LOSSLESS64 = 1, ACDSP_PATH_MFMA_I8 = 2, ACDSP_PATH_MFMA_GEN = 3,
@@ -273,6 +282,8 @@ int32_t acdsp_fir_kernel_stats(acdsp_fir_t h, int32_t last_k, float *avg_ms, flo
 int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples);
 /* bytes of one INPUT container of the handle: 1 under ACDSP_FLAG_IN_BYTES, else acdsp_elem_bytes(in.W) */
 int32_t acdsp_fir_in_elem_bytes(acdsp_fir_t h);
+/* bytes of one OUTPUT container of the handle: 1 under ACDSP_FLAG_OUT_BYTES, else acdsp_elem_bytes(out.W) */
+int32_t acdsp_fir_out_elem_bytes(acdsp_fir_t h);
 
 /* ---- CIC ---- */
 int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out);
