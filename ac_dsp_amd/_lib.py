@@ -14,8 +14,8 @@ KINDS = {"const": 0, "load": 1, "prog": 2, "reg_share": 3}
 PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 5: "mfma_lossy", 8: "mfma_long", 9: "mfma_s8"}   # (6 = ACDSP_PATH_CIC_2STAGE: Cic.path only)
 KCLASSES = {**PATHS, 6: "lossy16", 7: "satacc16"}
 FLAG_FORCE_GENERIC = 1
-FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator), PolyDec / NodePolyDec, IntgDump / NodeIntgDump: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
-FLAG_OUT_BYTES = 4  # Fir / NodeFir together with FLAG_IN_BYTES: OUT_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_OUT_BYTES)
+FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator), PolyDec / NodePolyDec, IntgDump / NodeIntgDump, MvAvg / NodeMvAvg: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
+FLAG_OUT_BYTES = 4  # Fir / NodeFir, MvAvg / NodeMvAvg together with FLAG_IN_BYTES: OUT_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_OUT_BYTES)
 
 
 class AcdspError(RuntimeError):
@@ -212,6 +212,9 @@ SYMBOLS = {
     "acdsp_mvavg_set_coeffs": (_i32, [_vp, C.POINTER(_i64)]),
     "acdsp_mvavg_out_per_frame": (_i64, [_vp, _i64]),
     "acdsp_mvavg_path": (_i32, [_vp]),
+    "acdsp_mvavg_in_elem_bytes": (_i32, [_vp]),
+    "acdsp_mvavg_out_elem_bytes": (_i32, [_vp]),
+    "acdsp_mvavg_frags_host": (_i32, [C.POINTER(_i64), _i32, _i32, _i32, C.POINTER(C.c_uint32), C.POINTER(_i64), C.POINTER(_i32)]),
     "acdsp_mvavg_run": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, C.POINTER(_i64), _vp]),
     "acdsp_mvavg_run_host": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, C.POINTER(_i64)]),
     "acdsp_fir_state_size": (_i64, [_vp]),

@@ -303,6 +303,7 @@ struct acdsp_mvavg {
   DevBuf d_frag;                // matrix-core form of the streaming kernel: fragments of the coefficient set (mv_avg_build_frags)
   int frag_nb = 0;
   int64_t frag_csum = 0;
+  int frag_gran = 8, frag_hi = 0;   // halo granularity of the fragments (16 under ACDSP_FLAG_IN_BYTES: mv_avg_s8_kernel's geometry); a high digit exists
   int last_path = 0;
   Staging st;
 };
@@ -324,12 +325,16 @@ int32_t acdsp_mvavg_create(const acdsp_mvavg_desc_t *desc, acdsp_mvavg_t *out) {
   // 128-bit exact intermediates: ACC x COEFF product aligned with the accumulator
   const int fc = desc->coeff.W - desc->coeff.I;
   if (desc->acc.W + desc->coeff.W + 2 + (fc < 0 ? -fc : 0) > 125) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: type combination needs more than 128-bit intermediates"); }
-  if (desc->flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
+  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0, out_bytes = (desc->flags & ACDSP_FLAG_OUT_BYTES) != 0;
+  if (in_bytes && desc->in.W > 8) { return fail(ACDSP_EINVAL, "mv_avg: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", desc->in.W); }
+  if (out_bytes && !in_bytes) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: ACDSP_FLAG_OUT_BYTES needs ACDSP_FLAG_IN_BYTES (1-byte output rows exist on the byte-sample kernels only)"); }
+  if (out_bytes && desc->out.W > 8) { return fail(ACDSP_EINVAL, "mv_avg: ACDSP_FLAG_OUT_BYTES: OUT_TYPE W=%d does not fit a 1-byte container", desc->out.W); }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_mvavg> h(new acdsp_mvavg());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
-  h->in_eb = elem_bytes(desc->in.W);
-  h->out_eb = elem_bytes(desc->out.W);
+  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
+  h->out_eb = out_bytes ? 1 : elem_bytes(desc->out.W);
+  h->frag_gran = in_bytes ? 16 : 8;
   if ((rc = h->d_coeffs.alloc((size_t)desc->taps * sizeof(int64_t))) || (rc = h->d_frag.alloc((size_t)kMvAvgFragWords * sizeof(uint32_t)))) { return rc; }
   *out = h.release();
   return ACDSP_OK;
@@ -368,7 +373,7 @@ int32_t acdsp_mvavg_set_coeffs(acdsp_mvavg_t h, const int64_t *coeffs) {
   h->h_coeffs.assign(coeffs, coeffs + h->d.taps);
   {
     std::vector<uint32_t> fr((size_t)kMvAvgFragWords, 0u);
-    h->frag_nb = mv_avg_build_frags(coeffs, h->d.taps, h->d.win_mode, fr.data(), &h->frag_csum);
+    h->frag_nb = mv_avg_build_frags(coeffs, h->d.taps, h->d.win_mode, h->frag_gran, fr.data(), &h->frag_csum, &h->frag_hi);
     if (h->frag_nb > 0 && (rc = h->d_frag.upload(fr.data(), fr.size() * sizeof(uint32_t)))) { return rc; }
   }
   h->coeffs_set = true;
@@ -376,6 +381,21 @@ int32_t acdsp_mvavg_set_coeffs(acdsp_mvavg_t h, const int64_t *coeffs) {
 }
 
 int32_t acdsp_mvavg_path(acdsp_mvavg_t h) { return h ? h->last_path : -1; }
+int32_t acdsp_mvavg_in_elem_bytes(acdsp_mvavg_t h) { return h ? h->in_eb : -1; }
+int32_t acdsp_mvavg_out_elem_bytes(acdsp_mvavg_t h) { return h ? h->out_eb : -1; }
+
+// Host only (no device, no handle): the Toeplitz fragments acdsp_mvavg_set_coeffs would upload for this coefficient set -- in_bytes != 0: in the
+// geometry of the byte-plane kernel -- into out[ACDSP_MVAVG_FRAG_WORDS].  Returns the K blocks (0: the set stays off the matrix cores).
+int32_t acdsp_mvavg_frags_host(const int64_t *coeffs, int32_t taps, int32_t win_mode, int32_t in_bytes, uint32_t *out, int64_t *csum, int32_t *hi_any) {
+  if (!coeffs || !out || !csum || !hi_any || taps < 1 || !(taps & 1) || win_mode < ACDSP_WIN_PLAIN || win_mode > ACDSP_WIN_CLIP) { (void)fail(ACDSP_EINVAL, "mvavg_frags_host: bad arguments"); return -1; }
+  static_assert(ACDSP_MVAVG_FRAG_WORDS == kMvAvgFragWords, "the header's fragment size");
+  memset(out, 0, (size_t)kMvAvgFragWords * sizeof(uint32_t));
+  *csum = 0; *hi_any = 0;
+  int hi = 0;
+  const int nb = mv_avg_build_frags(coeffs, taps, win_mode, in_bytes ? 16 : 8, out, csum, &hi);
+  *hi_any = hi;
+  return nb;
+}
 
 int64_t acdsp_mvavg_out_per_frame(acdsp_mvavg_t h, int64_t n_sample) {
   if (!h || n_sample < 1 || n_sample > h->d.max_sample) { return -1; }
@@ -434,6 +454,7 @@ int32_t acdsp_mvavg_run(acdsp_mvavg_t h, const void *d_in, int64_t in_stride, in
   p.n_sample = n_sample; p.n_frames = n_frames; p.out_per_frame = opf; p.in_stride = in_stride; p.out_stride = out_stride;
   p.x = d_in; p.y = d_out; p.coeffs = h->d_coeffs.get<int64_t>(); p.h_coeffs = h->h_coeffs.data();
   p.frag = h->frag_nb > 0 ? h->d_frag.get<uint32_t>() : nullptr; p.frag_nb = h->frag_nb; p.frag_csum = h->frag_csum;
+  p.frag_gran = h->frag_gran; p.frag_hi = h->frag_hi;
   hipError_t e = launch_mv_avg(p, (hipStream_t)stream, &h->last_path);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "mv_avg kernel launch failed: %s", hipGetErrorString(e)); }
   return ACDSP_OK;

@@ -828,20 +828,25 @@ static bool try_stream(const MvAvgParams &p, hipStream_t s, bool *mfma) {
   return true;
 }
 
-// Toeplitz fragments of the matrix-core form (mv_avg_stream_kernel, MF instantiations).  Returns the K blocks (1 / 2; 0: the coefficient set
-// or the window does not fit) and fills out[((m nb + b) 2 + plane) 64 + lane][4 dwords]: lane (row i = lane & 15, kg = lane >> 4) holds
-// A[i][16 kg .. 16 kg + 15] of K block b, A[i][kk] = digit_plane(c[64 b + kk - sigma_m(i) - off]), sigma_m(i) = 8 (i >> 2) + (i & 3) + 4 m;
-// c = 256 ch + cl with both digits signed bytes (balanced: cl = int8(c & 255)), so that every product is a signed i8 x i8 one.
-int mv_avg_build_frags(const int64_t *c, int taps, int win_mode, uint32_t *out, int64_t *csum) {
-  const int h = taps / 2, hb = win_mode == 0 ? 0 : 8 * ((h + 7) / 8), off = win_mode == 0 ? 0 : hb - h;
+// Toeplitz fragments of the matrix-core forms (mv_avg_stream_kernel, MF instantiations: gran = 8 samples; mv_avg_s8_kernel: gran = 16, the
+// samples its 16-byte tile loads are aligned to).  The window's half length is rounded up to `gran` in front of a tile (hb; 0 under AC_WIN) and
+// the window starts off = hb - TAPS / 2 samples into the image.  Returns the K blocks (1 / 2; 0: the coefficient set or the window does not
+// fit) and fills out[((m nb + b) 2 + plane) 64 + lane][4 dwords]: lane (row i = lane & 15, kg = lane >> 4) holds A[i][16 kg .. 16 kg + 15] of
+// K block b, A[i][kk] = digit_plane(c[64 b + kk - sigma_m(i) - off]), sigma_m(i) = 8 (i >> 2) + (i & 3) + 4 m; c = 256 ch + cl with both digits
+// signed bytes (balanced: cl = int8(c & 255)), so that every product is a signed i8 x i8 one.  *hi_any: some ch is not 0 (plane 1 is needed).
+int mv_avg_build_frags(const int64_t *c, int taps, int win_mode, int gran, uint32_t *out, int64_t *csum, int *hi_any) {
+  const int h = taps / 2, hb = win_mode == 0 ? 0 : gran * ((h + gran - 1) / gran), off = win_mode == 0 ? 0 : hb - h;
   if (taps > 65 || 31 + off + taps - 1 >= 128) { return 0; }
   const int nb = (31 + off + taps - 1 < 64) ? 1 : 2;
   int64_t sum = 0;
+  int hi = 0;
   for (int t = 0; t < taps; t++) {
     if (c[t] < -32768 || c[t] > 32639) { return 0; }   // the balanced high digit of 32640 .. 32767 is 128
     sum += c[t];
+    hi |= (c[t] < -128 || c[t] > 127) ? 1 : 0;
   }
   *csum = sum;
+  *hi_any = hi;
   for (int m = 0; m < 2; m++) {
     for (int b = 0; b < nb; b++) {
       for (int lane = 0; lane < 64; lane++) {
@@ -867,6 +872,7 @@ int mv_avg_build_frags(const int64_t *c, int taps, int win_mode, uint32_t *out, 
 hipError_t launch_mv_avg(const MvAvgParams &p, hipStream_t s, int *path) {
   if (p.out_per_frame <= 0 || p.n_frames <= 0) { return hipSuccess; }
   bool mfma = false;
+  if (p.in_eb == 1 && mv_avg_try_s8(p, s)) { *path = 5; return hipGetLastError(); }   // byte rows outside its class: the container-agnostic kernels below
   if (try_stream(p, s, &mfma)) { *path = mfma ? 4 : 2; return hipGetLastError(); }
   if (try_w32(p, s)) { *path = 3; return hipGetLastError(); }
   *path = p.fast ? 1 : 0;

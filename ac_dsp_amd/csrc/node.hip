@@ -519,6 +519,8 @@ int32_t acdsp_node_mvavg_create(const acdsp_mvavg_desc_t *desc, int32_t n_device
   if (rc) { return rc; }
   h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   if ((rc = create_shards<acdsp_mvavg_desc_t, acdsp_mvavg_t>(h, *desc, &acdsp_mvavg_desc_t::n_objects, acdsp_mvavg_create))) { return rc; }
+  h->in_eb = acdsp_mvavg_in_elem_bytes((acdsp_mvavg_t)h->shards[0].handle);     // 1 under ACDSP_FLAG_IN_BYTES
+  h->out_eb = acdsp_mvavg_out_elem_bytes((acdsp_mvavg_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_OUT_BYTES
   *out = h;
   return ACDSP_OK;
 }

@@ -724,16 +724,34 @@ class IntgDump:
 WIN_MODES = {"WIN": 0, "MIRROR": 1, "CLIP": 2}   # AC_WIN / AC_MIRROR / AC_CLIP
 
 
+def _mvavg_flags(force_generic, in_bytes, out_bytes):
+    return (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0) | (_lib.FLAG_OUT_BYTES if out_bytes else 0)
+
+
+def _byte_dtype(fmt, as_bytes):
+    """torch dtype of a row of `fmt` words: int8 / uint8 by signedness in 1-byte containers, else the format's own container"""
+    if as_bytes:
+        return torch.int8 if fmt.S else torch.uint8
+    return torch_dtype_for(fmt)
+
+
 class MvAvg:
     """n_objects independent ac_mv_avg<MAX_SAMPLE, TAPS, WIN_TYPE, ...> objects (C ABI acdsp_mvavg_*): rows hold n_frames
     frames of n_sample inputs back to back; run() is one run() call of every object."""
 
-    def __init__(self, max_sample, taps, win_mode, fin, fcoeff, facc, fout, n_objects=1, device=0, force_generic=False):
+    def __init__(self, max_sample, taps, win_mode, fin, fcoeff, facc, fout, n_objects=1, device=0, force_generic=False, in_bytes=False,
+                 out_bytes=False):
+        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8
+        out_bytes (with in_bytes): OUT_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_OUT_BYTES): output rows are torch.int8 / torch.uint8"""
         self.fin, self.fout, self.n_objects, self.taps = fin, fout, n_objects, taps
+        self.in_bytes, self.out_bytes = bool(in_bytes), bool(out_bytes)
         d = MvAvgDesc(max_sample, taps, WIN_MODES[win_mode] if isinstance(win_mode, str) else win_mode, n_objects, fin, fcoeff, facc,
-                      fout, device, _lib.FLAG_FORCE_GENERIC if force_generic else 0)
+                      fout, device, _mvavg_flags(force_generic, in_bytes, out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_mvavg_create(C.byref(d), C.byref(self._h)))
+
+    in_dtype = property(lambda self: _byte_dtype(self.fin, self.in_bytes), doc="torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE")
+    out_dtype = property(lambda self: _byte_dtype(self.fout, self.out_bytes), doc="torch dtype of the output rows: int8 / uint8 containers under out_bytes, else the container of OUT_TYPE")
 
     def set_coeffs(self, coeffs):
         c = np.ascontiguousarray(coeffs, dtype=np.int64)
@@ -746,19 +764,31 @@ class MvAvg:
     @property
     def path(self):
         """kernel family of the last run()"""
-        return {0: "exact_order", 1: "int64_sums", 2: "stream", 3: "stream32", 4: "stream_mfma"}[lib.acdsp_mvavg_path(self._h)]
+        return {0: "exact_order", 1: "int64_sums", 2: "stream", 3: "stream32", 4: "stream_mfma", 5: "stream_s8"}[lib.acdsp_mvavg_path(self._h)]
 
     def run(self, x, n_sample, out=None):
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_objects and x.stride(1) == 1 and x.shape[1] % n_sample == 0
-        assert x.dtype == torch_dtype_for(self.fin), (x.dtype, self.fin)
+        assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         n_frames = x.shape[1] // n_sample
         no = max(self.out_per_frame(n_sample), 0) * n_frames
         if out is None:
-            out = torch.empty((self.n_objects, max(no, 1)), dtype=torch_dtype_for(self.fout), device=x.device)
+            out = torch.empty((self.n_objects, max(no, 1)), dtype=self.out_dtype, device=x.device)
+        assert out.element_size() == torch.empty((), dtype=self.out_dtype).element_size(), (out.dtype, self.fout)
         n_out = C.c_int64()
         check(lib.acdsp_mvavg_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), n_sample, n_frames, C.c_void_p(out.data_ptr()), out.stride(0),
                                   C.byref(n_out), _stream_ptr(x)))
         return out[:, :n_out.value]
+
+    def run_host(self, x, n_sample):
+        """run() on host rows [n_objects][n_frames * n_sample] (numpy; int8 / uint8 under in_bytes) -> host rows of the output containers"""
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_in_dtype(self.fin, self.in_bytes))
+        assert x.shape[0] == self.n_objects and x.shape[1] % n_sample == 0
+        n_frames = x.shape[1] // n_sample
+        no = max(self.out_per_frame(n_sample), 0) * n_frames
+        y = _alloc_out_host(self.fout, self.n_objects, max(no, 1), self.out_bytes)
+        n_out = C.c_int64()
+        check(lib.acdsp_mvavg_run_host(self._h, x.ctypes.data_as(C.c_void_p), n_sample, n_frames, y.ctypes.data_as(C.c_void_p), y.shape[1], C.byref(n_out)))
+        return y[:, :n_out.value]
 
     def clone(self):
         """Deep copy, stream state included; the two objects are independent afterwards (acdsp_mvavg_clone)."""
@@ -1044,9 +1074,12 @@ class NodeIntgDump(_Node):
 class NodeMvAvg(_Node):
     """A MvAvg bank (rows = objects) sharded over `devices` (acdsp_node_mvavg_*)."""
 
-    def __init__(self, max_sample, taps, win_mode, fin, fcoeff, facc, fout, n_objects, devices):
+    def __init__(self, max_sample, taps, win_mode, fin, fcoeff, facc, fout, n_objects, devices, in_bytes=False, out_bytes=False):
+        """in_bytes / out_bytes: as for MvAvg (ACDSP_FLAG_IN_BYTES, ACDSP_FLAG_OUT_BYTES)"""
         self.fin, self.fout, self.n_objects, self.taps = fin, fout, n_objects, taps
-        d = MvAvgDesc(max_sample, taps, WIN_MODES[win_mode] if isinstance(win_mode, str) else win_mode, n_objects, fin, fcoeff, facc, fout, 0, 0)
+        self.in_bytes, self.out_bytes = bool(in_bytes), bool(out_bytes)
+        d = MvAvgDesc(max_sample, taps, WIN_MODES[win_mode] if isinstance(win_mode, str) else win_mode, n_objects, fin, fcoeff, facc, fout, 0,
+                      _mvavg_flags(False, in_bytes, out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_node_mvavg_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -1056,13 +1089,17 @@ class NodeMvAvg(_Node):
         assert c.shape == (self.taps,)
         check(lib.acdsp_node_mvavg_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
 
+    in_dtype = MvAvg.in_dtype
+    out_dtype = MvAvg.out_dtype
+
     def run(self, xs, n_sample, outs=None):
         n = xs[0].shape[1]
         assert n % n_sample == 0
         if outs is None:
-            outs = self.alloc(self.fout, n)
-        pin, sin = self._ptrs(xs, self.fin)
-        pout, sout = self._ptrs(outs, self.fout)
+            outs = ([torch.empty((hi - lo, n), dtype=self.out_dtype, device=torch.device("cuda", d)) for (lo, hi), d in zip(self.slices, self.devices)]
+                    if self.out_bytes else self.alloc(self.fout, n))
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
+        pout, sout = self._ptrs(outs, self.fout, self.out_dtype)
         n_out = C.c_int64()
         check(lib.acdsp_node_mvavg_run(self._h, pin, sin, n_sample, n // n_sample, pout, sout, C.byref(n_out)))
         return [o[:, :n_out.value] for o in outs]

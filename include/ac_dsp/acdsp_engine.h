@@ -653,12 +653,14 @@ private:
 template <class IN_TYPE, class COEFF_TYPE, class ACC_TYPE, class OUT_TYPE>
 class mvavg_engine {
 public:
+  // flags: ACDSP_FLAG_* of acdsp_mvavg_desc_t (ACDSP_FLAG_IN_BYTES: in_bytes() == 1, rows of 1-byte containers; with it ACDSP_FLAG_OUT_BYTES:
+  // out_bytes() == 1, output rows of 1-byte containers)
   mvavg_engine(int max_sample, int taps, int win_mode, int n_objects = 1, int device = -1, int flags = 0)
       : max_sample_(max_sample), taps_(taps), win_mode_(win_mode), n_obj_(n_objects), device_(device < 0 ? default_device() : device), flags_(flags) {}
 
   int n_objects() const { return n_obj_; }
-  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
-  int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
+  int in_bytes() const { return (flags_ & ACDSP_FLAG_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
+  int out_bytes() const { return (flags_ & ACDSP_FLAG_OUT_BYTES) ? 1 : acdsp_elem_bytes(OUT_TYPE::width); }
   acdsp_mvavg_t handle() { ensure(); return h_.get(); }
   // raw COEFF_TYPE words [taps]; uploaded only when they changed
   void set_coeffs_raw(const std::vector<int64_t> &c) {

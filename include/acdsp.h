@@ -61,25 +61,29 @@ enum {
 
 /* flags */
 #define ACDSP_FLAG_FORCE_GENERIC 1 /* never pick the MFMA / fast kernels (parity tests) */
-/* acdsp_fir_desc_t::flags, acdsp_polydec_desc_t::flags, acdsp_intgdump_desc_t::flags, and acdsp_cic_desc_t::flags of a decimator
- * (interp == 0).  IN_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE containers: the caller's input rows, the handle's history and
- * the FIR / CIC / poly_dec state blob hold int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() / acdsp_cic_in_elem_bytes() /
- * acdsp_polydec_in_elem_bytes() / acdsp_intgdump_in_elem_bytes() == 1; acdsp_elem_bytes() is not asked for the input).  A flagged ac_poly_dec
- * handle resolves as an unflagged one does: ACDSP_PATH_MFMA_GEN on one sample plane where the ring / window kernels plan the shape,
- * ACDSP_PATH_MFMA_S8 (polydec_s8.hip) on long prototypes, the exact-order kernel elsewhere.  A flagged ac_intg_dump handle keeps no samples: its
- * state blob (the ACC words of temp[]) is that of an unflagged handle and moves both ways; acdsp_intgdump_path below names its kernels.
- * in_stride stays in elements; the output containers are unchanged.  W > 8: ACDSP_EINVAL (every family, ac_intg_dump included -- its only
- * refusal); ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its input stream is the thin one) and either stage of
+/* acdsp_fir_desc_t::flags, acdsp_polydec_desc_t::flags, acdsp_intgdump_desc_t::flags, acdsp_mvavg_desc_t::flags, and acdsp_cic_desc_t::flags
+ * of a decimator (interp == 0).  IN_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE containers: the caller's input rows, the
+ * handle's history and the FIR / CIC / poly_dec state blob hold int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() /
+ * acdsp_cic_in_elem_bytes() / acdsp_polydec_in_elem_bytes() / acdsp_intgdump_in_elem_bytes() / acdsp_mvavg_in_elem_bytes() == 1;
+ * acdsp_elem_bytes() is not asked for the input).  A flagged ac_poly_dec handle resolves as an unflagged one does: ACDSP_PATH_MFMA_GEN on one
+ * sample plane where the ring / window kernels plan the shape, ACDSP_PATH_MFMA_S8 (polydec_s8.hip) on long prototypes, the exact-order kernel
+ * elsewhere.  A flagged ac_intg_dump handle keeps no samples: its state blob (the ACC words of temp[]) is that of an unflagged handle and
+ * moves both ways; acdsp_intgdump_path below names its kernels.  A flagged ac_mv_avg handle has no state at all; acdsp_mvavg_path below names
+ * its kernels (5, the byte-plane streaming kernel, or the container-agnostic 0 / 1).  in_stride stays in elements; the output containers are
+ * unchanged unless ACDSP_FLAG_OUT_BYTES is set as well.  W > 8: ACDSP_EINVAL (every family; the only refusal of ac_intg_dump and ac_mv_avg);
+ * ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its input stream is the thin one) and either stage of
  * acdsp_ddc_create / acdsp_node_ddc_create: ACDSP_EUNSUPPORTED, all before any device use.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_IN_BYTES 2
-/* acdsp_fir_desc_t::flags only, and only together with ACDSP_FLAG_IN_BYTES.  OUT_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE
- * containers: the rows acdsp_fir_run / acdsp_node_fir_run write and the output of acdsp_fir_run_host / acdsp_node_fir_run_host hold int8_t /
- * uint8_t raw words (acdsp_fir_out_elem_bytes() == 1), so a flagged FIR's output row feeds a second handle under ACDSP_FLAG_IN_BYTES as it
- * is.  out_stride stays in elements; rows take 16-byte stores where d_out % 16 == 0 and out_stride % 16 == 0, element stores elsewhere.  The
- * handle resolves exactly as under ACDSP_FLAG_IN_BYTES alone (path, acdsp_fir_mfma_issued); the state blob holds input history only and moves
- * both ways between handles with and without this flag.  out.W > 8: ACDSP_EINVAL.  The flag without ACDSP_FLAG_IN_BYTES (the int16-sample
- * kernels have no 1-byte output tile yet), and the flag on any other family's descriptor -- acdsp_{cic,polydec,polyintr,intgdump,mvavg}_create,
- * either stage of acdsp_ddc_create: ACDSP_EUNSUPPORTED, all before any device use.  INTEGRATION.md "Byte samples". */
+/* acdsp_fir_desc_t::flags and acdsp_mvavg_desc_t::flags, and only together with ACDSP_FLAG_IN_BYTES.  OUT_TYPE has W <= 8 (signed or
+ * unsigned) and travels in 1-BYTE containers: the rows acdsp_fir_run / acdsp_node_fir_run / acdsp_mvavg_run / acdsp_node_mvavg_run write and
+ * the output of the run_host calls hold int8_t / uint8_t raw words (acdsp_fir_out_elem_bytes() / acdsp_mvavg_out_elem_bytes() == 1), so a
+ * flagged handle's output row feeds a second handle under ACDSP_FLAG_IN_BYTES as it is (mv_avg -> FIR -> CIC decimator without a narrowing
+ * pass).  out_stride stays in elements.  FIR rows take 16-byte stores where d_out % 16 == 0 and out_stride % 16 == 0, mv_avg rows 8-byte
+ * stores where d_out, out_stride and the outputs per frame are multiples of 8; element stores elsewhere.  The handle resolves exactly as under
+ * ACDSP_FLAG_IN_BYTES alone (path, acdsp_fir_mfma_issued); the FIR state blob holds input history only and moves both ways between handles
+ * with and without this flag.  Refusals, in this order and all before any device use: the flag without ACDSP_FLAG_IN_BYTES (the int16-sample
+ * kernels have no 1-byte output tile) and the flag on any other family's descriptor -- acdsp_{cic,polydec,polyintr,intgdump}_create, either
+ * stage of acdsp_ddc_create: ACDSP_EUNSUPPORTED; then out.W > 8: ACDSP_EINVAL.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_OUT_BYTES 4
 
 /* which kernel family a FIR handle resolved to (acdsp_fir_path) */
@@ -414,7 +418,25 @@ int32_t acdsp_mvavg_destroy(acdsp_mvavg_t h);
 int32_t acdsp_mvavg_clone(acdsp_mvavg_t h, acdsp_mvavg_t *out);           /* descriptor and bound coefficients (there is no stream state): "clone" below */
 int32_t acdsp_mvavg_set_coeffs(acdsp_mvavg_t h, const int64_t *coeffs);   /* raw COEFF_TYPE words [TAPS] */
 int64_t acdsp_mvavg_out_per_frame(acdsp_mvavg_t h, int64_t n_sample);     /* -1: n_sample outside 1..MAX_SAMPLE */
-int32_t acdsp_mvavg_path(acdsp_mvavg_t h);   /* kernel family of the last run(): 0 exact per-tap order, 1 order-free int64 sums, 2 streaming (16-bit samples, int32 sums), 3 sliding window on 32-bit samples (int64 sums), 4 streaming with the window sums on the matrix cores (17 taps and more) */
+/* kernel family of the last run(): 0 exact per-tap order, 1 order-free int64 sums, 2 streaming (16-bit samples, int32 sums), 3 sliding window
+ * on 32-bit samples (int64 sums), 4 streaming with the window sums on the matrix cores (16-bit samples, 17 taps and more), 5 byte-plane
+ * streaming kernel (mv_avg_s8.hip).  A handle without ACDSP_FLAG_IN_BYTES never reports 5; a flagged one reports 5, 1 or 0 only: 5 for 1 .. 65
+ * taps of the linear class (exact cast of a sample to a wrapping or sat-free AC_TRN / AC_RND ACC_TYPE with acc.F - in.F >= coeff.F >= 0,
+ * coefficients <= 32639 with sum |c| <= 32767, AC_TRN / AC_RND into AC_WRAP / AC_SAT outputs) on frames of n_sample >= TAPS, n_sample % 16 ==
+ * 0, with d_in % 16 == 0 and in_stride % 16 == 0; elsewhere -- the per-tap class acc.F - in.F < coeff.F, longer windows, accumulators that
+ * can saturate, other frame lengths and alignments, ACDSP_FLAG_FORCE_GENERIC -- the container-agnostic kernels 1 / 0 (exact, and slow). */
+int32_t acdsp_mvavg_path(acdsp_mvavg_t h);
+/* bytes of one INPUT / OUTPUT container of the handle: 1 under ACDSP_FLAG_IN_BYTES / ACDSP_FLAG_OUT_BYTES, else acdsp_elem_bytes(in.W) /
+ * acdsp_elem_bytes(out.W) */
+int32_t acdsp_mvavg_in_elem_bytes(acdsp_mvavg_t h);
+int32_t acdsp_mvavg_out_elem_bytes(acdsp_mvavg_t h);
+/* Host only -- no device, no handle: the matrix-core fragments acdsp_mvavg_set_coeffs builds for a coefficient set, for tests of the digit
+ * split and the Toeplitz indexing.  out[ACDSP_MVAVG_FRAG_WORDS] is laid out [row order m (2)][K block b (nb)][digit plane (2)][lane (64)][4
+ * dwords]: lane (i = lane & 15, kg = lane >> 4) holds A[i][16 kg .. 16 kg + 15] of K block b, A[i][kk] = digit(c[64 b + kk - s - off]) with
+ * s = 8 (i >> 2) + (i & 3) + 4 m, off = hb - TAPS / 2, hb = TAPS / 2 rounded up to 8 (in_bytes != 0: to 16; 0 under ACDSP_WIN_PLAIN).
+ * Returns nb (1 / 2; 0: the set or the window does not fit; -1: bad arguments); *csum = sum of the coefficients, *hi_any = a high digit exists. */
+#define ACDSP_MVAVG_FRAG_WORDS 2048
+int32_t acdsp_mvavg_frags_host(const int64_t *coeffs, int32_t taps, int32_t win_mode, int32_t in_bytes, uint32_t *out, int64_t *csum, int32_t *hi_any);
 int32_t acdsp_mvavg_run(acdsp_mvavg_t h, const void *d_in, int64_t in_stride, int64_t n_sample, int64_t n_frames, void *d_out,
                         int64_t out_stride, int64_t *n_out, void *stream);
 int32_t acdsp_mvavg_run_host(acdsp_mvavg_t h, const void *h_in, int64_t n_sample, int64_t n_frames, void *h_out, int64_t out_cap,
