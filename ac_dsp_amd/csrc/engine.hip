@@ -402,42 +402,23 @@ int64_t acdsp_fir_state_size(acdsp_fir_t h) { return h ? (int64_t)(sizeof(StateH
 int32_t acdsp_fir_state_get(acdsp_fir_t h, void *buf, uint64_t cap_bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
   const StateHdr s = fir_state_hdr(h);
-  const uint64_t pay = state_payload(s);
-  if (cap_bytes < sizeof s + pay) { return fail(ACDSP_EINVAL, "fir_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay)); }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous: the state of the last call must have landed
-  if (h->rt_hybrid && !h->rt_valid && (rc = fir_rt_from_hist(h))) { return rc; }
-  memcpy(buf, &s, sizeof s);
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->use_rt ? (const void *)fir_rt_cur(h) : h->hist.cur(), pay, hipMemcpyDeviceToHost));
-  return ACDSP_OK;
+  StatePart part = {h->hist.cur(), state_payload(s)};
+  return state_blob_get("fir", h->d.device, s, &part, 1, buf, cap_bytes, [&] {
+    const int rc = h->rt_hybrid && !h->rt_valid ? fir_rt_from_hist(h) : (int)ACDSP_OK;
+    if (h->use_rt) { part.dev = fir_rt_cur(h); }
+    return rc;
+  });
 }
 
 int32_t acdsp_fir_state_set(acdsp_fir_t h, const void *buf, uint64_t bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
-  const StateHdr mine = fir_state_hdr(h);
+  // filter memory: n_taps - 1 samples (the handle's length is that rounded up for the kernels' windows, and a padded MFMA plan reaches a block
+  // further back).  reg_trans[] (kind 2) holds partial sums, not samples: no other length is this filter's state
   StateHdr s;
-  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "fir_state_set: blob shorter than its header"); }
-  memcpy(&s, buf, sizeof s);
-  // An input-history blob (kind 1) of another history LENGTH is still this filter's state as long as it covers the taps: the handle's
-  // length is n_taps - 1 rounded up for the kernels' windows (and changed between builds: a padded MFMA plan reaches a block further
-  // back), the samples beyond n_taps - 1 only ever meet zero coefficients.  The newest min(blob, mine) samples are kept, older ones zero.
-  StateHdr same_len = s;
-  same_len.per_channel = mine.per_channel;
-  const bool relen = s.kind == 1 && mine.kind == 1 && s.per_channel != mine.per_channel && s.per_channel + 1 >= (uint64_t)h->d.n_taps &&
-                     s.per_channel <= (uint64_t(1) << 20) && state_compatible(same_len, mine) && bytes == sizeof s + state_payload(s);
-  if (!relen && (!state_compatible(s, mine) || bytes != sizeof s + state_payload(mine))) {
-    return fail(ACDSP_EINVAL, "fir_state_set: blob does not belong to a filter of this class / tap count / channel count");
-  }
-  int rc = check_device(h->d.device);
+  int rc = history_state_set("fir", "blob does not belong to a filter of this class / tap count / channel count", h->d.device, fir_state_hdr(h),
+                             h->use_rt ? (void *)fir_rt_cur(h) : h->hist.cur(), buf, bytes, 0, h->use_rt ? kNoOtherLength : (uint64_t)h->d.n_taps - 1,
+                             uint64_t(1) << 20, false, &s);
   if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());
-  if (relen) {
-    const std::vector<unsigned char> img = relen_image(s, mine, (const unsigned char *)buf + sizeof s);
-    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
-    return ACDSP_OK;
-  }
-  HIP_TRY(hipMemcpy(h->use_rt ? (void *)fir_rt_cur(h) : h->hist.cur(), (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
   if (h->rt_hybrid) {   // partial sums of unknown coefficients and samples: the next n_taps - 1 outputs come from them, the history starts empty
     HIP_TRY(hipMemset(h->hist.cur(), 0, h->hist.bytes()));
     h->rt_valid = true; h->rt_since = 0;
@@ -450,43 +431,18 @@ int64_t acdsp_cic_state_size(acdsp_cic_t h) { return h ? (int64_t)(sizeof(StateH
 int32_t acdsp_cic_state_get(acdsp_cic_t h, void *buf, uint64_t cap_bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
   const StateHdr s = cic_state_hdr(h);
-  const uint64_t pay = state_payload(s);
-  if (cap_bytes < sizeof s + pay) { return fail(ACDSP_EINVAL, "cic_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay)); }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());
-  memcpy(buf, &s, sizeof s);
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
-  return ACDSP_OK;
+  return state_blob_get("cic", h->d.device, s, {{h->hist.cur(), state_payload(s)}}, buf, cap_bytes);
 }
 
 int32_t acdsp_cic_state_set(acdsp_cic_t h, const void *buf, uint64_t bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
-  const StateHdr mine = cic_state_hdr(h);
-  StateHdr s;
-  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "cic_state_set: blob shorter than its header"); }
-  memcpy(&s, buf, sizeof s);
-  // A blob of another history LENGTH is still this filter's state as long as it covers the filter memory (N R M' - 1 inputs for the
-  // decimator): a handle that can take the two-stage kernel (cic2.hip) keeps a longer history than one that cannot (ACDSP_NO_CIC2, an
-  // older build), and the samples beyond the memory only ever feed warm-up values the combs cancel.  The newest min(blob, mine) samples
-  // are kept, older ones zero.
-  StateHdr same_len = s;
-  same_len.per_channel = mine.per_channel;
+  // filter memory: N R M' - 1 inputs for the decimator, N M' + 1 for the interpolator (a handle that can take the two-stage kernel, cic2.hip,
+  // keeps a longer history than one that cannot: ACDSP_NO_CIC2, an older build)
   const uint64_t mem = h->d.interp ? (uint64_t)h->d.N * h->me + 1 : (uint64_t)h->d.N * h->d.R * h->me - 1;
-  const bool relen = s.per_channel != mine.per_channel && s.per_channel >= mem && s.per_channel <= (uint64_t(1) << 24) && state_compatible(same_len, mine) &&
-                     bytes == sizeof s + state_payload(s);
-  if ((!relen && (!state_compatible(s, mine) || bytes != sizeof s + state_payload(mine))) || s.t_total < 0) {
-    return fail(ACDSP_EINVAL, "cic_state_set: blob does not belong to a CIC filter of these parameters / channel count");
-  }
-  int rc = check_device(h->d.device);
+  StateHdr s;
+  const int rc = history_state_set("cic", "blob does not belong to a CIC filter of these parameters / channel count", h->d.device, cic_state_hdr(h),
+                                   h->hist.cur(), buf, bytes, 0, mem, uint64_t(1) << 24, true, &s);
   if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());
-  if (relen) {
-    const std::vector<unsigned char> img = relen_image(s, mine, (const unsigned char *)buf + sizeof s);
-    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(h->hist.cur(), (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
-  }
   h->t_total = s.t_total;
   return ACDSP_OK;
 }
@@ -511,38 +467,29 @@ int64_t acdsp_ddc_state_size(acdsp_ddc_t h) { return h ? (int64_t)(sizeof(StateH
 int32_t acdsp_ddc_state_get(acdsp_ddc_t h, void *buf, uint64_t cap_bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
   const StateHdr s = ddc_state_hdr(h);
-  const uint64_t pay = state_payload(s);
-  if (cap_bytes < sizeof s + pay) { return fail(ACDSP_EINVAL, "ddc_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay)); }
-  int rc = check_device(h->cic->d.device);
-  if (rc) { return rc; }
-  memcpy(buf, &s, sizeof s);
-  if (h->fused) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
-    return ACDSP_OK;
-  }
+  // (two-kernel mode: the payload is the two stage blobs, which the stage functions write)
+  int rc = state_blob_get("ddc", h->cic->d.device, s, {{h->fused ? h->hist.cur() : nullptr, state_payload(s)}}, buf, cap_bytes);
+  if (rc || h->fused) { return rc; }
   const uint64_t nc = (uint64_t)acdsp_cic_state_size(h->cic);
   if ((rc = acdsp_cic_state_get(h->cic, (char *)buf + sizeof s, nc))) { return rc; }
-  return acdsp_fir_state_get(h->fir, (char *)buf + sizeof s + nc, pay - nc);
+  return acdsp_fir_state_get(h->fir, (char *)buf + sizeof s + nc, state_payload(s) - nc);
 }
 
 int32_t acdsp_ddc_state_set(acdsp_ddc_t h, const void *buf, uint64_t bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
+  static const char kRefusal[] = "blob does not belong to a cascade of these parameters / channel count / kernel mode";
   const StateHdr mine = ddc_state_hdr(h);
   StateHdr s;
-  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "ddc_state_set: blob shorter than its header"); }
-  memcpy(&s, buf, sizeof s);
-  if (!state_compatible(s, mine) || s.reserved != mine.reserved || bytes != sizeof s + state_payload(mine) || s.t_total < 0) {
-    return fail(ACDSP_EINVAL, "ddc_state_set: blob does not belong to a cascade of these parameters / channel count / kernel mode");
-  }
-  int rc = check_device(h->cic->d.device);
+  int rc = state_blob_hdr("ddc", buf, bytes, &s);
   if (rc) { return rc; }
-  if (h->fused) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(h->hist.cur(), (const char *)buf + sizeof s, state_payload(mine), hipMemcpyHostToDevice));
+  if (s.reserved != mine.reserved) { return fail(ACDSP_EINVAL, "ddc_state_set: %s", kRefusal); }
+  if (h->fused) {   // (every kernel path of the cascade keeps the same history: no other length)
+    if ((rc = history_state_set("ddc", kRefusal, h->cic->d.device, mine, h->hist.cur(), buf, bytes, 0, kNoOtherLength, 0, true, &s))) { return rc; }
     h->t_total = s.t_total;
     return ACDSP_OK;
   }
+  if (!state_compatible(s, mine) || bytes != sizeof s + state_payload(mine) || s.t_total < 0) { return fail(ACDSP_EINVAL, "ddc_state_set: %s", kRefusal); }
+  if ((rc = check_device(h->cic->d.device))) { return rc; }
   const uint64_t nc = (uint64_t)acdsp_cic_state_size(h->cic);
   if ((rc = acdsp_cic_state_set(h->cic, (const char *)buf + sizeof s, nc))) { return rc; }
   return acdsp_fir_state_set(h->fir, (const char *)buf + sizeof s + nc, state_payload(mine) - nc);

@@ -31,9 +31,12 @@ int cic_int_type(const acdsp_cic_desc_t &d, acdsp_fmt_t *it) {
   return ACDSP_OK;
 }
 
-// ACDSP_FLAG_IN_BYTES on a CIC descriptor: what is refused before any device use
-int cic_bytes_refusal(const acdsp_cic_desc_t &d) {
-  if (d.in.W > 8) { return fail(ACDSP_EINVAL, "CIC: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
+// The byte-container flags of a CIC descriptor (`flags`: the descriptor's, or those of them the caller looks at): *in_eb, or what is refused
+// before any device use
+int cic_byte_rows(const acdsp_cic_desc_t &d, int flags, int *in_eb) {
+  int out_eb;
+  const int rc = byte_rows("CIC", flags, d.in, d.out, nullptr, in_eb, &out_eb);
+  if (rc || *in_eb != 1) { return rc; }
   if (d.interp) { return fail(ACDSP_EUNSUPPORTED, "CIC: ACDSP_FLAG_IN_BYTES on an interpolator (interp == 1) is not supported: its input stream is the thin one"); }
   if (d.out.W > 64) { return fail(ACDSP_EUNSUPPORTED, "CIC: ACDSP_FLAG_IN_BYTES with an OUT_TYPE wider than 64 bits (W=%d) is not supported", d.out.W); }
   return ACDSP_OK;
@@ -67,14 +70,14 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   if (desc->interp && desc->N > 255) { return fail(ACDSP_EUNSUPPORTED, "CIC: N too large"); }
   if (desc->n_channels < 1) { return fail(ACDSP_EINVAL, "CIC: n_channels=%d must be positive", desc->n_channels); }
   if (desc->n_channels > 65535) { return fail(ACDSP_EUNSUPPORTED, "CIC: n_channels=%d outside 1..65535", desc->n_channels); }
-  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
-  if (in_bytes && (rc = cic_bytes_refusal(*desc))) { return rc; }
-  if (desc->flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "CIC: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
+  int in_eb;
+  if ((rc = cic_byte_rows(*desc, desc->flags, &in_eb))) { return rc; }
+  const bool in_bytes = in_eb == 1;
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_cic> h(new acdsp_cic());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   h->it = it;
-  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
+  h->in_eb = in_eb;
   h->out_eb = elem_bytes(desc->out.W);
   h->me = desc->M < 2 ? desc->M : 2;  // effective comb delay of the reference's delay line, see cic.hip
   h->wide = it.W > 64 || desc->out.W > 64;
@@ -169,9 +172,9 @@ int32_t acdsp_cic_two_stage_rates(const acdsp_cic_desc_t *desc, int32_t *R1, int
   if ((rc = check_fmt(desc->in, "IN_TYPE")) || (rc = check_fmt(desc->out, "OUT_TYPE", 128))) { return rc; }
   acdsp_fmt_t it;
   if ((rc = cic_int_type(*desc, &it))) { return rc; }
-  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
-  if (in_bytes && (rc = cic_bytes_refusal(*desc))) { return rc; }
-  const int in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
+  int in_eb;
+  if ((rc = cic_byte_rows(*desc, desc->flags & ~ACDSP_FLAG_OUT_BYTES, &in_eb))) { return rc; }   // (the rates do not depend on the OUT rows)
+  const bool in_bytes = in_eb == 1;
   if (desc->interp || it.W > 64 || desc->out.W > 64 || desc->N > kCicMaxN || desc->R > 256) { return ACDSP_OK; }
   if ((desc->flags & ACDSP_FLAG_FORCE_GENERIC) || !(in_bytes || fits_container(desc->in, in_eb))) { return ACDSP_OK; }
   int r1 = 0, r2 = 0, wu = 0;

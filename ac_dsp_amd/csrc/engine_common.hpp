@@ -4,7 +4,9 @@
 // There is no CPU compute path: every run() launches HIP kernels.
 // Building blocks of the handles, each the single owner of what the families used to spell out one by one: DevBuf (one device allocation),
 // History (the ping-pong input history), PhasePlans (per first % 16 fir_gen plans with their fragments), Staging + run_host_staged (the
-// host-buffer calls), sat_free_bound / fits_container (arithmetic of the path decisions), Timer (event ring).
+// host-buffer calls), sat_free_bound / fits_container (arithmetic of the path decisions), Timer (event ring), byte_rows (the byte-container
+// flags of a descriptor), and for the state blobs StateHdr with history_blob_fits (THE re-length rule), state_blob_get (every _state_get) and
+// history_state_set (the _state_set of every input-history family).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +14,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <utility>
@@ -399,15 +402,90 @@ inline std::vector<unsigned char> relen_image(const StateHdr &s, const StateHdr 
 }
 
 // An input-history blob `s` of `bytes` bytes (header, history, `extra` bytes behind it) against the header `mine` of the handle it is meant for:
-// 0 = not this handle's, 1 = the handle's own layout, 2 = another history LENGTH that still covers the filter memory of `mem` samples (the
-// rule of acdsp_fir_state_set: relen_image keeps the newest samples)
-inline int history_blob_fits(const StateHdr &s, const StateHdr &mine, uint64_t bytes, uint64_t extra, uint64_t mem) {
+// 0 = not this handle's, 1 = the handle's own layout, 2 = another history LENGTH, of at most max_len samples, that still covers the filter
+// memory of `mem` samples.  THE re-length rule of every input-history family: a handle's length is its filter memory rounded up for the kernels'
+// windows -- it differs between kernel paths and between builds -- and the samples beyond the memory only ever meet zero coefficients (or feed
+// warm-up values the combs cancel), so relen_image keeps the newest min(blob, mine) samples and zeroes older ones.
+constexpr uint64_t kNoOtherLength = ~uint64_t(0);   // `mem` of a state that is not an input history (FIR reg_trans sums) or whose length never varies
+inline int history_blob_fits(const StateHdr &s, const StateHdr &mine, uint64_t bytes, uint64_t extra, uint64_t mem, uint64_t max_len) {
   if (state_compatible(s, mine)) { return bytes == sizeof s + state_payload(mine) + extra ? 1 : 0; }
   StateHdr same_len = s;
   same_len.per_channel = mine.per_channel;
-  const bool relen = s.per_channel != mine.per_channel && s.per_channel >= mem && s.per_channel <= (uint64_t(1) << 20) && state_compatible(same_len, mine) &&
+  const bool relen = s.per_channel != mine.per_channel && s.per_channel >= mem && s.per_channel <= max_len && state_compatible(same_len, mine) &&
                      bytes == sizeof s + state_payload(s) + extra;
   return relen ? 2 : 0;
+}
+
+// The header of a blob handed to acdsp_<name>_state_set
+inline int state_blob_hdr(const char *name, const void *buf, uint64_t bytes, StateHdr *s) {
+  if (bytes < sizeof *s) { return fail(ACDSP_EINVAL, "%s_state_set: blob shorter than its header", name); }
+  memcpy(s, buf, sizeof *s);
+  return ACDSP_OK;
+}
+
+// acdsp_<name>_state_get: the header `s`, then the device blocks `parts` in order, into buf[cap]; a part without a pointer is counted and left
+// for the caller to fill.  `pre` runs on the drained device in front of the copies; the parts' pointers are read after it (FIR: reg_trans[] may
+// have to be rebuilt first, into the other buffer).
+struct StatePart { const void *dev; uint64_t bytes; };
+template <typename Pre>
+int state_blob_get(const char *name, int device, const StateHdr &s, const StatePart *parts, int n_parts, void *buf, uint64_t cap, Pre pre) {
+  uint64_t need = sizeof s;
+  for (int i = 0; i < n_parts; i++) { need += parts[i].bytes; }
+  if (cap < need) { return fail(ACDSP_EINVAL, "%s_state_get: buffer of %llu bytes, state needs %llu", name, (unsigned long long)cap, (unsigned long long)need); }
+  int rc = check_device(device);
+  if (rc) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous: the state of the last call must have landed
+  if ((rc = pre())) { return rc; }
+  memcpy(buf, &s, sizeof s);
+  char *dst = (char *)buf + sizeof s;
+  for (int i = 0; i < n_parts; i++) {
+    if (parts[i].dev) { HIP_TRY(hipMemcpy(dst, parts[i].dev, parts[i].bytes, hipMemcpyDeviceToHost)); }
+    dst += parts[i].bytes;
+  }
+  return ACDSP_OK;
+}
+inline int state_blob_get(const char *name, int device, const StateHdr &s, std::initializer_list<StatePart> parts, void *buf, uint64_t cap) {
+  return state_blob_get(name, device, s, parts.begin(), (int)parts.size(), buf, cap, [] { return (int)ACDSP_OK; });
+}
+
+// acdsp_<name>_state_set of the input-history families: the blob buf[bytes] -- header, history, `extra` bytes behind it -- goes into the history
+// at d_hist if history_blob_fits() says it is the state of the handle with header `mine`, re-lengthed where it has to be; anything else, and a
+// negative input count where the family carries a phase in t_total (`phased`), is refused with "<name>_state_set: <refusal>" before the device
+// is touched.  *s_out = the blob's header: the caller takes t_total and whatever follows the history from it.
+inline int history_state_set(const char *name, const char *refusal, int device, const StateHdr &mine, void *d_hist, const void *buf, uint64_t bytes,
+                             uint64_t extra, uint64_t mem, uint64_t max_len, bool phased, StateHdr *s_out) {
+  StateHdr &s = *s_out;
+  int rc = state_blob_hdr(name, buf, bytes, &s);
+  if (rc) { return rc; }
+  const int fit = history_blob_fits(s, mine, bytes, extra, mem, max_len);
+  if (!fit || (phased && s.t_total < 0)) { return fail(ACDSP_EINVAL, "%s_state_set: %s", name, refusal); }
+  if ((rc = check_device(device))) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  const unsigned char *pay = (const unsigned char *)buf + sizeof s;
+  if (fit == 2) {
+    const std::vector<unsigned char> img = relen_image(s, mine, pay);
+    HIP_TRY(hipMemcpy(d_hist, img.data(), img.size(), hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(hipMemcpy(d_hist, pay, state_payload(mine), hipMemcpyHostToDevice));
+  }
+  return ACDSP_OK;
+}
+
+// The byte-container flags of a descriptor (ACDSP_FLAG_IN_BYTES / ACDSP_FLAG_OUT_BYTES): container bytes of the IN and OUT rows, or the refusal.
+// One order of checks for every family; `prefix` = the family's name in its messages (nullptr: none); out_needs_in = the family's sentence for
+// OUT_BYTES without IN_BYTES where it has 1-byte output rows, nullptr where it has none.  Family-specific refusals follow in the family.
+inline int byte_rows(const char *prefix, int flags, const acdsp_fmt_t &in, const acdsp_fmt_t &out, const char *out_needs_in, int *in_eb, int *out_eb) {
+  const bool in_bytes = (flags & ACDSP_FLAG_IN_BYTES) != 0, out_bytes = (flags & ACDSP_FLAG_OUT_BYTES) != 0;
+  const std::string p = prefix ? std::string(prefix) + ": " : std::string();
+  if (in_bytes && in.W > 8) { return fail(ACDSP_EINVAL, "%sACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", p.c_str(), in.W); }
+  if (out_bytes && !out_needs_in) {
+    return fail(ACDSP_EUNSUPPORTED, "%sACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)", p.c_str());
+  }
+  if (out_bytes && !in_bytes) { return fail(ACDSP_EUNSUPPORTED, "%s%s", p.c_str(), out_needs_in); }
+  if (out_bytes && out.W > 8) { return fail(ACDSP_EINVAL, "%sACDSP_FLAG_OUT_BYTES: OUT_TYPE W=%d does not fit a 1-byte container", p.c_str(), out.W); }
+  *in_eb = in_bytes ? 1 : elem_bytes(in.W);
+  *out_eb = out_bytes ? 1 : elem_bytes(out.W);
+  return ACDSP_OK;
 }
 
 }  // namespace eng

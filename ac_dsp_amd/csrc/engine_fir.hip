@@ -106,7 +106,8 @@ const char *fir_bytes_refusal(const acdsp_fir_desc_t &d) {
   return nullptr;
 }
 
-int fir_validate(const acdsp_fir_desc_t &d) {
+// (*in_eb / *out_eb: container bytes of the rows under the descriptor's byte flags)
+int fir_validate(const acdsp_fir_desc_t &d, int *in_eb, int *out_eb) {
   if (d.kind < ACDSP_FIR_CONST || d.kind > ACDSP_FIR_REG_SHARE) { return fail(ACDSP_EINVAL, "bad FIR class %d", d.kind); }
   if (d.ftype < 0 || d.ftype > ACDSP_FOLD_ODD_ANTI) { return fail(ACDSP_EINVAL, "bad ftype %d", d.ftype); }
   if (internal_ftype(d.kind, d.ftype) < 0) {
@@ -137,15 +138,13 @@ int fir_validate(const acdsp_fir_desc_t &d) {
     return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 256-bit intermediates");
   }
   if (wide && d.kind == ACDSP_FIR_REG_SHARE) { return fail(ACDSP_EUNSUPPORTED, "ac_fir_reg_share: ACC / OUT wider than 64 bits not supported"); }
-  if (d.flags & ACDSP_FLAG_OUT_BYTES) {
-    if (d.out.W > 8) { return fail(ACDSP_EINVAL, "ACDSP_FLAG_OUT_BYTES: OUT_TYPE W=%d does not fit a 1-byte container", d.out.W); }
-    // the int16-sample kernels have no 1-byte output tile: byte outputs of an unflagged input are the follow-up
-    if (!(d.flags & ACDSP_FLAG_IN_BYTES)) {
-      return fail(ACDSP_EUNSUPPORTED, "ACDSP_FLAG_OUT_BYTES without ACDSP_FLAG_IN_BYTES: only the byte-sample kernels write 1-byte output rows (the int16-sample kernels are not done yet)");
-    }
+  // (the int16-sample kernels have no 1-byte output tile: byte outputs of an unflagged input are the follow-up)
+  if ((rc = byte_rows(nullptr, d.flags, d.in, d.out,
+                      "ACDSP_FLAG_OUT_BYTES without ACDSP_FLAG_IN_BYTES: only the byte-sample kernels write 1-byte output rows (the int16-sample kernels are not done yet)",
+                      in_eb, out_eb))) {
+    return rc;
   }
   if (d.flags & ACDSP_FLAG_IN_BYTES) {
-    if (d.in.W > 8) { return fail(ACDSP_EINVAL, "ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
     if (wide) { return fail(ACDSP_EUNSUPPORTED, "ACDSP_FLAG_IN_BYTES: ACC_TYPE or OUT_TYPE wider than 64 bits not supported"); }
     // more than 2048 taps: the byte-sample matrix-core kernel or nothing
     if (d.n_taps > 2048) {
@@ -166,14 +165,14 @@ extern "C" {
 
 int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   if (!desc || !out) { return fail(ACDSP_EINVAL, "null argument"); }
-  int rc = fir_validate(*desc);
+  int in_eb, out_eb;
+  int rc = fir_validate(*desc, &in_eb, &out_eb);
   if (rc) { return rc; }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_fir> h(new acdsp_fir());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
-  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
-  h->out_eb = (desc->flags & ACDSP_FLAG_OUT_BYTES) ? 1 : elem_bytes(desc->out.W);   // (fir_validate: W <= 8 and byte samples under the flag)
+  h->in_eb = in_eb; h->out_eb = out_eb;
   h->wide = desc->acc.W > 64 || desc->out.W > 64;
   h->rt_eb = h->wide ? 16 : 8;
   h->hl = round_up(desc->n_taps + 15, 32);  // >= n_taps-1 for every kernel, >= n_taps+14 for the 16-aligned windows of fir_gen

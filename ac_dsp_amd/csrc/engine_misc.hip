@@ -55,13 +55,12 @@ int32_t acdsp_intgdump_create(const acdsp_intgdump_desc_t *desc, acdsp_intgdump_
   if (d.n_objects > 65535) { return fail(ACDSP_EUNSUPPORTED, "n_objects=%d outside 1..65535", d.n_objects); }
   int rc;
   if ((rc = check_fmt(d.in, "IN_TYPE")) || (rc = check_fmt(d.acc, "ACC_TYPE")) || (rc = check_fmt(d.out, "OUT_TYPE"))) { return rc; }
-  const bool in_bytes = (d.flags & ACDSP_FLAG_IN_BYTES) != 0;
-  if (in_bytes && d.in.W > 8) { return fail(ACDSP_EINVAL, "intg_dump: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", d.in.W); }
-  if (d.flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "intg_dump: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
+  int in_eb, out_eb;
+  if ((rc = byte_rows("intg_dump", d.flags, d.in, d.out, nullptr, &in_eb, &out_eb))) { return rc; }
   if ((rc = check_device(d.device))) { return rc; }
   std::unique_ptr<acdsp_intgdump> h(new acdsp_intgdump());   // (check_device has made the device current: a failure below frees there)
   h->d = d;
-  h->in_eb = in_bytes ? 1 : elem_bytes(d.in.W); h->out_eb = elem_bytes(d.out.W);
+  h->in_eb = in_eb; h->out_eb = out_eb;
   if ((rc = h->temp.init(d.n_objects, d.chn, sizeof(int64_t)))) { return rc; }   // temp[i] = 0.0 (ac_intg_dump.h:86-89)
   *out = h.release();
   return ACDSP_OK;
@@ -249,22 +248,15 @@ int64_t acdsp_intgdump_state_size(acdsp_intgdump_t h) { return h ? (int64_t)(siz
 int32_t acdsp_intgdump_state_get(acdsp_intgdump_t h, void *buf, uint64_t cap_bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
   const StateHdr s = intgdump_state_hdr(h);
-  const uint64_t pay = state_payload(s);
-  if (cap_bytes < sizeof s + pay) { return fail(ACDSP_EINVAL, "intgdump_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay)); }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous: the sums of the last call must have landed
-  memcpy(buf, &s, sizeof s);
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->temp.cur(), pay, hipMemcpyDeviceToHost));
-  return ACDSP_OK;
+  return state_blob_get("intgdump", h->d.device, s, {{h->temp.cur(), state_payload(s)}}, buf, cap_bytes);
 }
 
 int32_t acdsp_intgdump_state_set(acdsp_intgdump_t h, const void *buf, uint64_t bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
   const StateHdr mine = intgdump_state_hdr(h);
   StateHdr s;
-  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "intgdump_state_set: blob shorter than its header"); }
-  memcpy(&s, buf, sizeof s);
+  int rc = state_blob_hdr("intgdump", buf, bytes, &s);
+  if (rc) { return rc; }
   if (!state_compatible(s, mine) || bytes != sizeof s + state_payload(mine) || (s.reserved & ~(uint64_t)1)) {
     return fail(ACDSP_EINVAL, "intgdump_state_set: blob does not belong to an ac_intg_dump of this NS / CHN / object count");
   }
@@ -277,8 +269,7 @@ int32_t acdsp_intgdump_state_set(acdsp_intgdump_t h, const void *buf, uint64_t b
     if (w < af.lo || w > af.hi) { return fail(ACDSP_EINVAL, "intgdump_state_set: word %llu = %lld is not an ACC_TYPE raw word", (unsigned long long)i, (long long)w); }
     all_zero = all_zero && w == 0;
   }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
+  if ((rc = check_device(h->d.device))) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(h->temp.cur(), pay, state_payload(mine), hipMemcpyHostToDevice));
   // what run() derives from temp[]: the tile / stream kernels leave temp[] alone only when it is known to be zero, and sums that are carried
@@ -325,16 +316,16 @@ int32_t acdsp_mvavg_create(const acdsp_mvavg_desc_t *desc, acdsp_mvavg_t *out) {
   // 128-bit exact intermediates: ACC x COEFF product aligned with the accumulator
   const int fc = desc->coeff.W - desc->coeff.I;
   if (desc->acc.W + desc->coeff.W + 2 + (fc < 0 ? -fc : 0) > 125) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: type combination needs more than 128-bit intermediates"); }
-  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0, out_bytes = (desc->flags & ACDSP_FLAG_OUT_BYTES) != 0;
-  if (in_bytes && desc->in.W > 8) { return fail(ACDSP_EINVAL, "mv_avg: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", desc->in.W); }
-  if (out_bytes && !in_bytes) { return fail(ACDSP_EUNSUPPORTED, "mv_avg: ACDSP_FLAG_OUT_BYTES needs ACDSP_FLAG_IN_BYTES (1-byte output rows exist on the byte-sample kernels only)"); }
-  if (out_bytes && desc->out.W > 8) { return fail(ACDSP_EINVAL, "mv_avg: ACDSP_FLAG_OUT_BYTES: OUT_TYPE W=%d does not fit a 1-byte container", desc->out.W); }
+  int in_eb, out_eb;
+  if ((rc = byte_rows("mv_avg", desc->flags, desc->in, desc->out, "ACDSP_FLAG_OUT_BYTES needs ACDSP_FLAG_IN_BYTES (1-byte output rows exist on the byte-sample kernels only)",
+                      &in_eb, &out_eb))) {
+    return rc;
+  }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_mvavg> h(new acdsp_mvavg());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
-  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
-  h->out_eb = out_bytes ? 1 : elem_bytes(desc->out.W);
-  h->frag_gran = in_bytes ? 16 : 8;
+  h->in_eb = in_eb; h->out_eb = out_eb;
+  h->frag_gran = in_eb == 1 ? 16 : 8;
   if ((rc = h->d_coeffs.alloc((size_t)desc->taps * sizeof(int64_t))) || (rc = h->d_frag.alloc((size_t)kMvAvgFragWords * sizeof(uint32_t)))) { return rc; }
   *out = h.release();
   return ACDSP_OK;

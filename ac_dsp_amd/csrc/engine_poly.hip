@@ -73,8 +73,9 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
       (rc = check_fmt(desc->out, "OUT_TYPE"))) {
     return rc;
   }
-  const bool in_bytes = (desc->flags & ACDSP_FLAG_IN_BYTES) != 0;
-  if (in_bytes && desc->in.W > 8) { return fail(ACDSP_EINVAL, "poly_dec: ACDSP_FLAG_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", desc->in.W); }
+  int in_eb, out_eb;
+  if ((rc = byte_rows("poly_dec", desc->flags, desc->in, desc->out, nullptr, &in_eb, &out_eb))) { return rc; }
+  const bool in_bytes = in_eb == 1;
   const int fi = desc->in.W - desc->in.I, fc = desc->coeff.W - desc->coeff.I, fa = desc->acc.W - desc->acc.I;
   const int f = fi + fc > fa ? fi + fc : fa;
   if (desc->in.W + desc->coeff.W + 2 + (f - fi - fc) > 125 || desc->acc.W + (f - fa) > 125) {
@@ -86,12 +87,10 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
     return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %lld: more than 2048 taps run on the long matrix-core kernel only, which does not take %s",
                 (long long)desc->n_taps * desc->df, long_why);
   }
-  if (desc->flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "poly_dec: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
   if ((rc = check_device(desc->device))) { return rc; }
   std::unique_ptr<acdsp_polydec> h(new acdsp_polydec());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
-  h->in_eb = in_bytes ? 1 : elem_bytes(desc->in.W);
-  h->out_eb = elem_bytes(desc->out.W);
+  h->in_eb = in_eb; h->out_eb = out_eb;
   h->hl = round_up(desc->n_taps * desc->df + 15, 32);
   h->lossless_shape = fa >= fi + fc && fa - fi - fc < 64;
   h->lossless = h->lossless_shape && desc->acc.O == ACDSP_WRAP;
@@ -308,37 +307,16 @@ int64_t acdsp_polydec_state_size(acdsp_polydec_t h) { return h ? (int64_t)(sizeo
 int32_t acdsp_polydec_state_get(acdsp_polydec_t h, void *buf, uint64_t cap_bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
   const StateHdr s = polydec_state_hdr(h);
-  const uint64_t pay = state_payload(s);
-  if (cap_bytes < sizeof s + pay) { return fail(ACDSP_EINVAL, "polydec_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay)); }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous: the state of the last call must have landed
-  memcpy(buf, &s, sizeof s);
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
-  return ACDSP_OK;
+  return state_blob_get("polydec", h->d.device, s, {{h->hist.cur(), state_payload(s)}}, buf, cap_bytes);
 }
 
 int32_t acdsp_polydec_state_set(acdsp_polydec_t h, const void *buf, uint64_t bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
-  const StateHdr mine = polydec_state_hdr(h);
-  StateHdr s;
-  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "polydec_state_set: blob shorter than its header"); }
-  memcpy(&s, buf, sizeof s);
   // every kernel path of a descriptor keeps the same history today; a blob of another length (another build) is taken as long as it covers
   // the NTAPS*DF - 1 samples an output reaches back
-  const int fit = history_blob_fits(s, mine, bytes, 0, (uint64_t)h->d.n_taps * h->d.df - 1);
-  if (!fit) { return fail(ACDSP_EINVAL, "polydec_state_set: blob does not belong to an ac_poly_dec of this NTAPS / DF / channel count"); }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());
-  const unsigned char *pay = (const unsigned char *)buf + sizeof s;
-  if (fit == 2) {
-    const std::vector<unsigned char> img = relen_image(s, mine, pay);
-    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(h->hist.cur(), pay, state_payload(mine), hipMemcpyHostToDevice));
-  }
-  return ACDSP_OK;
+  StateHdr s;
+  return history_state_set("polydec", "blob does not belong to an ac_poly_dec of this NTAPS / DF / channel count", h->d.device, polydec_state_hdr(h),
+                           h->hist.cur(), buf, bytes, 0, (uint64_t)h->d.n_taps * h->d.df - 1, uint64_t(1) << 20, false, &s);
 }
 
 }  // extern "C"
@@ -844,41 +822,21 @@ int64_t acdsp_polyintr_state_size(acdsp_polyintr_t h) {
 
 int32_t acdsp_polyintr_state_get(acdsp_polyintr_t h, void *buf, uint64_t cap_bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
-  const StateHdr s = polyintr_state_hdr(h);
-  const uint64_t pay = state_payload(s), sv = polyintr_saved_bytes(h);
-  if (cap_bytes < sizeof s + pay + sv) { return fail(ACDSP_EINVAL, "polyintr_state_get: buffer of %llu bytes, state needs %llu", (unsigned long long)cap_bytes, (unsigned long long)(sizeof s + pay + sv)); }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());   // run() is asynchronous, on two streams: the state of the last call must have landed
-  memcpy(buf, &s, sizeof s);
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s, h->hist.cur(), pay, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy((char *)buf + sizeof s + pay, h->d_saved[h->hist.index()].get(), sv, hipMemcpyDeviceToHost));
-  return ACDSP_OK;
+  const StateHdr s = polyintr_state_hdr(h);   // (run() is asynchronous on two streams: the getter drains the device)
+  return state_blob_get("polyintr", h->d.device, s, {{h->hist.cur(), state_payload(s)}, {h->d_saved[h->hist.index()].get(), polyintr_saved_bytes(h)}}, buf, cap_bytes);
 }
 
 int32_t acdsp_polyintr_state_set(acdsp_polyintr_t h, const void *buf, uint64_t bytes) {
   if (!h || !buf) { return fail(ACDSP_EINVAL, "null argument"); }
-  const StateHdr mine = polyintr_state_hdr(h);
-  StateHdr s;
-  if (bytes < sizeof s) { return fail(ACDSP_EINVAL, "polyintr_state_set: blob shorter than its header"); }
-  memcpy(&s, buf, sizeof s);
   // every kernel path of a descriptor keeps the same history today; a blob of another length (another build) is taken as long as it covers
   // the NTAPS samples the sums of a call's first group reach back
   const uint64_t sv = polyintr_saved_bytes(h);
-  const int fit = history_blob_fits(s, mine, bytes, sv, (uint64_t)h->d.n_taps);
-  if (!fit || s.t_total < 0) { return fail(ACDSP_EINVAL, "polyintr_state_set: blob does not belong to an ac_poly_intr of this NTAPS / IF / ftype / COEFFSZ / channel count"); }
-  int rc = check_device(h->d.device);
+  StateHdr s;
+  const int rc = history_state_set("polyintr", "blob does not belong to an ac_poly_intr of this NTAPS / IF / ftype / COEFFSZ / channel count", h->d.device,
+                                   polyintr_state_hdr(h), h->hist.cur(), buf, bytes, sv, (uint64_t)h->d.n_taps, uint64_t(1) << 20, true, &s);
   if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());
-  const unsigned char *pay = (const unsigned char *)buf + sizeof s;
-  if (fit == 2) {
-    const std::vector<unsigned char> img = relen_image(s, mine, pay);
-    HIP_TRY(hipMemcpy(h->hist.cur(), img.data(), img.size(), hipMemcpyHostToDevice));
-  } else {
-    HIP_TRY(hipMemcpy(h->hist.cur(), pay, state_payload(mine), hipMemcpyHostToDevice));
-  }
   // the saved sums are indexed like the history: they go beside the buffer just written
-  HIP_TRY(hipMemcpy(h->d_saved[h->hist.index()].get(), pay + state_payload(s), sv, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_saved[h->hist.index()].get(), (const char *)buf + sizeof s + state_payload(s), sv, hipMemcpyHostToDevice));
   h->t_total = s.t_total;
   return ACDSP_OK;
 }

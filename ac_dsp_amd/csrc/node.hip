@@ -282,18 +282,7 @@ int32_t acdsp_node_fir_create(const acdsp_fir_desc_t *desc, int32_t n_devices, c
   int rc = make_node(kNodeFir, desc->n_channels, n_devices, devices, &h);
   if (rc) { return rc; }
   h->n_taps = desc->n_taps; h->coeffs_per_channel = desc->coeffs_per_channel;
-  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
-  const acdsp_fir_desc_t d0 = *desc;
-  rc = run_all(h, [h, d0](int i) {
-    Shard &s = h->shards[(size_t)i];
-    acdsp_fir_desc_t d = d0;
-    d.n_channels = (int32_t)(s.hi - s.lo); d.device = s.device;
-    acdsp_fir_t f = nullptr;
-    const int r = acdsp_fir_create(&d, &f);
-    s.handle = f;
-    return r;
-  });
-  if (rc) { const std::string keep = acdsp_last_error(); free_node(h); return set_error(rc, keep.c_str()); }
+  if ((rc = create_shards<acdsp_fir_desc_t, acdsp_fir_t>(h, *desc, &acdsp_fir_desc_t::n_channels, acdsp_fir_create))) { return rc; }
   h->in_eb = acdsp_fir_in_elem_bytes((acdsp_fir_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES: run_host slices byte rows
   h->out_eb = acdsp_fir_out_elem_bytes((acdsp_fir_t)h->shards[0].handle);  // 1 under ACDSP_FLAG_OUT_BYTES
   *out = h;
@@ -337,19 +326,9 @@ int32_t acdsp_node_cic_create(const acdsp_cic_desc_t *desc, int32_t n_devices, c
   acdsp_node *h = nullptr;
   int rc = make_node(kNodeCic, desc->n_channels, n_devices, devices, &h);
   if (rc) { return rc; }
-  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
-  const acdsp_cic_desc_t d0 = *desc;
-  rc = run_all(h, [h, d0](int i) {
-    Shard &s = h->shards[(size_t)i];
-    acdsp_cic_desc_t d = d0;
-    d.n_channels = (int32_t)(s.hi - s.lo); d.device = s.device;
-    acdsp_cic_t c = nullptr;
-    const int r = acdsp_cic_create(&d, &c);
-    s.handle = c;
-    return r;
-  });
-  if (rc) { const std::string keep = acdsp_last_error(); free_node(h); return set_error(rc, keep.c_str()); }
+  if ((rc = create_shards<acdsp_cic_desc_t, acdsp_cic_t>(h, *desc, &acdsp_cic_desc_t::n_channels, acdsp_cic_create))) { return rc; }
   h->in_eb = acdsp_cic_in_elem_bytes((acdsp_cic_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES
+  h->out_eb = acdsp_elem_bytes(desc->out.W);
   *out = h;
   return ACDSP_OK;
 }
@@ -382,20 +361,17 @@ int32_t acdsp_node_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_
   int rc = make_node(kNodeDdc, cic->n_channels, n_devices, devices, &h);
   if (rc) { return rc; }
   h->n_taps = fir->n_taps;
-  h->in_eb = acdsp_elem_bytes(cic->in.W); h->out_eb = acdsp_elem_bytes(fir->out.W);
-  const acdsp_cic_desc_t c0 = *cic;
-  const acdsp_fir_desc_t f0 = *fir;
-  rc = run_all(h, [h, c0, f0](int i) {
-    Shard &s = h->shards[(size_t)i];
-    acdsp_cic_desc_t c = c0;
-    acdsp_fir_desc_t f = f0;
-    c.n_channels = f.n_channels = (int32_t)(s.hi - s.lo); c.device = f.device = s.device;
-    acdsp_ddc_t d = nullptr;
-    const int r = acdsp_ddc_create(&c, &f, &d);
-    s.handle = d;
-    return r;
+  // both stage descriptors take the slice's channel count and device
+  struct Stages { acdsp_cic_desc_t cic; acdsp_fir_desc_t fir; int32_t n_channels, device; };
+  const Stages both = {*cic, *fir, 0, 0};
+  rc = create_shards<Stages, acdsp_ddc_t>(h, both, &Stages::n_channels, [](const Stages *st, acdsp_ddc_t *e) {
+    acdsp_cic_desc_t c = st->cic;
+    acdsp_fir_desc_t f = st->fir;
+    c.n_channels = f.n_channels = st->n_channels; c.device = f.device = st->device;
+    return acdsp_ddc_create(&c, &f, e);
   });
-  if (rc) { const std::string keep = acdsp_last_error(); free_node(h); return set_error(rc, keep.c_str()); }
+  if (rc) { return rc; }
+  h->in_eb = acdsp_elem_bytes(cic->in.W); h->out_eb = acdsp_elem_bytes(fir->out.W);
   *out = h;
   return ACDSP_OK;
 }
@@ -433,9 +409,9 @@ int32_t acdsp_node_polydec_create(const acdsp_polydec_desc_t *desc, int32_t n_de
   acdsp_node *h = nullptr;
   int rc = make_node(kNodePolyDec, desc->n_channels, n_devices, devices, &h);
   if (rc) { return rc; }
-  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   if ((rc = create_shards<acdsp_polydec_desc_t, acdsp_polydec_t>(h, *desc, &acdsp_polydec_desc_t::n_channels, acdsp_polydec_create))) { return rc; }
   h->in_eb = acdsp_polydec_in_elem_bytes((acdsp_polydec_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES
+  h->out_eb = acdsp_elem_bytes(desc->out.W);
   *out = h;
   return ACDSP_OK;
 }
@@ -460,8 +436,8 @@ int32_t acdsp_node_polyintr_create(const acdsp_polyintr_desc_t *desc, int32_t n_
   acdsp_node *h = nullptr;
   int rc = make_node(kNodePolyIntr, desc->n_channels, n_devices, devices, &h);
   if (rc) { return rc; }
-  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   if ((rc = create_shards<acdsp_polyintr_desc_t, acdsp_polyintr_t>(h, *desc, &acdsp_polyintr_desc_t::n_channels, acdsp_polyintr_create))) { return rc; }
+  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   *out = h;
   return ACDSP_OK;
 }
@@ -492,9 +468,9 @@ int32_t acdsp_node_intgdump_create(const acdsp_intgdump_desc_t *desc, int32_t n_
   acdsp_node *h = nullptr;
   int rc = make_node(kNodeIntgDump, desc->n_objects, n_devices, devices, &h);
   if (rc) { return rc; }
-  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   if ((rc = create_shards<acdsp_intgdump_desc_t, acdsp_intgdump_t>(h, *desc, &acdsp_intgdump_desc_t::n_objects, acdsp_intgdump_create))) { return rc; }
   h->in_eb = acdsp_intgdump_in_elem_bytes((acdsp_intgdump_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_IN_BYTES
+  h->out_eb = acdsp_elem_bytes(desc->out.W);
   *out = h;
   return ACDSP_OK;
 }
@@ -517,7 +493,6 @@ int32_t acdsp_node_mvavg_create(const acdsp_mvavg_desc_t *desc, int32_t n_device
   acdsp_node *h = nullptr;
   int rc = make_node(kNodeMvAvg, desc->n_objects, n_devices, devices, &h);
   if (rc) { return rc; }
-  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
   if ((rc = create_shards<acdsp_mvavg_desc_t, acdsp_mvavg_t>(h, *desc, &acdsp_mvavg_desc_t::n_objects, acdsp_mvavg_create))) { return rc; }
   h->in_eb = acdsp_mvavg_in_elem_bytes((acdsp_mvavg_t)h->shards[0].handle);     // 1 under ACDSP_FLAG_IN_BYTES
   h->out_eb = acdsp_mvavg_out_elem_bytes((acdsp_mvavg_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_OUT_BYTES

@@ -32,10 +32,22 @@ def is_wide(fmt):
     return lib.acdsp_elem_bytes(fmt.W) == 16
 
 
-def _alloc_out(fmt, n_ch, n, device):
-    """[n_ch][n] OUT containers; 16-byte containers are a trailing dimension of two int64 (low, high)."""
-    shape = (n_ch, n, 2) if is_wide(fmt) else (n_ch, n)
-    return torch.empty(shape, dtype=torch_dtype_for(fmt), device=device)
+def _byte_dtype(fmt, as_bytes):
+    """torch dtype of a row of `fmt` words: int8 / uint8 by signedness in 1-byte containers, else the format's own container"""
+    if as_bytes:
+        return torch.int8 if fmt.S else torch.uint8
+    return torch_dtype_for(fmt)
+
+
+def _flags(force_generic=False, in_bytes=False, out_bytes=False):
+    """flag word of a descriptor"""
+    return (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0) | (_lib.FLAG_OUT_BYTES if out_bytes else 0)
+
+
+def _alloc_out(fmt, n_ch, n, device, as_bytes=False):
+    """[n_ch][n] OUT containers; 16-byte containers are a trailing dimension of two int64 (low, high); as_bytes: 1-byte containers."""
+    shape = (n_ch, n, 2) if is_wide(fmt) and not as_bytes else (n_ch, n)
+    return torch.empty(shape, dtype=_byte_dtype(fmt, as_bytes), device=device)
 
 
 def _alloc_out_host(fmt, n_ch, n, out_bytes=False):
@@ -183,24 +195,57 @@ def diag_fir_envelope_copygeom_ms(coeffs, mfma_per_step, mfma_hi_per_step, x, y,
     return ms.value, nbytes
 
 
-def _clone(obj, clone_fn):
-    """A new object of obj's class around clone_fn(obj's handle): same descriptor, coefficients and stream state, independent afterwards."""
-    h = C.c_void_p()
-    check(clone_fn(obj._h, C.byref(h)))
-    twin = object.__new__(type(obj))
-    twin.__dict__.update(obj.__dict__)
-    twin._h = h
-    return twin
+class _Rows:
+    """Row containers of an engine or node object: self.fin / self.fout, in 1-byte containers under self.in_bytes / self.out_bytes."""
+    in_bytes = out_bytes = False
+    in_dtype = property(lambda self: _byte_dtype(self.fin, self.in_bytes), doc="torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE")
+    out_dtype = property(lambda self: _byte_dtype(self.fout, self.out_bytes), doc="torch dtype of the output rows: int8 / uint8 containers under out_bytes, else the container of OUT_TYPE")
 
 
-def _state_get(h, size_fn, get_fn):
-    buf = (C.c_char * size_fn(h))()
-    check(get_fn(h, buf, len(buf)))
-    return bytes(buf)
+class _Handle(_Rows):
+    """Owner of one engine handle self._h of the family acdsp_<_c>_*."""
+    _c = None   # the family's C prefix
+
+    def _fn(self, name):
+        return getattr(lib, "acdsp_%s_%s" % (self._c, name))
+
+    def clone(self):
+        """Deep copy -- descriptor, coefficients and stream state; the two objects are independent afterwards (acdsp_*_clone)."""
+        h = C.c_void_p()
+        check(self._fn("clone")(self._h, C.byref(h)))
+        twin = object.__new__(type(self))
+        twin.__dict__.update(self.__dict__)
+        twin._h = h
+        return twin
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
 
 
-class Fir:
+class _Stateful(_Handle):
+    """... whose stream state can be saved, restored and cleared (acdsp_*_state_size / _state_get / _state_set / _reset)."""
+
+    def state(self):
+        """Versioned state blob (bytes): the family's stream state of every channel (include/acdsp.h lists what each kind holds)."""
+        buf = (C.c_char * self._fn("state_size")(self._h))()
+        check(self._fn("state_get")(self._h, buf, len(buf)))
+        return bytes(buf)
+
+    def set_state(self, blob):
+        check(self._fn("state_set")(self._h, C.c_char_p(blob), len(blob)))
+
+    def reset(self):
+        check(self._fn("reset")(self._h))
+
+
+class Fir(_Stateful):
     """n_channels independent reference FIR objects (ac_fir_{const,load,prog}_coeffs) behind one handle."""
+    _c = "fir"
 
     def __init__(self, n_taps, ftype, fin, fcoeff, facc, fout, n_channels=1, kind="load", coeffs_per_channel=False,
                  device=0, force_generic=False, in_bytes=False, out_bytes=False):
@@ -213,8 +258,7 @@ class Fir:
         self.out_bytes = bool(out_bytes)
         d = FirDesc(KINDS[kind] if isinstance(kind, str) else kind, FTYPES[ftype] if isinstance(ftype, str) else ftype,
                     n_taps, n_channels, int(self.coeffs_per_channel), fin, fcoeff, facc, fout, device,
-                    (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0) |
-                    (_lib.FLAG_OUT_BYTES if out_bytes else 0))
+                    _flags(force_generic, in_bytes, out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_fir_create(C.byref(d), C.byref(self._h)))
 
@@ -223,20 +267,6 @@ class Fir:
         want = (self.n_channels, self.n_taps) if self.coeffs_per_channel else (self.n_taps,)
         assert c.shape == want, (c.shape, want)
         check(lib.acdsp_fir_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
-
-    @property
-    def in_dtype(self):
-        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
-        if self.in_bytes:
-            return torch.int8 if self.fin.S else torch.uint8
-        return torch_dtype_for(self.fin)
-
-    @property
-    def out_dtype(self):
-        """torch dtype of the output rows: int8 / uint8 containers under out_bytes, else the container of OUT_TYPE"""
-        if self.out_bytes:
-            return torch.int8 if self.fout.S else torch.uint8
-        return torch_dtype_for(self.fout)
 
     @property
     def path(self):
@@ -258,7 +288,7 @@ class Fir:
         assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         n = x.shape[1]
         if out is None:
-            out = torch.empty((self.n_channels, n), dtype=self.out_dtype, device=x.device) if self.out_bytes else _alloc_out(self.fout, self.n_channels, n, x.device)
+            out = _alloc_out(self.fout, self.n_channels, n, x.device, self.out_bytes)
         assert out.dtype == self.out_dtype and out.shape[1] >= n
         check(lib.acdsp_fir_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), n, C.c_void_p(out.data_ptr()),
                                 _row_stride(out, self.fout), _stream_ptr(x)))
@@ -270,18 +300,6 @@ class Fir:
         y = _alloc_out_host(self.fout, self.n_channels, x.shape[1], self.out_bytes)
         check(lib.acdsp_fir_run_host(self._h, x.ctypes.data_as(C.c_void_p), x.shape[1], y.ctypes.data_as(C.c_void_p)))
         return y
-
-    def state(self):
-        """Versioned state blob (bytes): input history / reg_trans of every channel (acdsp_fir_state_get)."""
-        buf = (C.c_char * lib.acdsp_fir_state_size(self._h))()
-        check(lib.acdsp_fir_state_get(self._h, buf, len(buf)))
-        return bytes(buf)
-
-    def set_state(self, blob):
-        check(lib.acdsp_fir_state_set(self._h, C.c_char_p(blob), len(blob)))
-
-    def reset(self):
-        check(lib.acdsp_fir_reset(self._h))
 
     def last_kernel_ms(self):
         ms = C.c_float()
@@ -300,21 +318,10 @@ class Fir:
         check(lib.acdsp_fir_mfma_issued(self._h, C.byref(v)))
         return v.value
 
-    def clone(self):
-        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_fir_clone)."""
-        return _clone(self, lib.acdsp_fir_clone)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.acdsp_fir_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-
-class Cic:
+class Cic(_Stateful):
     """n_channels independent ac_cic_dec_full (interp=False) / ac_cic_intr_full (interp=True) objects."""
+    _c = "cic"
 
     def __init__(self, interp, R, M, N, fin, fout, n_channels=1, device=0, force_generic=False, in_bytes=False):
         """in_bytes: decimator on an IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
@@ -322,7 +329,7 @@ class Cic:
         self.fin, self.fout, self.n_channels, self.device = fin, fout, n_channels, device
         self.in_bytes = bool(in_bytes)
         self._d = CicDesc(int(self.interp), R, M, N, n_channels, fin, fout, device,
-                          (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0))
+                          _flags(force_generic, in_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_cic_create(C.byref(self._d), C.byref(self._h)))
 
@@ -331,13 +338,6 @@ class Cic:
         it = Fmt()
         check(lib.acdsp_cic_int_type(C.byref(self._d), C.byref(it)))
         return it
-
-    @property
-    def in_dtype(self):
-        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
-        if self.in_bytes:
-            return torch.int8 if self.fin.S else torch.uint8
-        return torch_dtype_for(self.fin)
 
     @property
     def two_stage_rates(self):
@@ -378,18 +378,6 @@ class Cic:
                                      y.shape[1], C.byref(n_out)))
         return y[:, :n_out.value]
 
-    def state(self):
-        """Versioned state blob (bytes): input history and input count (phase) of every channel (acdsp_cic_state_get)."""
-        buf = (C.c_char * lib.acdsp_cic_state_size(self._h))()
-        check(lib.acdsp_cic_state_get(self._h, buf, len(buf)))
-        return bytes(buf)
-
-    def set_state(self, blob):
-        check(lib.acdsp_cic_state_set(self._h, C.c_char_p(blob), len(blob)))
-
-    def reset(self):
-        check(lib.acdsp_cic_reset(self._h))
-
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib.acdsp_cic_last_kernel_ms(self._h, C.byref(ms)))
@@ -400,21 +388,10 @@ class Cic:
         check(lib.acdsp_cic_kernel_stats(self._h, last_k, C.byref(a), C.byref(m)))
         return a.value, m.value
 
-    def clone(self):
-        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_cic_clone)."""
-        return _clone(self, lib.acdsp_cic_clone)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.acdsp_cic_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-
-class PolyDec:
+class PolyDec(_Stateful):
     """n_channels independent ac_poly_dec objects (NTAPS taps per branch, decimation DF)."""
+    _c = "polydec"
 
     def __init__(self, n_taps, df, fin, fcoeff, facc, fout, n_channels=1, device=0, force_generic=False, in_bytes=False):
         """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
@@ -422,7 +399,7 @@ class PolyDec:
         self.fin, self.fcoeff, self.facc, self.fout = fin, fcoeff, facc, fout
         self.in_bytes = bool(in_bytes)
         d = PolyDecDesc(n_taps, df, n_channels, fin, fcoeff, facc, fout, device,
-                        (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0))
+                        _flags(force_generic, in_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_polydec_create(C.byref(d), C.byref(self._h)))
 
@@ -430,13 +407,6 @@ class PolyDec:
         c = np.ascontiguousarray(coeffs, dtype=np.int64)
         assert c.shape == (self.n_taps * self.df,)
         check(lib.acdsp_polydec_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
-
-    @property
-    def in_dtype(self):
-        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
-        if self.in_bytes:
-            return torch.int8 if self.fin.S else torch.uint8
-        return torch_dtype_for(self.fin)
 
     @property
     def path(self):
@@ -475,32 +445,11 @@ class PolyDec:
         check(lib.acdsp_polydec_long_geometry(self._h, C.byref(slab), C.byref(group), C.byref(nbytes)))
         return slab.value, group.value, nbytes.value
 
-    def reset(self):
-        check(lib.acdsp_polydec_reset(self._h))
 
-    def state(self):
-        """Versioned state blob (bytes): input history of every channel (acdsp_polydec_state_get)."""
-        return _state_get(self._h, lib.acdsp_polydec_state_size, lib.acdsp_polydec_state_get)
-
-    def set_state(self, blob):
-        check(lib.acdsp_polydec_state_set(self._h, C.c_char_p(blob), len(blob)))
-
-    def clone(self):
-        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_polydec_clone)."""
-        return _clone(self, lib.acdsp_polydec_clone)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.acdsp_polydec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-
-class Ddc:
+class Ddc(_Stateful):
     """n_channels independent cascades ac_cic_dec_full(R, M, N) -> FIR on the decimator's lossless INT_TYPE words
     (C ABI acdsp_ddc_*): one fused kernel for the BASELINE config-5 shape class, the two stage kernels otherwise."""
+    _c = "ddc"
 
     def __init__(self, R, M, N, fin, n_taps, ftype, fcoeff, facc, fout, n_channels=1, kind="const", device=0, flags=0):
         self.fin, self.fout, self.n_channels, self.n_taps = fin, fout, n_channels, n_taps
@@ -539,46 +488,23 @@ class Ddc:
                                 C.byref(n_out), _stream_ptr(x)))
         return out[:, :n_out.value]
 
-    def state(self):
-        """Versioned state blob (bytes) of the cascade (acdsp_ddc_state_get)."""
-        buf = (C.c_char * lib.acdsp_ddc_state_size(self._h))()
-        check(lib.acdsp_ddc_state_get(self._h, buf, len(buf)))
-        return bytes(buf)
-
-    def set_state(self, blob):
-        check(lib.acdsp_ddc_state_set(self._h, C.c_char_p(blob), len(blob)))
-
-    def reset(self):
-        check(lib.acdsp_ddc_reset(self._h))
-
     def kernel_stats(self, last_k):
         a, m = C.c_float(), C.c_float()
         check(lib.acdsp_ddc_kernel_stats(self._h, last_k, C.byref(a), C.byref(m)))
         return a.value, m.value
 
-    def clone(self):
-        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_ddc_clone)."""
-        return _clone(self, lib.acdsp_ddc_clone)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.acdsp_ddc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
 
 POLY_FTYPES = {"FOLD_EVEN": 0, "FOLD_ODD": 1, "FOLD_ANTI": 2}   # the enum of ac_poly_intr.h:71
 
 
-class PolyIntr:
+class PolyIntr(_Stateful):
     """n_channels independent ac_poly_intr objects (C ABI acdsp_polyintr_*): IF outputs per input sample."""
+    _c = "polyintr"
 
     def __init__(self, n_taps, coeff_sz, ifac, ftype, fin, fcoeff, facc, fout, n_channels=1, device=0, force_generic=False):
         self.fin, self.fout, self.n_channels, self.coeff_sz, self.ifac = fin, fout, n_channels, coeff_sz, ifac
         d = PolyIntrDesc(n_taps, coeff_sz, ifac, POLY_FTYPES[ftype] if isinstance(ftype, str) else ftype, n_channels, fin, fcoeff,
-                         facc, fout, device, _lib.FLAG_FORCE_GENERIC if force_generic else 0)
+                         facc, fout, device, _flags(force_generic))
         self._h = C.c_void_p()
         check(lib.acdsp_polyintr_create(C.byref(d), C.byref(self._h)))
 
@@ -621,47 +547,19 @@ class PolyIntr:
         check(lib.acdsp_polyintr_long_geometry(self._h, C.byref(slab), C.byref(group), C.byref(nbytes)))
         return slab.value, group.value, nbytes.value
 
-    def reset(self):
-        check(lib.acdsp_polyintr_reset(self._h))
 
-    def state(self):
-        """Versioned state blob (bytes): input history, input count and saved sub-filter sums of every channel (acdsp_polyintr_state_get)."""
-        return _state_get(self._h, lib.acdsp_polyintr_state_size, lib.acdsp_polyintr_state_get)
-
-    def set_state(self, blob):
-        check(lib.acdsp_polyintr_state_set(self._h, C.c_char_p(blob), len(blob)))
-
-    def clone(self):
-        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_polyintr_clone)."""
-        return _clone(self, lib.acdsp_polyintr_clone)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.acdsp_polyintr_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-
-class IntgDump:
+class IntgDump(_Stateful):
     """n_objects independent ac_intg_dump<IN, ACC, OUT, N_TYPE, NS, CHN> objects (C ABI acdsp_intgdump_*); rows are the
     interleaved streams, n_sample the per-block N_TYPE words (shared by the objects)."""
+    _c = "intgdump"
 
     def __init__(self, ns, chn, fin, facc, fout, n_objects=1, device=0, in_bytes=False):
         """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8"""
         self.fin, self.fout, self.n_objects, self.chn = fin, fout, n_objects, chn
         self.in_bytes = bool(in_bytes)
-        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, device, _lib.FLAG_IN_BYTES if in_bytes else 0)
+        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, device, _flags(in_bytes=in_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_intgdump_create(C.byref(d), C.byref(self._h)))
-
-    @property
-    def in_dtype(self):
-        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
-        if self.in_bytes:
-            return torch.int8 if self.fin.S else torch.uint8
-        return torch_dtype_for(self.fin)
 
     def counts(self, n_sample):
         ns = np.ascontiguousarray(n_sample, dtype=np.int64)
@@ -698,46 +596,14 @@ class IntgDump:
         """kernel family of the last run() (acdsp_intgdump_path)"""
         return {0: "exact_order", 1: "tile", 2: "stream", 3: "mfma"}[lib.acdsp_intgdump_path(self._h)]
 
-    def reset(self):
-        check(lib.acdsp_intgdump_reset(self._h))
-
-    def state(self):
-        """Versioned state blob (bytes): temp[] of every object and the pending flag (acdsp_intgdump_state_get)."""
-        return _state_get(self._h, lib.acdsp_intgdump_state_size, lib.acdsp_intgdump_state_get)
-
-    def set_state(self, blob):
-        check(lib.acdsp_intgdump_state_set(self._h, C.c_char_p(blob), len(blob)))
-
-    def clone(self):
-        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_intgdump_clone)."""
-        return _clone(self, lib.acdsp_intgdump_clone)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.acdsp_intgdump_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
 
 WIN_MODES = {"WIN": 0, "MIRROR": 1, "CLIP": 2}   # AC_WIN / AC_MIRROR / AC_CLIP
 
 
-def _mvavg_flags(force_generic, in_bytes, out_bytes):
-    return (_lib.FLAG_FORCE_GENERIC if force_generic else 0) | (_lib.FLAG_IN_BYTES if in_bytes else 0) | (_lib.FLAG_OUT_BYTES if out_bytes else 0)
-
-
-def _byte_dtype(fmt, as_bytes):
-    """torch dtype of a row of `fmt` words: int8 / uint8 by signedness in 1-byte containers, else the format's own container"""
-    if as_bytes:
-        return torch.int8 if fmt.S else torch.uint8
-    return torch_dtype_for(fmt)
-
-
-class MvAvg:
+class MvAvg(_Handle):
     """n_objects independent ac_mv_avg<MAX_SAMPLE, TAPS, WIN_TYPE, ...> objects (C ABI acdsp_mvavg_*): rows hold n_frames
     frames of n_sample inputs back to back; run() is one run() call of every object."""
+    _c = "mvavg"
 
     def __init__(self, max_sample, taps, win_mode, fin, fcoeff, facc, fout, n_objects=1, device=0, force_generic=False, in_bytes=False,
                  out_bytes=False):
@@ -746,12 +612,9 @@ class MvAvg:
         self.fin, self.fout, self.n_objects, self.taps = fin, fout, n_objects, taps
         self.in_bytes, self.out_bytes = bool(in_bytes), bool(out_bytes)
         d = MvAvgDesc(max_sample, taps, WIN_MODES[win_mode] if isinstance(win_mode, str) else win_mode, n_objects, fin, fcoeff, facc,
-                      fout, device, _mvavg_flags(force_generic, in_bytes, out_bytes))
+                      fout, device, _flags(force_generic, in_bytes, out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_mvavg_create(C.byref(d), C.byref(self._h)))
-
-    in_dtype = property(lambda self: _byte_dtype(self.fin, self.in_bytes), doc="torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE")
-    out_dtype = property(lambda self: _byte_dtype(self.fout, self.out_bytes), doc="torch dtype of the output rows: int8 / uint8 containers under out_bytes, else the container of OUT_TYPE")
 
     def set_coeffs(self, coeffs):
         c = np.ascontiguousarray(coeffs, dtype=np.int64)
@@ -790,18 +653,6 @@ class MvAvg:
         check(lib.acdsp_mvavg_run_host(self._h, x.ctypes.data_as(C.c_void_p), n_sample, n_frames, y.ctypes.data_as(C.c_void_p), y.shape[1], C.byref(n_out)))
         return y[:, :n_out.value]
 
-    def clone(self):
-        """Deep copy, stream state included; the two objects are independent afterwards (acdsp_mvavg_clone)."""
-        return _clone(self, lib.acdsp_mvavg_clone)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib.acdsp_mvavg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
 
 def node_shard(n_total, n_shards, shard):
     """Channel slice [lo, hi) of shard `shard` (acdsp_node_shard: contiguous, the first n_total % n_shards slices one longer)."""
@@ -810,7 +661,7 @@ def node_shard(n_total, n_shards, shard):
     return lo.value, hi.value
 
 
-class _Node:
+class _Node(_Rows):
     """Common part of the node-level handles (acdsp_node_*): one filter bank cut into contiguous channel slices, one per entry of
     `devices` (a device may repeat: its shards are then concurrent streams of one GPU), one engine handle + stream + host thread each."""
 
@@ -841,11 +692,11 @@ class _Node:
             torch.cuda.current_stream(d).synchronize()
         return (C.c_void_p * self.n_shards)(*[t.data_ptr() for t in tensors]), strides.pop()
 
-    def alloc(self, fmt, n, fill=None):
-        """One [slice channels][n] device block per shard, on that shard's device."""
+    def alloc(self, fmt, n, fill=None, as_bytes=False):
+        """One [slice channels][n] device block per shard, on that shard's device (as_bytes: of 1-byte containers)."""
         out = []
         for (lo, hi), d in zip(self.slices, self.devices):
-            t = _alloc_out(fmt, hi - lo, n, torch.device("cuda", d))
+            t = _alloc_out(fmt, hi - lo, n, torch.device("cuda", d), as_bytes)
             if fill is not None:
                 fill(t, lo)
             out.append(t)
@@ -883,17 +734,10 @@ class NodeFir(_Node):
         self.in_bytes = bool(in_bytes)
         self.out_bytes = bool(out_bytes)
         d = FirDesc(KINDS[kind], FTYPES[ftype] if isinstance(ftype, str) else ftype, n_taps, n_channels, int(self.coeffs_per_channel),
-                    fin, fcoeff, facc, fout, 0, (_lib.FLAG_IN_BYTES if in_bytes else 0) | (_lib.FLAG_OUT_BYTES if out_bytes else 0))
+                    fin, fcoeff, facc, fout, 0, _flags(in_bytes=in_bytes, out_bytes=out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_node_fir_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
-
-    @property
-    def out_dtype(self):
-        """torch dtype of the output rows: int8 / uint8 containers under out_bytes, else the container of OUT_TYPE"""
-        if self.out_bytes:
-            return torch.int8 if self.fout.S else torch.uint8
-        return torch_dtype_for(self.fout)
 
     def set_coeffs(self, coeffs):
         c = np.ascontiguousarray(coeffs, dtype=np.int64)
@@ -905,10 +749,9 @@ class NodeFir(_Node):
         n = xs[0].shape[1]
         assert all(x.shape[1] == n for x in xs)
         if outs is None:
-            outs = ([torch.empty((hi - lo, n), dtype=self.out_dtype, device=torch.device("cuda", d)) for (lo, hi), d in zip(self.slices, self.devices)]
-                    if self.out_bytes else self.alloc(self.fout, n))
-        pin, sin = self._ptrs(xs, self.fin, (torch.int8 if self.fin.S else torch.uint8) if self.in_bytes else None)
-        pout, sout = self._ptrs(outs, self.fout, self.out_dtype if self.out_bytes else None)
+            outs = self.alloc(self.fout, n, as_bytes=self.out_bytes)
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
+        pout, sout = self._ptrs(outs, self.fout, self.out_dtype)
         check(lib.acdsp_node_fir_run(self._h, pin, sin, n, pout, sout))
         return outs
 
@@ -926,7 +769,7 @@ class NodeCic(_Node):
     def __init__(self, interp, R, M, N, fin, fout, n_channels, devices, in_bytes=False):
         self.fin, self.fout, self.n_channels = fin, fout, n_channels
         self.in_bytes = bool(in_bytes)
-        d = CicDesc(int(bool(interp)), R, M, N, n_channels, fin, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
+        d = CicDesc(int(bool(interp)), R, M, N, n_channels, fin, fout, 0, _flags(in_bytes=in_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_node_cic_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -940,7 +783,7 @@ class NodeCic(_Node):
         if outs is None:
             per64 = max(1, 64 // lib.acdsp_elem_bytes(self.fout.W))
             outs = self.alloc(self.fout, (max(no, 1) + per64 - 1) // per64 * per64)
-        pin, sin = self._ptrs(xs, self.fin, (torch.int8 if self.fin.S else torch.uint8) if self.in_bytes else None)
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
         pout, sout = self._ptrs(outs, self.fout)
         n_out = C.c_int64()
         check(lib.acdsp_node_cic_run(self._h, pin, sin, n_in, pout, sout, C.byref(n_out)))
@@ -988,7 +831,7 @@ class NodePolyDec(_Node):
     def __init__(self, n_taps, df, fin, fcoeff, facc, fout, n_channels, devices, in_bytes=False):
         self.fin, self.fout, self.n_channels, self.n_taps, self.df = fin, fout, n_channels, n_taps, df
         self.in_bytes = bool(in_bytes)
-        d = PolyDecDesc(n_taps, df, n_channels, fin, fcoeff, facc, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
+        d = PolyDecDesc(n_taps, df, n_channels, fin, fcoeff, facc, fout, 0, _flags(in_bytes=in_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_node_polydec_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -1003,7 +846,7 @@ class NodePolyDec(_Node):
         assert n_in % self.df == 0
         if outs is None:
             outs = self.alloc(self.fout, n_in // self.df + 8)
-        pin, sin = self._ptrs(xs, self.fin, (torch.int8 if self.fin.S else torch.uint8) if self.in_bytes else None)
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
         pout, sout = self._ptrs(outs, self.fout)
         check(lib.acdsp_node_polydec_run(self._h, pin, sin, n_in, pout, sout))
         return [o[:, :n_in // self.df] for o in outs]
@@ -1047,24 +890,17 @@ class NodeIntgDump(_Node):
     def __init__(self, ns, chn, fin, facc, fout, n_objects, devices, in_bytes=False):
         self.fin, self.fout, self.n_objects, self.ns, self.chn = fin, fout, n_objects, ns, chn
         self.in_bytes = bool(in_bytes)
-        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, 0, _lib.FLAG_IN_BYTES if in_bytes else 0)
+        d = IntgDumpDesc(ns, chn, n_objects, fin, facc, fout, 0, _flags(in_bytes=in_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_node_intgdump_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
-
-    @property
-    def in_dtype(self):
-        """torch dtype of the input rows: int8 / uint8 containers under in_bytes, else the container of IN_TYPE"""
-        if self.in_bytes:
-            return torch.int8 if self.fin.S else torch.uint8
-        return torch_dtype_for(self.fin)
 
     def run(self, xs, n_sample, outs=None):
         ns = np.ascontiguousarray(n_sample, dtype=np.int64)
         n_dump = int(((ns >= 1) & (ns <= self.ns)).sum()) * self.chn
         if outs is None:
             outs = self.alloc(self.fout, (max(n_dump, 1) + 7) // 8 * 8)
-        pin, sin = self._ptrs(xs, self.fin, self.in_dtype if self.in_bytes else None)
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
         pout, sout = self._ptrs(outs, self.fout)
         n_out = C.c_int64()
         check(lib.acdsp_node_intgdump_run(self._h, pin, sin, ns.ctypes.data_as(C.POINTER(C.c_int64)), len(ns), pout, sout, C.byref(n_out)))
@@ -1079,7 +915,7 @@ class NodeMvAvg(_Node):
         self.fin, self.fout, self.n_objects, self.taps = fin, fout, n_objects, taps
         self.in_bytes, self.out_bytes = bool(in_bytes), bool(out_bytes)
         d = MvAvgDesc(max_sample, taps, WIN_MODES[win_mode] if isinstance(win_mode, str) else win_mode, n_objects, fin, fcoeff, facc, fout, 0,
-                      _mvavg_flags(False, in_bytes, out_bytes))
+                      _flags(in_bytes=in_bytes, out_bytes=out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_node_mvavg_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -1089,15 +925,11 @@ class NodeMvAvg(_Node):
         assert c.shape == (self.taps,)
         check(lib.acdsp_node_mvavg_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
 
-    in_dtype = MvAvg.in_dtype
-    out_dtype = MvAvg.out_dtype
-
     def run(self, xs, n_sample, outs=None):
         n = xs[0].shape[1]
         assert n % n_sample == 0
         if outs is None:
-            outs = ([torch.empty((hi - lo, n), dtype=self.out_dtype, device=torch.device("cuda", d)) for (lo, hi), d in zip(self.slices, self.devices)]
-                    if self.out_bytes else self.alloc(self.fout, n))
+            outs = self.alloc(self.fout, n, as_bytes=self.out_bytes)
         pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
         pout, sout = self._ptrs(outs, self.fout, self.out_dtype)
         n_out = C.c_int64()

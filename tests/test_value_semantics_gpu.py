@@ -451,17 +451,71 @@ def relen_blob(blob, new_len, rng):
     return struct.pack("<8sIIIIQq4IQ", *hdr) + out.tobytes() + blob[64 + n_ch * per * eb:]
 
 
-@pytest.mark.parametrize("family", ["polydec", "polyintr"])
+CIC_IN, CIC_OUT = A.Fmt(16, 8), A.Fmt(31, 23)
+
+
+def cic_family(interp, n_ch, R=8, M=1, N=5):
+    def make():
+        return A.Cic(interp, R, M, N, CIC_IN, CIC_OUT, n_channels=n_ch)
+
+    def run(eng, x):
+        return host_words(eng.run(dev_rows(x, CIC_IN)))
+
+    def oracle():
+        orc = OracleCic(interp, R, M, N, ofmt(CIC_IN), ofmt(CIC_OUT), n_ch=n_ch)
+        return orc.run
+
+    return Family(make, run, oracle)
+
+
+def cic_pieces(n_ch, seed=10):
+    """a head of 333 samples: no multiple of R = 8, the decimation phase goes with the blob"""
+    x = rand_fmt(np.random.default_rng(seed), CIC_IN, (n_ch, 900))
+    return x[:, :333], x[:, 333:], None
+
+
+def fir_family(n_taps, ftype, n_ch, kind="load", seed=11):
+    c = rand_fmt(np.random.default_rng(seed), F16, (n_taps,))
+
+    def make():
+        eng = A.Fir(n_taps, ftype, F16, F16, FA40, FO, n_channels=n_ch, kind=kind)
+        eng.set_coeffs(c)
+        return eng
+
+    def run(eng, x):
+        return host_words(eng.run(dev_rows(x, F16)))
+
+    def oracle():
+        orc = OracleFir(n_taps, ftype, ofmt(F16), ofmt(F16), ofmt(FA40), ofmt(FO), n_ch=n_ch)
+        return lambda x: orc.run(c, x)
+
+    return Family(make, run, oracle)
+
+
+def blob_per_channel(blob):
+    import struct
+    return struct.unpack("<8sIIIIQq4IQ", blob[:64])[5]
+
+
+@pytest.mark.parametrize("family", ["polydec", "polyintr", "cic_dec", "cic_intr"])
 def test_history_blobs_of_another_length(family):
+    own = None                   # (CIC: read from the blob -- a handle that takes the two-stage kernel keeps a longer history)
     if family == "polydec":      # NTAPS*DF = 32: an output reaches 31 samples back, the handle keeps 64
         fam, (head, tail, _), mem, own = polydec_family(8, 4, 5), polydec_pieces(4, 5, 700), 31, 64
-    else:                        # NTAPS = 16: the sums of a call's first group reach 16 samples back, the handle keeps 32
+    elif family == "polyintr":   # NTAPS = 16: the sums of a call's first group reach 16 samples back, the handle keeps 32
         fam, (head, tail, _), mem, own = polyintr_family(16, 4, "FOLD_EVEN", 5), polyintr_pieces(5, 257, 700), 16, 32
+    elif family == "cic_dec":    # R = 8, M = 1, N = 5: the filter memory is N R M - 1 = 39 inputs
+        fam, (head, tail, _), mem = cic_family(False, 4), cic_pieces(4), 39
+    else:                        # the interpolator's memory: N M + 1 = 6 inputs
+        fam, (head, tail, _), mem = cic_family(True, 4), cic_pieces(4), 6
     rng = np.random.default_rng(9)
     want = fam.oracle()(fam.join(head, tail))
     a = fam.make()
     y_head = fam.run(a, head)
     blob = blob_of(a)
+    if own is None:
+        own = blob_per_channel(blob)
+        assert own > mem
     assert len(relen_blob(blob, own, rng)) == len(blob)
     for new_len in (own + 32, mem):
         r = fam.make()
@@ -473,3 +527,50 @@ def test_history_blobs_of_another_length(family):
     refuses(r, relen_blob(blob, mem - 1, rng), "a history shorter than the filter memory")
     refuses(r, relen_blob(blob, own + 32, rng)[:-2], "a longer history, truncated")
     assert r.state() == mine
+
+
+def test_fir_reg_trans_blob_of_another_length_is_refused():
+    """TRANSPOSED with loadable coefficients carries reg_trans partial sums (a kind-2 blob): no other length is this filter's state"""
+    import struct
+    fam = fir_family(40, "TRANSPOSED", 2)
+    eng = fam.make()
+    fam.run(eng, rand_fmt(np.random.default_rng(12), F16, (2, 300)))
+    mine = eng.state()
+    hdr = list(struct.unpack("<8sIIIIQq4IQ", mine[:64]))
+    assert hdr[2] == 2 and hdr[3] == 2 and hdr[5] == 40, hdr          # kind 2, 2 channels, n_taps words per channel
+    hdr[5] = 41
+    longer = struct.pack("<8sIIIIQq4IQ", *hdr) + mine[64:] + bytes(2 * hdr[4])
+    assert len(longer) == 64 + 2 * 41 * hdr[4]
+    refuses(eng, longer, "reg_trans words of another length")
+    assert eng.state() == mine
+    eng.close()
+
+
+def stateful_families():
+    fin, fa = A.Fmt(16, 8), A.Fmt(32, 16)
+    return {
+        "fir": fir_family(31, "SHIFT_REG", 3),
+        "cic": cic_family(False, 4),
+        "ddc": ddc_family(R=16, cin=A.Fmt(16, 1), n_taps=127, fc=A.Fmt(16, 1), fa=A.Fmt(60, 30), fo=A.Fmt(24, 9, True, "RND", "SAT"), n_ch=3),
+        "polydec": polydec_family(8, 4, 5),
+        "polyintr": polyintr_family(16, 4, "FOLD_EVEN", 5),
+        "intgdump": intgdump_family(16, 3, 5, fin, fa, fa),
+    }
+
+
+@pytest.mark.parametrize("name", ["fir", "cic", "ddc", "polydec", "polyintr", "intgdump"])
+def test_state_blob_messages(name):
+    import ctypes as C
+    eng = stateful_families()[name].make()
+    mine = eng.state()
+    with pytest.raises(A.AcdspError) as e:
+        eng.set_state(mine[:63])
+    assert e.value.code == EINVAL and str(e.value).endswith("%s_state_set: blob shorter than its header" % name), str(e.value)
+    size = getattr(A.lib, "acdsp_%s_state_size" % name)(eng._h)
+    assert size == len(mine)
+    buf = (C.c_char * size)()
+    assert getattr(A.lib, "acdsp_%s_state_get" % name)(eng._h, buf, size - 1) == EINVAL
+    msg = A.lib.acdsp_last_error().decode()
+    assert msg.startswith("%s_state_get: buffer of %d bytes" % (name, size - 1)) and "state needs %d" % size in msg, msg
+    assert eng.state() == mine
+    eng.close()
