@@ -15,6 +15,7 @@ PATHS = {0: "generic", 1: "lossless64", 2: "mfma_i8", 3: "mfma_gen", 4: "wide", 
 KCLASSES = {**PATHS, 6: "lossy16", 7: "satacc16"}
 FLAG_FORCE_GENERIC = 1
 FLAG_IN_BYTES = 2   # Fir / NodeFir, Cic / NodeCic (decimator), PolyDec / NodePolyDec, IntgDump / NodeIntgDump, MvAvg / NodeMvAvg: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES)
+DDC_IN_BYTES = 1    # Ddc / NodeDdc: ddc_flags of acdsp_ddc_create_ex (ACDSP_DDC_IN_BYTES) -- the cascade's rows and history in 1-byte containers; not a descriptor flag
 FLAG_OUT_BYTES = 4  # Fir / NodeFir, MvAvg / NodeMvAvg together with FLAG_IN_BYTES: OUT_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_OUT_BYTES)
 
 
@@ -128,6 +129,7 @@ SYMBOLS = {
     "acdsp_node_cic_out_count": (_i64, [_vp, _i64]),
     "acdsp_node_cic_run": (_i32, [_vp, C.POINTER(_vp), _i64, _i64, C.POINTER(_vp), _i64, C.POINTER(_i64)]),
     "acdsp_node_ddc_create": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), _i32, C.POINTER(_i32), C.POINTER(_vp)]),
+    "acdsp_node_ddc_create_ex": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), _i32, _i32, C.POINTER(_i32), C.POINTER(_vp)]),
     "acdsp_node_ddc_set_coeffs": (_i32, [_vp, C.POINTER(_i64)]),
     "acdsp_node_ddc_out_count": (_i64, [_vp, _i64]),
     "acdsp_node_ddc_run": (_i32, [_vp, C.POINTER(_vp), _i64, _i64, C.POINTER(_vp), _i64, C.POINTER(_i64)]),
@@ -244,6 +246,8 @@ SYMBOLS = {
     "acdsp_stream_read_header": (_i32, [C.c_char_p, C.POINTER(StreamHdr)]),
     "acdsp_stream_read": (_i32, [C.c_char_p, _vp, C.c_uint64]),
     "acdsp_ddc_create": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), C.POINTER(_vp)]),
+    "acdsp_ddc_create_ex": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), _i32, C.POINTER(_vp)]),
+    "acdsp_ddc_in_elem_bytes": (_i32, [_vp]),
     "acdsp_ddc_destroy": (_i32, [_vp]),
     "acdsp_ddc_set_coeffs": (_i32, [_vp, C.POINTER(_i64)]),
     "acdsp_ddc_out_count": (_i64, [_vp, _i64]),

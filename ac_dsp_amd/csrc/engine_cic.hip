@@ -91,9 +91,10 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   std::vector<uint32_t> fr;
   // decimator on the matrix cores through that identity (fir_gen.hip): where the taps have a plan at both ends of the window offsets
   // (byte rows: fir_gen.hip has no 1-byte shape -- every rate with a byte stage-1 shape goes to the two-stage kernel, the rest to the recurrence kernel)
-  h->gen_ok = !in_bytes && !desc->interp && !h->wide && !no_gen && fits_container(desc->in, h->in_eb) &&
-              fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 15, &probe, &fr) &&   // worst-case window offset
-              fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 0, &probe, &fr);
+  h->gen_plan_ok = !desc->interp && !h->wide && !no_gen &&
+                   fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 15, &probe, &fr) &&   // worst-case window offset
+                   fir_gen_plan(h->h_taps.data(), (int)h->h_taps.size(), desc->R, 0, &probe, &fr);
+  h->gen_ok = !in_bytes && fits_container(desc->in, h->in_eb) && h->gen_plan_ok;
   {
     // two-stage decimator (cic2.hip) where R = R1 R2 with a compiled stage-1 rate: its chunk 0 starts `wu` steps of 256 R1 inputs early,
     // so the handle keeps that much input history (the samples beyond the filter memory only ever feed warm-up values the combs cancel)

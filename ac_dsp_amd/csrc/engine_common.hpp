@@ -557,6 +557,7 @@ struct acdsp_cic {
   // decimator through its FIR identity on the matrix cores (fir_gen.hip): taps, and per (first mod 16) plans / fragments
   std::vector<int64_t> h_taps;
   bool gen_ok = false;
+  bool gen_plan_ok = false;      // ... its plan class alone, whatever the row containers (the byte cascade stands on it: engine_ddc.hip)
   PhasePlans gen;
   // decimator in two stages (cic2.hip): R = c2_R1 * c2_R2, stage-1 taps z^-(N-1) boxcar(R1)^N with their per (first mod 16) plans / fragments
   bool c2_ok = false;
@@ -583,7 +584,12 @@ struct acdsp_cic {
 struct acdsp_ddc {
   acdsp_cic_t cic = nullptr;     // stage A: parameter checks, INT_TYPE, FIR-identity taps; runs the stage in two-kernel mode
   acdsp_fir_t fir = nullptr;     // stage B: coefficient checks; runs the stage in two-kernel mode
-  bool fused = false;            // decided at creation / coefficient load; a handle never switches modes mid-stream
+  // what the caller handed to acdsp_ddc_create_ex: clone recreates from these -- under ACDSP_DDC_IN_BYTES the decimator stage itself was created
+  // from a copy carrying ACDSP_FLAG_IN_BYTES (cic->d), which the cascade's own entry point refuses
+  acdsp_cic_desc_t cic_desc;
+  acdsp_fir_desc_t fir_desc;
+  int32_t ddc_flags = 0;
+  bool fused = false;           // decided at creation / coefficient load; a handle never switches modes mid-stream
   // fused mode: the only state is the input history (stage B's window is recomputed from it) and the input count
   int hl = 0;
   History hist;

@@ -7,6 +7,48 @@ using namespace acdsp::eng;
 // ---------------------------------------------------------------------------------------------
 // DDC cascade: ac_cic_dec_full -> ac_fir_* on the decimator's lossless INT_TYPE words
 // ---------------------------------------------------------------------------------------------
+namespace acdsp {
+int ddc_flag_refusals(const acdsp_cic_desc_t &cic, const acdsp_fir_desc_t &fir, int32_t ddc_flags) {
+  if (ddc_flags & ~ACDSP_DDC_IN_BYTES) { return fail(ACDSP_EINVAL, "ddc: unknown bits 0x%x in ddc_flags", (unsigned)(ddc_flags & ~ACDSP_DDC_IN_BYTES)); }
+  if (fir.flags & ACDSP_FLAG_IN_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_IN_BYTES on the cascade's FIR (it reads the decimator's INT_TYPE words)"); }
+  if (cic.flags & ACDSP_FLAG_IN_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_IN_BYTES on the cascade's CIC decimator (the cascade kernel reads int16 rows)"); }
+  if ((fir.flags | cic.flags) & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_OUT_BYTES on a stage of the cascade (1-byte output rows: the FIR under both byte flags only)"); }
+  if ((ddc_flags & ACDSP_DDC_IN_BYTES) && cic.in.W > 8) { return fail(ACDSP_EINVAL, "ddc: ACDSP_DDC_IN_BYTES: IN_TYPE W=%d does not fit a 1-byte container", cic.in.W); }
+  return ACDSP_OK;
+}
+}  // namespace acdsp
+
+namespace {
+// The format part of both stages' kernel arguments (the per-call fields stay zero): what launch_cascade and cascade_shape_ok read
+void ddc_stage_params(const acdsp_ddc *h, FirParams *pa_out, FirParams *pb_out) {
+  const acdsp_cic_desc_t &cd = h->cic->d;
+  const acdsp_fir_desc_t &fd = h->fir->d;
+  FirParams &pa = *pa_out, &pb = *pb_out;
+  memset(&pa, 0, sizeof pa); memset(&pb, 0, sizeof pb);
+  pa.n_ch = cd.n_channels; pa.in = make_dfmt(cd.in); pa.out = make_dfmt(cd.out); pa.acc = pa.out; pa.cf = pa.in;
+  pa.in_eb = h->cic->in_eb; pa.out_eb = h->cic->out_eb; pa.hl = h->hl;
+  pb.n_ch = fd.n_channels; pb.in = make_dfmt(fd.in); pb.cf = make_dfmt(fd.coeff); pb.acc = make_dfmt(fd.acc); pb.out = make_dfmt(fd.out);
+  pb.in_eb = h->fir->in_eb; pb.out_eb = h->fir->out_eb;
+  pb.lossless_shift = pb.acc.F - pb.in.F - pb.cf.F;
+}
+
+// Does the fused kernel take this decimator and these formats at every window phase?  Asked at creation: a descriptor outside the compiled
+// families -- 8-bit samples in int16 rows, whose INT_TYPE has fewer than 33 bits, as much as a byte cascade at another rate -- runs the two
+// kernels instead of resolving to a fused handle whose every run() then fails with "shape outside the compiled cascade kernel".
+bool ddc_stage_a_ok(const acdsp_ddc *h) {
+  FirParams pa, pb;
+  ddc_stage_params(h, &pa, &pb);
+  const std::vector<int64_t> &taps = h->cic->h_taps;
+  for (int fm = 0; fm < 16; fm++) {
+    FirGenPlan pl;
+    std::vector<uint32_t> fr;
+    if (!fir_gen_plan(taps.data(), (int)taps.size(), h->cic->d.R, fm, &pl, &fr) || fr.size() > kGenFragWords ||
+        !cascade_shape_ok(pa, pl, h->cic->it.W, pb, nullptr)) { return false; }
+  }
+  return true;
+}
+}  // namespace
+
 extern "C" {
 
 int32_t acdsp_ddc_destroy(acdsp_ddc_t h) {
@@ -20,17 +62,22 @@ int32_t acdsp_ddc_destroy(acdsp_ddc_t h) {
   return ACDSP_OK;
 }
 
-int32_t acdsp_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, acdsp_ddc_t *out) {
+int32_t acdsp_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, acdsp_ddc_t *out) { return acdsp_ddc_create_ex(cic, fir, 0, out); }
+
+int32_t acdsp_ddc_create_ex(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t ddc_flags, acdsp_ddc_t *out) {
   if (!cic || !fir || !out) { return fail(ACDSP_EINVAL, "null argument"); }
+  int rc;
+  if ((rc = ddc_flag_refusals(*cic, *fir, ddc_flags))) { return rc; }
   if (cic->interp) { return fail(ACDSP_EINVAL, "ddc: stage A must be the decimator"); }
   if (cic->n_channels != fir->n_channels || cic->device != fir->device) { return fail(ACDSP_EINVAL, "ddc: both stages must cover the same channels on one device"); }
   if (fir->coeffs_per_channel) { return fail(ACDSP_EUNSUPPORTED, "ddc: one shared coefficient set"); }
-  if (fir->flags & ACDSP_FLAG_IN_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_IN_BYTES on the cascade's FIR (it reads the decimator's INT_TYPE words)"); }
-  if (cic->flags & ACDSP_FLAG_IN_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_IN_BYTES on the cascade's CIC decimator (the cascade kernel reads int16 rows)"); }
-  if ((fir->flags | cic->flags) & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "ddc: ACDSP_FLAG_OUT_BYTES on a stage of the cascade (1-byte output rows: the FIR under both byte flags only)"); }
+  const bool in_bytes = (ddc_flags & ACDSP_DDC_IN_BYTES) != 0;
   std::unique_ptr<acdsp_ddc, int32_t (*)(acdsp_ddc_t)> h(new acdsp_ddc(), acdsp_ddc_destroy);
-  int rc;
-  if ((rc = acdsp_cic_create(cic, &h->cic)) || (rc = acdsp_fir_create(fir, &h->fir))) { return rc; }
+  h->cic_desc = *cic; h->fir_desc = *fir; h->ddc_flags = ddc_flags;
+  // the container flag belongs to the composite; its decimator stage is the byte-row decimator
+  acdsp_cic_desc_t stage_a = *cic;
+  if (in_bytes) { stage_a.flags |= ACDSP_FLAG_IN_BYTES; }
+  if ((rc = acdsp_cic_create(&stage_a, &h->cic)) || (rc = acdsp_fir_create(fir, &h->fir))) { return rc; }
   // the cascade is lossless in the middle: the decimator writes its INT_TYPE and the FIR reads exactly that type
   const acdsp_fmt_t &it = h->cic->it;
   const bool same = [&](const acdsp_fmt_t &f) { return f.W == it.W && f.I == it.I && f.S == it.S; }(cic->out) && fir->in.W == it.W &&
@@ -39,8 +86,8 @@ int32_t acdsp_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fi
     return fail(ACDSP_EINVAL, "ddc: the decimator's OUT_TYPE and the FIR's IN_TYPE must both be the INT_TYPE <%d,%d>", it.W, it.I);
   }
   static const bool no_fuse = getenv("ACDSP_NO_FUSE") != nullptr;
-  h->fused = !no_fuse && h->cic->gen_ok && h->fir->lossless && !(fir->flags & ACDSP_FLAG_FORCE_GENERIC) &&
-             !(cic->flags & ACDSP_FLAG_FORCE_GENERIC) && h->cic->in_eb == 2 && h->fir->out_eb == 4;
+  h->fused = !no_fuse && h->fir->lossless && !(fir->flags & ACDSP_FLAG_FORCE_GENERIC) && !(cic->flags & ACDSP_FLAG_FORCE_GENERIC) && h->fir->out_eb == 4 &&
+             (in_bytes ? h->cic->gen_plan_ok : (h->cic->gen_ok && h->cic->in_eb == 2)) && ddc_stage_a_ok(h.get());
   if (h->fused) {
     h->hl = round_up(256 * cic->R + (int)h->cic->h_taps.size() + 48, 64);
     if ((rc = h->hist.init(cic->n_channels, h->hl, h->cic->in_eb)) || (rc = h->plansA.init()) ||
@@ -62,7 +109,7 @@ int32_t acdsp_ddc_set_coeffs(acdsp_ddc_t h, const int64_t *coeffs) {
     std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
     std::vector<uint32_t> fr;
     if (!fir_gen_plan(eff.data(), d.n_taps, 1, 0, &h->planB, &fr) || fr.size() > kGenFragWords || h->planB.nb > 3 ||
-        h->planB.pc > 2 || h->planB.off != 128) {
+        h->planB.pc > 2 || h->planB.off != 128) {   // (byte rows: stage B's plan class is the int16 cascade's, on four planes)
       if (h->t_total != 0) { return fail(ACDSP_EUNSUPPORTED, "ddc: this coefficient set does not fit the fused kernel and the stream has started"); }
       h->fused = false;   // before the first sample: the two kernels for the handle's lifetime
     } else {
@@ -79,7 +126,7 @@ int32_t acdsp_ddc_set_coeffs(acdsp_ddc_t h, const int64_t *coeffs) {
 int32_t acdsp_ddc_clone(acdsp_ddc_t h, acdsp_ddc_t *out) {
   if (!h || !out) { return fail(ACDSP_EINVAL, "null argument"); }
   acdsp_ddc_t c = nullptr;
-  int rc = acdsp_ddc_create(&h->cic->d, &h->fir->d, &c);
+  int rc = acdsp_ddc_create_ex(&h->cic_desc, &h->fir_desc, h->ddc_flags, &c);
   if (rc) { return rc; }
   std::unique_ptr<acdsp_ddc, int32_t (*)(acdsp_ddc_t)> guard(c, acdsp_ddc_destroy);
   // (the clone's stream has not started: a set that does not fit the fused kernel moves it to the two kernels, as it moved the original)
@@ -113,6 +160,8 @@ int64_t acdsp_ddc_out_count(acdsp_ddc_t h, int64_t n_in) {
 
 int32_t acdsp_ddc_path(acdsp_ddc_t h) { return h ? (h->fused ? 1 : 0) : -1; }
 
+int32_t acdsp_ddc_in_elem_bytes(acdsp_ddc_t h) { return h ? h->cic->in_eb : -1; }
+
 int32_t acdsp_ddc_reset(acdsp_ddc_t h) {
   if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
   int rc = acdsp_cic_reset(h->cic);
@@ -133,7 +182,6 @@ int32_t acdsp_ddc_run(acdsp_ddc_t h, const void *d_in, int64_t in_stride, int64_
   if (n_in == 0) { return ACDSP_OK; }
   if (no > 0 && (!d_out || out_stride < no)) { return fail(ACDSP_EINVAL, "ddc_run: output buffer too small for %lld outputs", (long long)no); }
   const acdsp_cic_desc_t &cd = h->cic->d;
-  const acdsp_fir_desc_t &fd = h->fir->d;
   int rc = check_device(cd.device);
   if (rc) { return rc; }
   hipStream_t s = (hipStream_t)stream;
@@ -192,13 +240,8 @@ int32_t acdsp_ddc_run(acdsp_ddc_t h, const void *d_in, int64_t in_stride, int64_
   h->plansA.get(fm, &planA, &fragA);
   if (!planA) { return fail(ACDSP_EUNSUPPORTED, "ddc_run (fused): decimator shape outside the fused kernel"); }
   FirParams pa, pb;
-  memset(&pa, 0, sizeof pa); memset(&pb, 0, sizeof pb);
-  pa.n_ch = cd.n_channels; pa.in = make_dfmt(cd.in); pa.out = make_dfmt(cd.out); pa.acc = pa.out; pa.cf = pa.in;
-  pa.in_eb = h->cic->in_eb; pa.out_eb = h->cic->out_eb; pa.hl = h->hl;
+  ddc_stage_params(h, &pa, &pb);
   pa.in_stride = in_stride; pa.n = n_in; pa.x = d_in; pa.hist = h->hist.cur();
-  pb.n_ch = fd.n_channels; pb.in = make_dfmt(fd.in); pb.cf = make_dfmt(fd.coeff); pb.acc = make_dfmt(fd.acc); pb.out = make_dfmt(fd.out);
-  pb.in_eb = h->fir->in_eb; pb.out_eb = h->fir->out_eb;
-  pb.lossless_shift = pb.acc.F - pb.in.F - pb.cf.F;
   pb.y = d_out; pb.out_stride = out_stride; pb.n = no;
   HIP_TRY(hipEventRecord(h->tm.start(), s));
   hipError_t e = launch_cascade(pa, *planA, fragA, h->cic->it.W, first, pb, h->planB, h->d_fragB.get<uint32_t>(), no, s);

@@ -1,7 +1,8 @@
 // fir_gen_kernels.hpp -- the kernels of the generalised exact FIR on the matrix cores (see fir_gen.hip for the formulation): the kernel
 // argument block, the four kernel templates and the plain functions their translation units call each other through.  A template is
 // compiled by whichever unit names an instantiation: fir_gen.hip (the window-per-step kernels), fir_gen_ring.hip (the ring kernel),
-// fir_gen_cascade.hip (the fused decimator -> FIR cascade).  Every instantiation is named in exactly one of them.
+// fir_gen_cascade.hip (the fused decimator -> FIR cascade; fir_gen_cascade_s8.hip: its byte-row family).  Every instantiation is named in
+// exactly one of them.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -828,10 +829,15 @@ __global__ void __launch_bounds__(64, 2) fir_gen_ring_kernel(FirParams p, const 
 //          offsets alive across the interior loop: 2 VGPRs of scratch at 256 registers.
 //   (Store bursts -- the tiles of 2 / 4 / 8 steps leaving as one contiguous burst -- were built and measured in round 4: no gain,
 //   profiles/r4_cascade_ablation.txt; removed.)
-template <int PXA, int PCA, int NBA, int SPLA, int PXB, int PCB, int NBB, bool GUARD, bool LIMB, int PART>
+//   TIN:   the container of the input rows.  int16_t: two sample planes (PXA = 2), a slot of 16 samples is two 16-byte pieces, stage A's
+//          words have 33 .. 40 bits (PXB = 5).  int8_t (ACDSP_DDC_IN_BYTES): ONE plane (PXA = 1) -- the 16-byte piece IS the slot and goes
+//          to LDS with one store, no byte gather and no re-bias (unsigned bytes: ^ 0x80, 128 * sum(h) in a.corr, which is non-zero for
+//          nothing else with one plane and doubles as the flag, as in fir_gen_kernel) -- and stage A's words have 25 .. 32 bits (PXB = 4).
+template <typename TIN, int PXA, int PCA, int NBA, int SPLA, int PXB, int PCB, int NBB, bool GUARD, bool LIMB, int PART>
 __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams pb, const v4i *__restrict__ fragA,
                                                        const v4i *__restrict__ fragB, GenArgs a, GenArgs b) {
-  typedef int16_t TIN;
+  constexpr bool BYTES = sizeof(TIN) == 1;
+  static_assert(BYTES ? PXA == 1 : (sizeof(TIN) == 2 && PXA == 2), "input rows: int8 on one plane or int16 on two");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // [A planes][B ring: PXB x 32 slots][1 KB output tile]
   const int lane = threadIdx.x;
   const int n_col = lane & 15, kg = lane >> 4;
@@ -860,16 +866,23 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
   const int64_t s1 = GUARD ? ((s0 + a.steps_per_wave < a.n_steps) ? s0 + a.steps_per_wave : a.n_steps) : s0 + a.steps_per_wave;
 
   // window loads coalesced over 16-byte pieces (8 samples; a slot is two pieces), as in fir_gen_fast_kernel
-  constexpr int NPCA = SPLA;   // 16-byte pieces per lane and step (ceil(n_slots * 2 / 64): 9 for R = 16, six K blocks)
+  constexpr int NPCA = SPLA;   // 16-byte pieces per lane and step (ceil(n_slots * 2 / 64): 9 for R = 16, six K blocks; byte rows: ceil(n_slots / 64) = 5)
   v4i pre[NPCA];
   int pc_off[NPCA], pc_ps[NPCA];
 #pragma unroll
   for (int k = 0; k < NPCA; k++) {
+    if constexpr (BYTES) {   // a piece is a slot
+      int slot = lane + 64 * k;
+      if (slot >= a.n_slots) { slot = a.n_slots - 1; }
+      pc_off[k] = 16 * slot;
+      pc_ps[k] = phys_slot(slot, a) * 16;
+    } else {
     int slot = (lane + 64 * k) / 2;
     const int sub = lane & 1;
     if (slot >= a.n_slots) { slot = a.n_slots - 1; }
     pc_off[k] = 16 * slot + 8 * sub;
     pc_ps[k] = phys_slot(slot, a) * 16 + 8 * sub;
+    }
   }
   // Interior chunks (every window of the chunk lies inside the call's samples: all but a row's first and last chunk) address
   // their pieces as uniform base + 16 bytes x lane + 1024 bytes x k -- no per-piece 64-bit selects; only the last two pieces,
@@ -886,7 +899,7 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
       const char *base = (const char *)(xrow + W0);
 #pragma unroll
       for (int k = 0; k < NPCA; k++) {
-        const unsigned off = k < NPCA - 2 ? lane16 + 1024u * k : 2u * (unsigned)pc_off[k];
+        const unsigned off = k < NPCA - 2 ? lane16 + 1024u * k : (unsigned)sizeof(TIN) * (unsigned)pc_off[k];
 #ifdef ACDSP_CASC_ABL_LOAD   // timing-only ablation: one load per step instead of nine
         if (k > 0) { pre[k] = pre[0]; continue; }
 #endif
@@ -901,9 +914,14 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
       }
     }
   };
+  const int fx = (BYTES && a.corr != 0) ? (int)0x80808080u : 0;   // unsigned bytes become x - 128
   auto stage_piece = [&](const v4i &v, int ps) {
+    if constexpr (BYTES) {
+      *(v4i *)(lds + ps) = v ^ (v4i){fx, fx, fx, fx};
+    } else {
 #pragma unroll
     for (int pp = 0; pp < PXA; pp++) { put_piece_plane<2, PXA>(v, pp, lds, plane_bytes, ps); }
+    }
   };
   int xs_of[NBA];
 #pragma unroll
@@ -924,9 +942,15 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
       if constexpr (LIMB) {
         // LDS offsets re-derived per piece rather than ten resident registers (the loop must not spill); the slot map is an add, so
         // the compiler folds the regular pieces into one base register + immediate offsets.
+        if constexpr (BYTES) {
+          int slot = lane + 64 * k;
+          if (k >= NPCA - 2 && slot >= a.n_slots) { slot = a.n_slots - 1; }
+          stage_piece(pre[k], phys_slot(slot, a) * 16);
+        } else {
         int slot = (lane >> 1) + 32 * k;
         if (k >= NPCA - 2 && slot >= a.n_slots) { slot = a.n_slots - 1; }
         stage_piece(pre[k], phys_slot(slot, a) * 16 + 8 * (lane & 1));
+        }
       } else {
         stage_piece(pre[k], pc_ps[k]);
       }
@@ -969,7 +993,20 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
     }
     // byte planes of the four words of this lane -> ring slot (st * 16 + n_col) & 31, bytes 4 kg .. 4 kg + 3
     const int wslot = (((int)(st & 1) * 16 + n_col) & 31) * 16 + 4 * kg;
-    if constexpr (LIMB) {
+    if constexpr (LIMB && BYTES) {
+      // y = acc_0 + (acc_1 << 8) + (acc_2 << 16) mod 2^32 (constant folded into the accumulators) holds the whole word: the INT_TYPE has
+      // at most 32 bits.  Planes 0 .. 2 are its low bytes, the top plane its signed field from bit 24 up to w_int (the wrap to INT_TYPE).
+      static_assert(PXA + PCA - 1 == 3 && PXB == 4, "limb epilogue on byte rows: three weight classes into four byte planes");
+      unsigned y[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) { y[r] = (unsigned)accA[0][r] + ((unsigned)accA[1][r] << 8) + ((unsigned)accA[2][r] << 16); }
+#pragma unroll
+      for (int pp = 0; pp < 3; pp++) { *(unsigned *)(ring + pp * 512 + wslot) = gather4(y[0], y[1], y[2], y[3], pp) ^ 0x80808080u; }
+      unsigned tb[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) { tb[r] = (unsigned)__builtin_amdgcn_sbfe((int)y[r], 24, a.w_int - 24); }
+      *(unsigned *)(ring + 3 * 512 + wslot) = gather4(tb[0], tb[1], tb[2], tb[3], 0);
+    } else if constexpr (LIMB) {
       // y = sum_w acc_w 2^(8w) is the exact word (constant folded into the accumulators): a byte carry chain in 32-bit
       // registers gives its bytes -- u_w = acc_w + (u_{w-1} >> 8), byte w = u_w & 255, the last u holds y >> 8 (NW - 1)
       static_assert(PXA + PCA - 1 == 4 && PXB == 5, "limb epilogue: four weight classes into five byte planes");
@@ -1032,12 +1069,13 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
     if constexpr (LIMB) {
       // z = sum_w acc_w 2^(8w) (exact; correction and rounding constant folded in) as two 32-bit limbs through 16-bit
       // carries; OUT = clamp(z >> rs): the high limb is clamped first so that the funnel shift cannot leave int32
-      static_assert(PXB + PCB - 1 == 6, "limb epilogue: six weight classes");
+      static_assert(PXB + PCB - 1 == (BYTES ? 5 : 6), "limb epilogue: six weight classes, five on byte rows");
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int p01 = accB[0][r] + (int)((unsigned)accB[1][r] << 8);
         const int p23 = accB[2][r] + (int)((unsigned)accB[3][r] << 8);
-        const int p45 = accB[4][r] + (int)((unsigned)accB[5][r] << 8);
+        int p45 = accB[4][r];
+        if constexpr (!BYTES) { p45 += (int)((unsigned)accB[5][r] << 8); }
         const int v1 = p23 + (p01 >> 16);
         int H = p45 + (v1 >> 16);                                                      // z >> 32
         const unsigned L = __builtin_amdgcn_perm((unsigned)v1, (unsigned)p01, 0x05040100u);   // z mod 2^32
@@ -1079,10 +1117,10 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
     {
       const int64_t W0 = a.first + (s0 - 1) * 256 * R - a.pl.off;
       const char *base = (const char *)(xrow + W0);
-      const int kskip = (8 * R * 32) / 1024;
+      const int kskip = (8 * R * 16 * (int)sizeof(TIN)) / 1024;
 #pragma unroll
       for (int k = 0; k < NPCA; k++) {
-        const unsigned off = k < NPCA - 2 ? lane16 + 1024u * k : 2u * (unsigned)pc_off[k];
+        const unsigned off = k < NPCA - 2 ? lane16 + 1024u * k : (unsigned)sizeof(TIN) * (unsigned)pc_off[k];
         if (k < NPCA - 2 && k < kskip) { pre[k] = (v4i){0, 0, 0, 0}; }
         else { pre[k] = *(const v4i *)(base + off); }
       }
@@ -1113,6 +1151,10 @@ __global__ void __launch_bounds__(64, 2) cascade_kernel(FirParams pa, FirParams 
 int gen_slot_map(GenArgs &a, int R, int n);
 bool gen_conv_params(const FirParams &p, int out_mode, int w_int, GenArgs *a, int src_bits = 0);
 int64_t gen_rebias_corr(int px, int64_t sum_h);
+
+// fir_gen_cascade_s8.hip: starts cascade_kernel<int8_t, 1, 3, 6, 5, 4, 2, 3, guard, limb, part> for launch_cascade (the byte-row family)
+hipError_t launch_cascade_s8(bool guard, bool limb, int part, dim3 grid, size_t lds_bytes, hipStream_t s, const FirParams &pa, const FirParams &pb,
+                             const v4i *fa, const v4i *fb, const GenArgs &a, const GenArgs &b);
 
 // fir_gen_ring.hip: the compiled shapes of fir_gen_ring_kernel, one row per instantiation <TIN, PX, PCT, NBT, R, OEB, SPW, PF, NT, FB, LZ>.
 // A plan takes the FIRST row with in_eb == sizeof(TIN), px == PX, pc <= PCT, nb <= NBT, oeb == OEB, pl.R == R and class B == LZ; the row's

@@ -200,6 +200,9 @@ struct SideStream {
 
 hipError_t launch_cascade(const FirParams &pa, const FirGenPlan &pla, const uint32_t *d_fragA, int w_int, int64_t first,
                           const FirParams &pb, const FirGenPlan &plb, const uint32_t *d_fragB, int64_t n_out, hipStream_t s);
+// does launch_cascade have a compiled shape and a branch-free conversion for these formats and plans (the per-call fields of pa / pb are not
+// read)?  plb == nullptr: stage A and the formats only -- what a handle knows before its coefficients
+bool cascade_shape_ok(const FirParams &pa, const FirGenPlan &pla, int w_int, const FirParams &pb, const FirGenPlan *plb);
 
 // Interpolating polyphase FIR on the matrix cores (fir_up.hip): z[n L + j] = sum_k E_j[k] x[n - k] mod 2^64.
 struct FirUpPlan {
@@ -278,6 +281,10 @@ int mv_avg_build_frags(const int64_t *c, int taps, int win_mode, int gran, uint3
 
 // Sets the calling thread's acdsp_last_error() message and returns `code` (engine.hip); for the layers above the engine (node.hip).
 int set_error(int code, const char *msg);
+// The refusals of acdsp_ddc_create_ex that depend on the flags alone, in its order and before any device use (engine_ddc.hip): unknown bits of
+// ddc_flags, a byte flag on a stage descriptor, ACDSP_DDC_IN_BYTES on samples wider than 8 bits.  acdsp_node_ddc_create_ex asks in front of its
+// threads and streams.
+int ddc_flag_refusals(const acdsp_cic_desc_t &cic, const acdsp_fir_desc_t &fir, int32_t ddc_flags);
 
 // Measurement kernels of acdsp_diag_* (diag.hip): a plain 16-byte-per-thread copy, and the stream + issued-MFMA envelope of a FIR row.
 hipError_t launch_diag_copy(const void *src, void *dst, int64_t bytes, hipStream_t s);

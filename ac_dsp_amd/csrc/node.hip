@@ -355,23 +355,29 @@ int32_t acdsp_node_cic_run(acdsp_node_t h, const void *const *d_in, int64_t in_s
 
 // ---- fused DDC ----
 int32_t acdsp_node_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t n_devices, const int32_t *devices, acdsp_node_t *out) {
+  return acdsp_node_ddc_create_ex(cic, fir, 0, n_devices, devices, out);
+}
+
+int32_t acdsp_node_ddc_create_ex(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t ddc_flags, int32_t n_devices, const int32_t *devices,
+                                 acdsp_node_t *out) {
   if (!cic || !fir) { return set_error(ACDSP_EINVAL, "node_ddc_create: null descriptor"); }
-  if (cic->flags & ACDSP_FLAG_IN_BYTES) { return set_error(ACDSP_EUNSUPPORTED, "node_ddc_create: ACDSP_FLAG_IN_BYTES on the cascade's CIC decimator (the cascade kernel reads int16 rows)"); }
-  acdsp_node *h = nullptr;
-  int rc = make_node(kNodeDdc, cic->n_channels, n_devices, devices, &h);
+  int rc = ddc_flag_refusals(*cic, *fir, ddc_flags);   // (in front of the threads and streams: before any device use)
   if (rc) { return rc; }
+  acdsp_node *h = nullptr;
+  if ((rc = make_node(kNodeDdc, cic->n_channels, n_devices, devices, &h))) { return rc; }
   h->n_taps = fir->n_taps;
-  // both stage descriptors take the slice's channel count and device
-  struct Stages { acdsp_cic_desc_t cic; acdsp_fir_desc_t fir; int32_t n_channels, device; };
-  const Stages both = {*cic, *fir, 0, 0};
+  // both stage descriptors -- the caller's own, with the cascade's flags beside them -- take the slice's channel count and device
+  struct Stages { acdsp_cic_desc_t cic; acdsp_fir_desc_t fir; int32_t ddc_flags; int32_t n_channels, device; };
+  const Stages both = {*cic, *fir, ddc_flags, 0, 0};
   rc = create_shards<Stages, acdsp_ddc_t>(h, both, &Stages::n_channels, [](const Stages *st, acdsp_ddc_t *e) {
     acdsp_cic_desc_t c = st->cic;
     acdsp_fir_desc_t f = st->fir;
     c.n_channels = f.n_channels = st->n_channels; c.device = f.device = st->device;
-    return acdsp_ddc_create(&c, &f, e);
+    return acdsp_ddc_create_ex(&c, &f, st->ddc_flags, e);
   });
   if (rc) { return rc; }
-  h->in_eb = acdsp_elem_bytes(cic->in.W); h->out_eb = acdsp_elem_bytes(fir->out.W);
+  h->in_eb = acdsp_ddc_in_elem_bytes((acdsp_ddc_t)h->shards[0].handle);   // 1 under ACDSP_DDC_IN_BYTES
+  h->out_eb = acdsp_elem_bytes(fir->out.W);
   *out = h;
   return ACDSP_OK;
 }

@@ -451,8 +451,11 @@ class Ddc(_Stateful):
     (C ABI acdsp_ddc_*): one fused kernel for the BASELINE config-5 shape class, the two stage kernels otherwise."""
     _c = "ddc"
 
-    def __init__(self, R, M, N, fin, n_taps, ftype, fcoeff, facc, fout, n_channels=1, kind="const", device=0, flags=0):
+    def __init__(self, R, M, N, fin, n_taps, ftype, fcoeff, facc, fout, n_channels=1, kind="const", device=0, flags=0, in_bytes=False):
+        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_DDC_IN_BYTES, a flag of the cascade and not of its stage descriptors, on
+        which `flags` lands): rows are torch.int8 / torch.uint8"""
         self.fin, self.fout, self.n_channels, self.n_taps = fin, fout, n_channels, n_taps
+        self.in_bytes = bool(in_bytes)
         probe = CicDesc(0, R, M, N, n_channels, fin, fin, device, flags)
         it = Fmt()
         check(lib.acdsp_cic_int_type(C.byref(probe), C.byref(it)))
@@ -461,7 +464,7 @@ class Ddc(_Stateful):
         fd = FirDesc(KINDS[kind], FTYPES[ftype] if isinstance(ftype, str) else ftype, n_taps, n_channels, 0, self.int_type, fcoeff,
                      facc, fout, device, flags)
         self._h = C.c_void_p()
-        check(lib.acdsp_ddc_create(C.byref(cd), C.byref(fd), C.byref(self._h)))
+        check(lib.acdsp_ddc_create_ex(C.byref(cd), C.byref(fd), _lib.DDC_IN_BYTES if in_bytes else 0, C.byref(self._h)))
 
     def set_coeffs(self, coeffs):
         c = np.ascontiguousarray(coeffs, dtype=np.int64)
@@ -477,7 +480,7 @@ class Ddc(_Stateful):
 
     def run(self, x, out=None):
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_channels and x.stride(1) == 1
-        assert x.dtype == torch_dtype_for(self.fin), (x.dtype, self.fin)
+        assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         n_in = x.shape[1]
         no = self.out_count(n_in)
         if out is None:
@@ -793,8 +796,10 @@ class NodeCic(_Node):
 class NodeDdc(_Node):
     """A Ddc bank sharded over `devices` (acdsp_node_ddc_*)."""
 
-    def __init__(self, R, M, N, fin, n_taps, ftype, fcoeff, facc, fout, n_channels, devices, kind="const"):
+    def __init__(self, R, M, N, fin, n_taps, ftype, fcoeff, facc, fout, n_channels, devices, kind="const", in_bytes=False):
+        """in_bytes: as for Ddc (ACDSP_DDC_IN_BYTES)"""
         self.fin, self.fout, self.n_channels, self.n_taps = fin, fout, n_channels, n_taps
+        self.in_bytes = bool(in_bytes)
         probe = CicDesc(0, R, M, N, n_channels, fin, fin, 0, 0)
         it = Fmt()
         check(lib.acdsp_cic_int_type(C.byref(probe), C.byref(it)))
@@ -802,7 +807,8 @@ class NodeDdc(_Node):
         cd = CicDesc(0, R, M, N, n_channels, fin, self.int_type, 0, 0)
         fd = FirDesc(KINDS[kind], FTYPES[ftype] if isinstance(ftype, str) else ftype, n_taps, n_channels, 0, self.int_type, fcoeff, facc, fout, 0, 0)
         self._h = C.c_void_p()
-        check(lib.acdsp_node_ddc_create(C.byref(cd), C.byref(fd), len(devices), self._dev_array(devices), C.byref(self._h)))
+        check(lib.acdsp_node_ddc_create_ex(C.byref(cd), C.byref(fd), _lib.DDC_IN_BYTES if in_bytes else 0, len(devices), self._dev_array(devices),
+                                           C.byref(self._h)))
         self._finish_create(devices)
 
     def set_coeffs(self, coeffs):
@@ -818,7 +824,7 @@ class NodeDdc(_Node):
         no = self.out_count(n_in)
         if outs is None:
             outs = self.alloc(self.fout, (max(no, 1) + 7) // 8 * 8)
-        pin, sin = self._ptrs(xs, self.fin)
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
         pout, sout = self._ptrs(outs, self.fout)
         n_out = C.c_int64()
         check(lib.acdsp_node_ddc_run(self._h, pin, sin, n_in, pout, sout, C.byref(n_out)))

@@ -451,7 +451,10 @@ private:
 template <class IN_TYPE, class INT_TYPE, class OUT_TYPE, class COEFF_TYPE, class ACC_TYPE>
 class ddc_engine {
 public:
-  ddc_engine(unsigned R, unsigned M, unsigned N, int fir_kind, int ftype, int n_taps, int n_channels = 1, int device = -1) {
+  // ddc_flags: ACDSP_DDC_* of acdsp_ddc_create_ex (ACDSP_DDC_IN_BYTES: in_bytes() == 1, input rows of 1-byte containers); the stage
+  // descriptors carry no byte flag -- the container belongs to the cascade
+  ddc_engine(unsigned R, unsigned M, unsigned N, int fir_kind, int ftype, int n_taps, int n_channels = 1, int device = -1, int ddc_flags = 0)
+      : ddc_flags_(ddc_flags) {
     acdsp_cic_desc_t c;
     c.interp = 0; c.R = (int32_t)R; c.M = (int32_t)M; c.N = (int32_t)N; c.n_channels = n_channels;
     c.in = fmt_of<IN_TYPE>(); c.out = fmt_of<INT_TYPE>(); c.device = device < 0 ? default_device() : device; c.flags = 0;
@@ -460,9 +463,10 @@ public:
     f.in = fmt_of<INT_TYPE>(); f.coeff = fmt_of<COEFF_TYPE>(); f.acc = fmt_of<ACC_TYPE>(); f.out = fmt_of<OUT_TYPE>();
     f.device = c.device; f.flags = 0;
     n_taps_ = n_taps;
-    check(acdsp_ddc_create(&c, &f, h_.slot()), "acdsp_ddc_create");
+    check(acdsp_ddc_create_ex(&c, &f, ddc_flags, h_.slot()), "acdsp_ddc_create_ex");
   }
-  // (copyable: acdsp_ddc_clone carries coefficients, kernel mode and the stream of both stages)
+  // (copyable: acdsp_ddc_clone carries the cascade's flags, coefficients, kernel mode and the stream of both stages)
+  int in_bytes() const { return (ddc_flags_ & ACDSP_DDC_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
   void set_coeffs(const COEFF_TYPE *c) {
     std::vector<int64_t> r((size_t)n_taps_);
     for (size_t i = 0; i < r.size(); i++) { r[i] = raw_of(c[i]); }
@@ -478,7 +482,7 @@ public:
 
 private:
   cloned_handle<acdsp_ddc_t, acdsp_ddc_clone, acdsp_ddc_destroy> h_;
-  int n_taps_;
+  int n_taps_, ddc_flags_;
 };
 
 // ---------------------------------------------------------------------------------------------

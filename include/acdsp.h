@@ -71,8 +71,10 @@ enum {
  * moves both ways; acdsp_intgdump_path below names its kernels.  A flagged ac_mv_avg handle has no state at all; acdsp_mvavg_path below names
  * its kernels (5, the byte-plane streaming kernel, or the container-agnostic 0 / 1).  in_stride stays in elements; the output containers are
  * unchanged unless ACDSP_FLAG_OUT_BYTES is set as well.  W > 8: ACDSP_EINVAL (every family; the only refusal of ac_intg_dump and ac_mv_avg);
- * ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its input stream is the thin one) and either stage of
- * acdsp_ddc_create / acdsp_node_ddc_create: ACDSP_EUNSUPPORTED, all before any device use.  INTEGRATION.md "Byte samples". */
+ * ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its input stream is the thin one) and either stage descriptor of
+ * acdsp_ddc_create[_ex] / acdsp_node_ddc_create[_ex]: ACDSP_EUNSUPPORTED, all before any device use -- the cascade takes byte rows through its
+ * own flag, ACDSP_DDC_IN_BYTES below: the FIR stage reads INT_TYPE words whatever the rows hold, so the container is a property of the
+ * composite, not of a stage.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_IN_BYTES 2
 /* acdsp_fir_desc_t::flags and acdsp_mvavg_desc_t::flags, and only together with ACDSP_FLAG_IN_BYTES.  OUT_TYPE has W <= 8 (signed or
  * unsigned) and travels in 1-BYTE containers: the rows acdsp_fir_run / acdsp_node_fir_run / acdsp_mvavg_run / acdsp_node_mvavg_run write and
@@ -85,6 +87,10 @@ enum {
  * kernels have no 1-byte output tile) and the flag on any other family's descriptor -- acdsp_{cic,polydec,polyintr,intgdump}_create, either
  * stage of acdsp_ddc_create: ACDSP_EUNSUPPORTED; then out.W > 8: ACDSP_EINVAL.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_OUT_BYTES 4
+/* ddc_flags of acdsp_ddc_create_ex / acdsp_node_ddc_create_ex (NOT a descriptor flag).  The decimator's IN_TYPE has W <= 8 (signed or unsigned)
+ * and the cascade's input rows, its input history and the history part of its state blob are 1-BYTE containers: int8_t rows, uint8_t for an
+ * unsigned IN_TYPE (acdsp_ddc_in_elem_bytes() == 1).  in_stride stays in elements; the output containers are those of the FIR's OUT_TYPE. */
+#define ACDSP_DDC_IN_BYTES 1
 
 /* which kernel family a FIR handle resolved to (acdsp_fir_path) */
 enum { ACDSP_PATH_GENERIC = 0, ACDSP_PATH_LOSSLESS64 = 1, ACDSP_PATH_MFMA_I8 = 2, ACDSP_PATH_MFMA_GEN = 3,
@@ -345,8 +351,18 @@ int32_t acdsp_polydec_long_geometry(acdsp_polydec_t h, int64_t *slab_outputs, in
  * the decimator's INT_TYPE (acdsp_cic_int_type).  For the BASELINE config-5 shape class (int16 input, 36-bit words,
  * <= 127 taps, int32 output containers) both stages run in ONE kernel and the INT_TYPE stream never reaches HBM
  * (acdsp_ddc_path = 1); otherwise the two stage kernels run back to back through an internal buffer (path 0).
- * Results are identical to running the two handles separately; state carries across calls like theirs. */
+ * Results are identical to running the two handles separately; state carries across calls like theirs.
+ * acdsp_ddc_create_ex takes ddc_flags (acdsp_ddc_create = flags 0).  ACDSP_DDC_IN_BYTES: 8-bit samples in 1-byte rows.  The fused kernel
+ * takes them on ONE sample plane for the same decimator class (R 16 N 5 and its neighbours) where the INT_TYPE has 25 .. 32 bits -- <8,1>
+ * samples: <28,21>, <8,8,false>: 29 bits -- with <= 127 taps in two coefficient digit planes and int32 output containers; every other byte
+ * cascade (other rates, an INT_TYPE below 25 bits, other output containers, ACDSP_NO_FUSE, ACDSP_FLAG_FORCE_GENERIC on a stage, a
+ * coefficient set outside the fused plan) runs the two stage kernels, the decimator as under ACDSP_FLAG_IN_BYTES.  Refusals, in this order and
+ * before any device use: null arguments; unknown bits in ddc_flags: ACDSP_EINVAL; ACDSP_FLAG_IN_BYTES / ACDSP_FLAG_OUT_BYTES on a stage
+ * descriptor: ACDSP_EUNSUPPORTED (1-byte OUTPUT rows are not part of the cascade); ACDSP_DDC_IN_BYTES with cic->in.W > 8: ACDSP_EINVAL; then
+ * everything acdsp_ddc_create checks.  Fused rows obey the 16-byte rule in units of the 1-byte container (ACDSP_EUNSUPPORTED otherwise). */
 int32_t acdsp_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, acdsp_ddc_t *out);
+int32_t acdsp_ddc_create_ex(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t ddc_flags, acdsp_ddc_t *out);
+int32_t acdsp_ddc_in_elem_bytes(acdsp_ddc_t h);                         /* 1 under ACDSP_DDC_IN_BYTES, else acdsp_elem_bytes(cic->in.W); -1 on a null handle */
 int32_t acdsp_ddc_destroy(acdsp_ddc_t h);
 int32_t acdsp_ddc_set_coeffs(acdsp_ddc_t h, const int64_t *coeffs);   /* FIR coefficients, raw COEFF_TYPE words [n_taps] */
 int64_t acdsp_ddc_out_count(acdsp_ddc_t h, int64_t n_in);
@@ -480,7 +496,8 @@ int64_t acdsp_cic_state_size(acdsp_cic_t h);
 int32_t acdsp_cic_state_get(acdsp_cic_t h, void *h_buf, uint64_t cap_bytes);
 int32_t acdsp_cic_state_set(acdsp_cic_t h, const void *h_buf, uint64_t bytes);
 /* cascade (acdsp_ddc_*): the input history and input count of the fused kernel (its FIR window is recomputed from them), or
- * the two stage blobs behind one header when the handle runs the stages as two kernels */
+ * the two stage blobs behind one header when the handle runs the stages as two kernels.  Under ACDSP_DDC_IN_BYTES the history words are
+ * 1-byte containers: such a blob moves between byte cascades of the same descriptors and is refused by every other handle (and theirs by it) */
 int64_t acdsp_ddc_state_size(acdsp_ddc_t h);
 int32_t acdsp_ddc_state_get(acdsp_ddc_t h, void *h_buf, uint64_t cap_bytes);
 int32_t acdsp_ddc_state_set(acdsp_ddc_t h, const void *h_buf, uint64_t bytes);
@@ -524,6 +541,9 @@ int32_t acdsp_node_cic_run(acdsp_node_t h, const void *const *d_in, int64_t in_s
                            int64_t *n_out);
 int32_t acdsp_node_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t n_devices, const int32_t *devices,
                               acdsp_node_t *out);
+/* ... with the ddc_flags of acdsp_ddc_create_ex (acdsp_node_ddc_create = flags 0): every shard is created from these descriptors and flags */
+int32_t acdsp_node_ddc_create_ex(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t ddc_flags, int32_t n_devices,
+                                 const int32_t *devices, acdsp_node_t *out);
 int32_t acdsp_node_ddc_set_coeffs(acdsp_node_t h, const int64_t *coeffs);
 int64_t acdsp_node_ddc_out_count(acdsp_node_t h, int64_t n_in);
 int32_t acdsp_node_ddc_run(acdsp_node_t h, const void *const *d_in, int64_t in_stride, int64_t n_in, void *const *d_out, int64_t out_stride,
