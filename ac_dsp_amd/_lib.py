@@ -199,6 +199,8 @@ SYMBOLS = {
     "acdsp_polyintr_run_host": (_i32, [_vp, _vp, _i64, _vp, _i64, C.POINTER(_i64)]),
     "acdsp_polyintr_reset": (_i32, [_vp]),
     "acdsp_polyintr_path": (_i32, [_vp]),
+    "acdsp_polyintr_in_elem_bytes": (_i32, [_vp]),
+    "acdsp_polyintr_out_elem_bytes": (_i32, [_vp]),
     "acdsp_polyintr_set_scratch_cap": (_i32, [_vp, C.c_uint64]),
     "acdsp_polyintr_long_geometry": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(C.c_uint64)]),
     "acdsp_intgdump_create": (_i32, [C.POINTER(IntgDumpDesc), C.POINTER(_vp)]),

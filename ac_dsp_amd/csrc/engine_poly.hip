@@ -337,7 +337,7 @@ struct acdsp_polyintr {
   // exact-accumulation class on the matrix cores (fir_up.hip): folded per-phase taps of the current control words
   bool up_ok = false;
   bool acc64_ok = false;        // a 64-bit ACC_TYPE whose sums the current control words keep inside 62 bits: the exact-accumulation class applies
-  int up_px = 2;                // input byte planes of the matrix-core kernel (= container bytes)
+  int up_px = 2;                // input byte planes of the matrix-core kernel (= container bytes; 1 under ACDSP_FLAG_IN_BYTES)
   FirUpPlan up_plan;
   uint32_t up_shmask = 0;
   int64_t up_max_abs = -1;      // bound on |z| of the folded taps (enables the 32-bit epilogue)
@@ -370,6 +370,7 @@ const char *polyintr_long_refusal(const acdsp_polyintr_desc_t &d) {
   if (nt > kPolyIntrLongMaxTaps) { return "more than 16384 taps per phase"; }
   if (d.flags & ACDSP_FLAG_FORCE_GENERIC) { return "ACDSP_FLAG_FORCE_GENERIC (the exact-order kernels end at NTAPS = 2048)"; }
   if (!d.in.S || d.in.W > 16) { return "an IN_TYPE that is unsigned or wider than 16 bits"; }
+  if (d.flags & ACDSP_FLAG_IN_BYTES) { return "ACDSP_FLAG_IN_BYTES (the long kernels read int16 rows; byte rows end at NTAPS = 2048, on the exact kernels)"; }
   if (d.coeff.S ? d.coeff.W > 16 : d.coeff.W > 15) { return "a COEFF_TYPE wider than 16 bits signed / 15 bits unsigned"; }
   if (!polyintr_lossless_desc(d)) {
     return "an ACC_TYPE that is not an exact accumulator (signed AC_WRAP, F_acc >= F_in + F_coeff, I_acc >= I_in + 1, W_acc <= 64)";
@@ -455,6 +456,8 @@ int32_t acdsp_polyintr_destroy(acdsp_polyintr_t h) {
 }
 
 int32_t acdsp_polyintr_path(acdsp_polyintr_t h) { return h ? h->last_path : -1; }
+int32_t acdsp_polyintr_in_elem_bytes(acdsp_polyintr_t h) { return h ? h->in_eb : -1; }
+int32_t acdsp_polyintr_out_elem_bytes(acdsp_polyintr_t h) { return h ? h->out_eb : -1; }
 
 int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_t *out) {
   if (!desc || !out) { return fail(ACDSP_EINVAL, "null argument"); }
@@ -479,16 +482,21 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
     const int f = fp > fa ? fp : fa;
     if (wp + (f - fp) > 125 || d.acc.W + (f - fa) > 125) { return fail(ACDSP_EUNSUPPORTED, "type combination needs more than 128-bit intermediates"); }
   }
+  // byte rows (ACDSP_FLAG_IN_BYTES, ACDSP_FLAG_OUT_BYTES with it): the common order of refusals, before the family's own
+  int in_eb, out_eb;
+  if ((rc = byte_rows("poly_intr", d.flags, d.in, d.out, "ACDSP_FLAG_OUT_BYTES needs ACDSP_FLAG_IN_BYTES (1-byte output rows exist on the byte-sample kernels only)",
+                      &in_eb, &out_eb))) {
+    return rc;
+  }
   // NTAPS above 2048: the long matrix-core kernels or nothing
   const char *const long_why = polyintr_long_refusal(d);
   if (d.n_taps > 2048 && long_why) {
     return fail(ACDSP_EUNSUPPORTED, "poly_intr: NTAPS=%d: more than 2048 taps run on the long matrix-core kernels only, which do not take %s", d.n_taps, long_why);
   }
-  if (d.flags & ACDSP_FLAG_OUT_BYTES) { return fail(ACDSP_EUNSUPPORTED, "poly_intr: ACDSP_FLAG_OUT_BYTES is not supported (1-byte output rows: the FIR under both byte flags only)"); }
   if ((rc = check_device(d.device))) { return rc; }
   std::unique_ptr<acdsp_polyintr> h(new acdsp_polyintr());   // (check_device has made the device current: a failure below frees there)
   h->d = d;
-  h->in_eb = elem_bytes(d.in.W); h->out_eb = elem_bytes(d.out.W);
+  h->in_eb = in_eb; h->out_eb = out_eb;
   h->hl = round_up(d.n_taps + 15, 32);
   if ((rc = h->hist.init(d.n_channels, h->hl, h->in_eb))) { return rc; }
   for (DevBuf &sv : h->d_saved) {
@@ -575,7 +583,7 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
     h->lplan = lpl;
     h->long_ok = true;
   }
-  // matrix-core path: exact-accumulation class, int16 samples, control words that keep the cores linear, and an
+  // matrix-core path: exact-accumulation class, int16 / int32 samples or int8 rows (ACDSP_FLAG_IN_BYTES: one plane), control words that keep the cores linear, and an
   // accumulator that cannot wrap (the symmetric-pair halving (t1 -/+ t2) >> 1 does not commute with a wrap)
   h->up_ok = false;
   static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
@@ -584,7 +592,7 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
   h->acc64_ok = lossless && d.acc.W == 64 && no_wrap;
   const int upx = h->in_eb;
   // (a long-capable handle has nt >= 65 taps per phase: fir_up_plan has no plan there)
-  if (!h->long_shape && no_wrap && !no_gen && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && (h->in_eb == 2 || h->in_eb == 4) && d.ifac <= 32) {
+  if (!h->long_shape && no_wrap && !no_gen && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && (h->in_eb == 1 || h->in_eb == 2 || h->in_eb == 4) && d.ifac <= 32) {
     std::vector<uint32_t> frag;
     std::vector<int64_t> ucorr;
     FirUpPlan pl;
@@ -698,7 +706,8 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
     const int64_t out_off = -(int64_t)p.skip * L, slot_a = h->up_plan.hs;
     const int64_t n_steps = (n_in / 16 - slot_a) / 32;
     // the tile stores need dword alignment only (gfx950 serves dword-aligned multi-dword stores): IF = 2 into 2-byte containers starts its
-    // first call one input's outputs = 4 bytes into the 8-byte grid
+    // first call one input's outputs = 4 bytes into the 8-byte grid.  1-byte rows: the first call of a folded core starts IF bytes in front
+    // of the row, so a factor that is no multiple of 4 leaves THAT call on the VALU kernels (later calls have out_off = 0)
     const int64_t oal = h->out_eb >= 8 ? 8 : 4;
     const bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && ((uintptr_t)d_out % oal == 0) &&
                          ((out_stride * h->out_eb) % oal == 0) && ((out_off * h->out_eb) % oal == 0);
@@ -804,7 +813,9 @@ int32_t acdsp_polyintr_clone(acdsp_polyintr_t h, acdsp_polyintr_t *out) {
   return ACDSP_OK;
 }
 
-// State blob, kind 7: the newest `hl` input samples of every channel, oldest first, in IN containers (taps[]), the input count in t_total
+// State blob, kind 7: the newest `hl` input samples of every channel, oldest first, in IN containers (taps[]; 1-byte ones under
+// ACDSP_FLAG_IN_BYTES: elem_bytes 1, so a flagged blob and an unflagged handle refuse each other, while ACDSP_FLAG_OUT_BYTES changes nothing --
+// the saved sums are ACC words -- and blobs move both ways between handles with and without it), the input count in t_total
 // (the folded cores emit nothing for the first sample of a stream) and, behind the histories, the sub-filter sums of the last sample
 // [channel][IF] as int64 ACC raw words (the bank of acc_a / acc_b that the next sample emits: formed with the control words of their own
 // time, so carried, not recomputed; all zero on FOLD_ANTI, which emits at once).

@@ -2,7 +2,7 @@
 //
 // The formulation, the mapping onto the matrix cores and the kernel itself are in fir_up_kernels.hpp.  This unit holds the host plan and
 // the dispatch and compiles the shape of 16-bit samples with two coefficient digit planes (launch_up_s221); fir_up_b.hip and fir_up_c.hip
-// compile the other shapes, for compile time.
+// compile the other shapes, for compile time; fir_up_s8.hip / fir_up_s8_b.hip those of byte samples (one sample plane).
 #include <stdlib.h>
 
 #include <vector>
@@ -68,6 +68,7 @@ bool fir_up_shape_ok(int in_eb, int px, int nb, int L, int out_eb) {
   if (nb < 1 || nb > 2 || (L != 2 && L != 4 && L != 8 && L != 16 && L != 7 && L != 3 && L != 5 && L != 6)) { return false; }
   if (in_eb == 2 && px == 2) { return out_eb == 2 || (out_eb == 4 && nb == 1) || out_eb == 8; }
   if (in_eb == 4 && px == 4) { return nb == 1 && out_eb == 8; }
+  if (in_eb == 1 && px == 1) { return out_eb == 1 || out_eb == 2; }   // byte samples (fir_up_s8.hip): 4- / 8-byte outputs stay on the VALU kernels
   return false;
 }
 
@@ -94,11 +95,11 @@ hipError_t launch_fir_up(const FirParams &p, const FirUpPlan &pl, int px, const 
     while (vb < 62 && (int64_t(1) << vb) <= max_abs_v) { vb++; }
     if (vb + p.lossless_shift + 1 < acc_bits) { acc_bits = vb + p.lossless_shift + 1; }
   }
-  if (mode == 0 && px == 2 && p.lossless_shift == 0 && rs >= 0 && rs <= 28 && p.out_eb == 2 &&
-      (p.out.Q == ACDSP_TRN || p.out.Q == ACDSP_RND) && (p.out.O == ACDSP_SAT || (p.out.O == ACDSP_WRAP && p.out.W == 16)) &&
+  if (mode == 0 && (px == 2 || px == 1) && p.lossless_shift == 0 && rs >= 0 && rs <= 28 && (p.out_eb == 2 || p.out_eb == 1) &&
+      (p.out.Q == ACDSP_TRN || p.out.Q == ACDSP_RND) && (p.out.O == ACDSP_SAT || (p.out.O == ACDSP_WRAP && p.out.W == 8 * p.out_eb)) &&
       max_abs_v >= 0 && max_abs_v < (int64_t(1) << 30)) {
     // 32-bit epilogue: poly_intr, no left shift into ACC_TYPE, |V| (+ rounding constant) inside int32; AC_SAT clamps, AC_WRAP at
-    // the container width is the truncation of the 16-bit store
+    // the container width is the truncation of the 16-bit (1-byte rows: 8-bit) store
     epi = 1;
     a.e_rs = rs;
     a.e_rnd = (p.out.Q == ACDSP_RND && rs > 0) ? (1 << (rs - 1)) : 0;
@@ -132,6 +133,12 @@ hipError_t launch_fir_up(const FirParams &p, const FirUpPlan &pl, int px, const 
   dim3 grid((unsigned)((n_steps + spw - 1) / spw), (unsigned)p.n_ch);
   // XCD-affine chunk order: loses 2 - 5 % on both interpolator rows in the one-shot form (profiles/r4_up_oneshot.txt); ACDSP_XCD_MAP=1 forces it
   a.xcd_map = (xcd_map_wanted(false) && ((int64_t)grid.x * grid.y) % 8 == 0) ? 1 : 0;
+  if (p.in_eb == 1) {
+    // byte samples: poly_intr only (the CIC interpolator's thin stream is refused under the flag); one sample plane, shapes as for int16
+    if (mode != 0) { return hipErrorNotSupported; }
+    if (pl.nb == 1 && pl.pc <= 2) { return launch_up_b121(a, d_frag, pl.L, p.out_eb, epi, grid, s); }
+    return pl.nb == 1 ? launch_up_b131(a, d_frag, pl.L, p.out_eb, epi, grid, s) : launch_up_b132(a, d_frag, pl.L, p.out_eb, epi, grid, s);
+  }
   if (p.in_eb == 2) {
     if (mode == 0) {
       // poly_intr: the pair taps E_j -+ E_cj can have 17 bits = 3 digit planes; sets whose folded taps stay inside two planes

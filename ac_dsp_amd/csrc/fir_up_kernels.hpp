@@ -1,6 +1,7 @@
 // fir_up_kernels.hpp -- the kernel of the exact interpolating (polyphase) FIR on the matrix cores and its launcher templates, shared by
-// the three translation units of the family: fir_up.hip (host plan, dispatch, the s221 shape), fir_up_b.hip (s231, s232) and fir_up_c.hip
-// (i421, i431).  A unit compiles the kernels of the shapes it defines and no others; fir_kernels.hpp stays the interface to the engine
+// the translation units of the family: fir_up.hip (host plan, dispatch, the s221 shape), fir_up_b.hip (s231, s232), fir_up_c.hip
+// (i421, i431) and, for byte samples (ACDSP_FLAG_IN_BYTES on ac_poly_intr: int8 rows, one sample plane, 1- or 2-byte outputs), fir_up_s8.hip
+// (b121, b131) and fir_up_s8_b.hip (b132).  A unit compiles the kernels of the shapes it defines and no others; fir_kernels.hpp stays the interface to the engine
 // layer.
 //
 //     z[n*L + j] = sum_{k < NT} E_j[k] * x[n - k]     (mod 2^64),   j = 0 .. L-1
@@ -106,26 +107,32 @@ struct UpArgs {
 template <typename TIN, int PX, int PCT, int NBT, int L, int OEB, int EPI, int NST>
 // (two waves per SIMD where the fragments + the register sets + accumulators need more than 168 registers: spills inside a step are
 // VMEM operations that every store-counting wait would have to drain)
-__global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0) ? 2 : 3)) fir_up_kernel(UpArgs a, const v4i *__restrict__ frag) {   // (factors that do not divide 32: sixteen-entry phase tables)
+// (byte samples: the six fragments of two K blocks beside the eight-entry phase tables of L = 16 and four register sets spill at 168)
+__global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0 || (sizeof(TIN) == 1 && NBT == 2 && L == 16)) ? 2 : 3)) fir_up_kernel(UpArgs a, const v4i *__restrict__ frag) {   // (factors that do not divide 32: sixteen-entry phase tables)
   constexpr int SPC = up_spc(L);                              // input samples per MFMA column
   constexpr int ROWS = SPC * L;                               // live rows of a tile (32 when L divides 32)
   constexpr int SS = 512;                                     // samples per step
   constexpr int G = 16 / SPC;                                 // MFMA groups (32 ROWS outputs each) per step
-  constexpr int NLD = (int)sizeof(TIN) / 2;                   // 1 KB loads per step
+  constexpr int NLD = (int)sizeof(TIN) / 2;                   // 1 KB loads per step (byte samples: none, the step rides behind the history)
+  constexpr bool BYTES = sizeof(TIN) == 1;                    // ACDSP_FLAG_IN_BYTES: the 16-byte loads ARE the one signed plane
+  static_assert(!BYTES || PX == 1, "byte samples are one plane");
+  static_assert(OEB != 1 || BYTES, "1-byte output tiles exist on the byte-sample kernels only");
   static_assert(NST >= 1 && NST <= 4, "up to four steps loaded up front");
   constexpr int HP = 32 * NBT;                                // history samples staged in front of a step
   constexpr int SPL = 16 / (int)sizeof(TIN);                  // samples per 16-byte load
   constexpr int NHL = HP / SPL;                               // lanes that load history
+  constexpr int NLL = BYTES ? NHL + SS / 16 : NHL;            // lanes whose load is staged (byte samples: history + the step's 32 lanes)
   constexpr int PLB = HP + SS + 16;                           // bytes of one plane array
   constexpr int FU = OEB == 8 ? 1 : ((OEB == 4 ? 2 : 4) < G ? (OEB == 4 ? 2 : 4) : G);   // groups per write-out
   constexpr int RUN = ROWS * OEB;                             // output bytes of one column
-  constexpr int UNIT = OEB == 2 ? 8 : 16;                     // bytes a lane writes per tile store
+  constexpr int UNIT = OEB == 1 ? 4 : (OEB == 2 ? 8 : 16);    // bytes a lane writes per tile store
   constexpr int RUNP = RUN + ((RUN / UNIT) % 2 == 0 ? UNIT : 0);   // column pitch of the tile: an odd number of store units (conflict-free writes)
   constexpr int NACC = PX + PCT - 1;
   constexpr int TS = up_tab_size<L>();
   static_assert(L >= 2 && L <= 16 && ROWS % 4 == 0 && ROWS <= 32, "live rows come in the accumulator groups of four");
   static_assert(G % FU == 0, "groups per write-out must divide the groups of a step");
-  static_assert((FU * 32 * RUN) % (OEB == 2 ? 1024 : 512) == 0, "whole store instructions per write-out");
+  static_assert((FU * 32 * RUN) % (OEB == 2 ? 1024 : 512) == 0, "whole store instructions per write-out");   // (1-byte outputs: 512, every compiled L)
+  static_assert(OEB != 1 || (RUN % 4 == 0 && RUNP % 4 == 0), "1-byte tiles are written and read in aligned dwords");
   __shared__ __attribute__((aligned(16))) unsigned char lds[PX * PLB + 64 * 16 + FU * 32 * RUNP];
   unsigned char *sink = lds + PX * PLB;                       // private dump of the lanes without a history load
   unsigned char *tile = sink + 64 * 16;
@@ -162,9 +169,9 @@ __global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0) ? 2
   const int64_t st0 = (int64_t)bx * a.steps_per_wave;
   const int64_t st1 = (st0 + a.steps_per_wave < a.n_steps) ? st0 + a.steps_per_wave : a.n_steps;
 
-  const int hl = lane < NHL ? lane : NHL - 1;                 // lanes past the history repeat its last load ...
+  const int hl = lane < NLL ? lane : NLL - 1;                 // lanes past the history repeat its last load ...
   // one register set per step of the chunk
-  v4i pre[NST][NLD], preh[NST];
+  v4i pre[NST][NLD > 0 ? NLD : 1], preh[NST];
   auto fetch = [&](int64_t st, auto set_c) {
     constexpr int S = decltype(set_c)::value;
     if (st > st1 - 1) { st = st1 - 1; }                       // past the chunk: the last step again (never consumed)
@@ -178,6 +185,11 @@ __global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0) ? 2
   // byte plane pp of the SPL samples in one 16-byte register set -> SPL bytes (put_piece_plane, mfma_planes.hpp)
   auto stage = [&](auto set_c) {
     constexpr int S = decltype(set_c)::value;
+    if constexpr (BYTES) {
+      // the first (HP + 512) / 16 lanes hold the plane array itself, in order: no v_perm, and no re-bias of a single signed plane
+      *(v4i *)(lane < NLL ? lds + lane * 16 : sink + lane * 16) = preh[S];
+      return;
+    }
 #pragma unroll
     for (int pp = 0; pp < PX; pp++) {
       unsigned char *pl = lds + pp * PLB;
@@ -195,7 +207,18 @@ __global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0) ? 2
     //   8-byte-per-lane form of round 3 (which had measured the same as 16 bytes under the round-3 plain-store policy);
     //   8-byte outputs (ac_cic_intr_full row): 8 bytes per lane, plain -- 16 bytes per lane 3.64 against 3.63 ms, and the non-temporal
     //   policy costs 13 % at either width (4.10 ms).
-    if constexpr (OEB == 2) {
+    if constexpr (OEB == 1) {
+      // 1-byte outputs: 8 bytes per lane (512 bytes per instruction divide the write-out of every compiled L; 16 bytes per lane would do so
+      // only where L divides 32), non-temporal as the 2-byte rows.  Two aligned dword reads: a column (20 .. 32 bytes, pitch a multiple of
+      // 4) is no multiple of 8 for L = 5 and 7, so an 8-byte piece may span two columns
+#pragma unroll
+      for (int k = 0; k < FU * 32 * RUN / 512; k++) {
+        const int lin = (k * 64 + lane) * 8;
+        const int c0 = lin / RUN, w0 = lin % RUN, c1 = (lin + 4) / RUN, w1 = (lin + 4) % RUN;
+        const v2u val = (v2u){*(const unsigned *)(tile + c0 * RUNP + w0), *(const unsigned *)(tile + c1 * RUNP + w1)};
+        __builtin_nontemporal_store(val, (v2u *)(yrow + e_unit * OEB + lin));
+      }
+    } else if constexpr (OEB == 2) {
 #pragma unroll
       for (int k = 0; k < FU * 32 * RUN / 1024; k++) {
         // two aligned 8-byte reads: the column pitch (72 bytes at 32 rows) is a multiple of 8, not of 16, and a DS access off its natural
@@ -342,7 +365,18 @@ __global__ void __launch_bounds__(64, ((PX * PCT * NBT >= 12 || 32 % L != 0) ? 2
         }
         unsigned char *dst = tile + ((g % FU) * 32 + c) * RUNP + (8 * g4 + 4 * h) * OEB;
         if (ROWS < 32 && 8 * g4 + 4 * h >= ROWS) { continue; }   // idle rows of a factor that does not divide 32
-        if (EPI == 1 || EPI == 3) {
+        if constexpr (OEB == 1) {
+          // four results of the lane = one dword of the column (v_perm: the low bytes of two words side by side, then the two halves)
+          unsigned lo2, hi2;
+          if constexpr (EPI == 1) {
+            lo2 = __builtin_amdgcn_perm((unsigned)o32[1], (unsigned)o32[0], 0x0c0c0400u);
+            hi2 = __builtin_amdgcn_perm((unsigned)o32[3], (unsigned)o32[2], 0x0c0c0400u);
+          } else {
+            lo2 = __builtin_amdgcn_perm((unsigned)o[1], (unsigned)o[0], 0x0c0c0400u);
+            hi2 = __builtin_amdgcn_perm((unsigned)o[3], (unsigned)o[2], 0x0c0c0400u);
+          }
+          *(unsigned *)dst = __builtin_amdgcn_perm(hi2, lo2, 0x05040100u);
+        } else if (EPI == 1 || EPI == 3) {
           if (OEB == 4) { *(v4i *)dst = (v4i){o32[0], o32[1], o32[2], o32[3]}; }
           else {
             *(v2u *)dst = (v2u){__builtin_amdgcn_perm((unsigned)o32[1], (unsigned)o32[0], 0x05040100u),
@@ -389,7 +423,8 @@ template <typename TIN, int PX, int PCT, int NBT, int L>
 static hipError_t launch_up_oeb(const UpArgs &a, const uint32_t *d_frag, int out_eb, int epi, dim3 grid, hipStream_t s) {
   const v4i *f = (const v4i *)d_frag;
   if (out_eb == 8) {
-    if (epi == 4) { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 8, 4, up_nst(L, 8, 4)>), grid, dim3(64), 0, s, a, f); }
+    if constexpr (sizeof(TIN) == 1) { return hipErrorNotSupported; }   // (byte samples into 4- / 8-byte rows stay on the VALU kernels)
+    else if (epi == 4) { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 8, 4, up_nst(L, 8, 4)>), grid, dim3(64), 0, s, a, f); }
     else if (epi == 2) { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 8, 2, up_nst(L, 8, 2)>), grid, dim3(64), 0, s, a, f); }
     else { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 8, 0, up_nst(L, 8, 0)>), grid, dim3(64), 0, s, a, f); }
   } else if (out_eb == 4) {
@@ -399,8 +434,19 @@ static hipError_t launch_up_oeb(const UpArgs &a, const uint32_t *d_frag, int out
       else if (epi == 0) { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 4, 0, up_nst(L, 4, 0)>), grid, dim3(64), 0, s, a, f); }
       else { return hipErrorNotSupported; }
     } else { return hipErrorNotSupported; }
-  } else if (out_eb == 2) {
-    if constexpr (sizeof(TIN) == 2) {
+  } else if (out_eb == 2 || out_eb == 1) {
+    if constexpr (sizeof(TIN) == 1) {   // byte samples (ACDSP_FLAG_IN_BYTES): poly_intr into 1- or 2-byte rows, 32-bit or generic epilogue
+      if (epi != 0 && epi != 1) { return hipErrorNotSupported; }
+      if (out_eb == 1) {
+        if (epi == 1) { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 1, 1, up_nst(L, 1, 1)>), grid, dim3(64), 0, s, a, f); }
+        else { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 1, 0, up_nst(L, 1, 0)>), grid, dim3(64), 0, s, a, f); }
+      } else {
+        if (epi == 1) { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 2, 1, up_nst(L, 2, 1)>), grid, dim3(64), 0, s, a, f); }
+        else { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 2, 0, up_nst(L, 2, 0)>), grid, dim3(64), 0, s, a, f); }
+      }
+    } else if (out_eb == 1) {
+      return hipErrorNotSupported;
+    } else if constexpr (sizeof(TIN) == 2) {
       if (epi == 1) {
         if constexpr (PCT == 3 || NBT == 1) { hipLaunchKernelGGL((fir_up_kernel<TIN, PX, PCT, NBT, L, 2, 1, up_nst(L, 2, 1)>), grid, dim3(64), 0, s, a, f); }
         else { return hipErrorNotSupported; }
@@ -443,5 +489,9 @@ hipError_t launch_up_s231(const UpArgs &a, const uint32_t *d_frag, int L, int ou
 hipError_t launch_up_s232(const UpArgs &a, const uint32_t *d_frag, int L, int out_eb, int epi, dim3 grid, hipStream_t s);   // fir_up_b.hip
 hipError_t launch_up_i421(const UpArgs &a, const uint32_t *d_frag, int L, int out_eb, int epi, dim3 grid, hipStream_t s);   // fir_up_c.hip
 hipError_t launch_up_i431(const UpArgs &a, const uint32_t *d_frag, int L, int out_eb, int epi, dim3 grid, hipStream_t s);   // fir_up_c.hip
+// poly_intr on byte samples (ACDSP_FLAG_IN_BYTES) = int8 rows, ONE sample plane, 2 or 3 digit planes, 1- or 2-byte outputs
+hipError_t launch_up_b121(const UpArgs &a, const uint32_t *d_frag, int L, int out_eb, int epi, dim3 grid, hipStream_t s);   // fir_up_s8.hip
+hipError_t launch_up_b131(const UpArgs &a, const uint32_t *d_frag, int L, int out_eb, int epi, dim3 grid, hipStream_t s);   // fir_up_s8.hip
+hipError_t launch_up_b132(const UpArgs &a, const uint32_t *d_frag, int L, int out_eb, int epi, dim3 grid, hipStream_t s);   // fir_up_s8_b.hip
 
 }  // namespace acdsp

@@ -443,7 +443,8 @@ int32_t acdsp_node_polyintr_create(const acdsp_polyintr_desc_t *desc, int32_t n_
   int rc = make_node(kNodePolyIntr, desc->n_channels, n_devices, devices, &h);
   if (rc) { return rc; }
   if ((rc = create_shards<acdsp_polyintr_desc_t, acdsp_polyintr_t>(h, *desc, &acdsp_polyintr_desc_t::n_channels, acdsp_polyintr_create))) { return rc; }
-  h->in_eb = acdsp_elem_bytes(desc->in.W); h->out_eb = acdsp_elem_bytes(desc->out.W);
+  h->in_eb = acdsp_polyintr_in_elem_bytes((acdsp_polyintr_t)h->shards[0].handle);     // 1 under ACDSP_FLAG_IN_BYTES
+  h->out_eb = acdsp_polyintr_out_elem_bytes((acdsp_polyintr_t)h->shards[0].handle);   // 1 under ACDSP_FLAG_OUT_BYTES
   *out = h;
   return ACDSP_OK;
 }

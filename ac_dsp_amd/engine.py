@@ -504,10 +504,14 @@ class PolyIntr(_Stateful):
     """n_channels independent ac_poly_intr objects (C ABI acdsp_polyintr_*): IF outputs per input sample."""
     _c = "polyintr"
 
-    def __init__(self, n_taps, coeff_sz, ifac, ftype, fin, fcoeff, facc, fout, n_channels=1, device=0, force_generic=False):
+    def __init__(self, n_taps, coeff_sz, ifac, ftype, fin, fcoeff, facc, fout, n_channels=1, device=0, force_generic=False, in_bytes=False,
+                 out_bytes=False):
+        """in_bytes: IN_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_IN_BYTES): rows are torch.int8 / torch.uint8
+        out_bytes (with in_bytes): OUT_TYPE of up to 8 bits in 1-byte containers (ACDSP_FLAG_OUT_BYTES): output rows are torch.int8 / torch.uint8"""
         self.fin, self.fout, self.n_channels, self.coeff_sz, self.ifac = fin, fout, n_channels, coeff_sz, ifac
+        self.in_bytes, self.out_bytes = bool(in_bytes), bool(out_bytes)
         d = PolyIntrDesc(n_taps, coeff_sz, ifac, POLY_FTYPES[ftype] if isinstance(ftype, str) else ftype, n_channels, fin, fcoeff,
-                         facc, fout, device, _flags(force_generic))
+                         facc, fout, device, _flags(force_generic, in_bytes, out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_polyintr_create(C.byref(d), C.byref(self._h)))
 
@@ -524,19 +528,29 @@ class PolyIntr(_Stateful):
 
     def run(self, x, out=None):
         assert x.is_cuda and x.dim() == 2 and x.shape[0] == self.n_channels and x.stride(1) == 1
-        assert x.dtype == torch_dtype_for(self.fin), (x.dtype, self.fin)
+        assert x.dtype == self.in_dtype, (x.dtype, self.fin)
         no = self.out_count(x.shape[1])
         if out is None:
-            out = torch.empty((self.n_channels, max(no, 1)), dtype=torch_dtype_for(self.fout), device=x.device)
-        assert out.shape[0] == self.n_channels and out.shape[1] >= no and out.stride(1) == 1 and out.dtype == torch_dtype_for(self.fout)
+            out = torch.empty((self.n_channels, max(no, 1)), dtype=self.out_dtype, device=x.device)
+        assert out.shape[0] == self.n_channels and out.shape[1] >= no and out.stride(1) == 1 and out.dtype == self.out_dtype
         n_out = C.c_int64()
         check(lib.acdsp_polyintr_run(self._h, C.c_void_p(x.data_ptr()), x.stride(0), x.shape[1], C.c_void_p(out.data_ptr()),
                                      out.stride(0), C.byref(n_out), _stream_ptr(x)))
         return out[:, :n_out.value]
 
+    def run_host(self, x):
+        """run() on host rows [n_channels][n] (numpy; int8 / uint8 under in_bytes) -> host rows [n_channels][n_out] of the output containers"""
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_np_in_dtype(self.fin, self.in_bytes))
+        assert x.shape[0] == self.n_channels
+        no = self.out_count(x.shape[1])
+        y = _alloc_out_host(self.fout, self.n_channels, max(no, 1), self.out_bytes)
+        n_out = C.c_int64()
+        check(lib.acdsp_polyintr_run_host(self._h, x.ctypes.data_as(C.c_void_p), x.shape[1], y.ctypes.data_as(C.c_void_p), y.shape[1], C.byref(n_out)))
+        return y[:, :n_out.value]
+
     @property
     def path(self):
-        """kernel family of the last run(): "generic", "lossless64" (tiled int64 VALU kernel), "mfma_gen" (fir_up.hip) or "mfma_long"
+        """kernel family of the last run(): "generic", "lossless64" (tiled int64 VALU kernel), "mfma_gen" (fir_up.hip; fir_up_s8.hip under in_bytes) or "mfma_long"
         (polyintr_long.hip: 65 taps per phase and more)"""
         return PATHS[lib.acdsp_polyintr_path(self._h)]
 
@@ -861,9 +875,12 @@ class NodePolyDec(_Node):
 class NodePolyIntr(_Node):
     """A PolyIntr bank sharded over `devices` (acdsp_node_polyintr_*)."""
 
-    def __init__(self, n_taps, coeff_sz, ifac, ftype, fin, fcoeff, facc, fout, n_channels, devices):
+    def __init__(self, n_taps, coeff_sz, ifac, ftype, fin, fcoeff, facc, fout, n_channels, devices, in_bytes=False, out_bytes=False):
+        """in_bytes / out_bytes: as for PolyIntr (ACDSP_FLAG_IN_BYTES, ACDSP_FLAG_OUT_BYTES)"""
         self.fin, self.fout, self.n_channels, self.ifac, self.coeff_sz = fin, fout, n_channels, ifac, coeff_sz
-        d = PolyIntrDesc(n_taps, coeff_sz, ifac, POLY_FTYPES[ftype] if isinstance(ftype, str) else ftype, n_channels, fin, fcoeff, facc, fout, 0, 0)
+        self.in_bytes, self.out_bytes = bool(in_bytes), bool(out_bytes)
+        d = PolyIntrDesc(n_taps, coeff_sz, ifac, POLY_FTYPES[ftype] if isinstance(ftype, str) else ftype, n_channels, fin, fcoeff, facc, fout, 0,
+                         _flags(in_bytes=in_bytes, out_bytes=out_bytes))
         self._h = C.c_void_p()
         check(lib.acdsp_node_polyintr_create(C.byref(d), len(devices), self._dev_array(devices), C.byref(self._h)))
         self._finish_create(devices)
@@ -882,9 +899,9 @@ class NodePolyIntr(_Node):
         n_in = xs[0].shape[1]
         no = self.out_count(n_in)
         if outs is None:
-            outs = self.alloc(self.fout, (max(no, 1) + 7) // 8 * 8)
-        pin, sin = self._ptrs(xs, self.fin)
-        pout, sout = self._ptrs(outs, self.fout)
+            outs = self.alloc(self.fout, (max(no, 1) + 7) // 8 * 8, as_bytes=self.out_bytes)
+        pin, sin = self._ptrs(xs, self.fin, self.in_dtype)
+        pout, sout = self._ptrs(outs, self.fout, self.out_dtype)
         n_out = C.c_int64()
         check(lib.acdsp_node_polyintr_run(self._h, pin, sin, n_in, pout, sout, C.byref(n_out)))
         return [o[:, :n_out.value] for o in outs]

@@ -559,12 +559,14 @@ private:
 template <class IN_TYPE, class COEFF_TYPE, class ACC_TYPE, class OUT_TYPE>
 class polyintr_engine {
 public:
+  // flags: ACDSP_FLAG_* of acdsp_polyintr_desc_t (ACDSP_FLAG_IN_BYTES: in_bytes() == 1, rows of 1-byte containers; with it ACDSP_FLAG_OUT_BYTES:
+  // out_bytes() == 1, output rows of 1-byte containers)
   polyintr_engine(int n_taps, int coeff_sz, int ifac, int ftype, int n_channels = 1, int device = -1, int flags = 0)
       : n_taps_(n_taps), coeff_sz_(coeff_sz), ifac_(ifac), ftype_(ftype), n_ch_(n_channels), device_(device < 0 ? default_device() : device), flags_(flags) {}
 
   int n_channels() const { return n_ch_; }
-  int in_bytes() const { return acdsp_elem_bytes(IN_TYPE::width); }
-  int out_bytes() const { return acdsp_elem_bytes(OUT_TYPE::width); }
+  int in_bytes() const { return (flags_ & ACDSP_FLAG_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
+  int out_bytes() const { return (flags_ & ACDSP_FLAG_OUT_BYTES) ? 1 : acdsp_elem_bytes(OUT_TYPE::width); }
   acdsp_polyintr_t handle() { ensure(); return h_.get(); }
   // the read_ctrl phase of the reference's run(): coeffs[coeff_sz] raw words, sign[ifac], corr[ifac]; uploaded only when they changed
   void set_ctrl_raw(const std::vector<int64_t> &c, const std::vector<unsigned char> &sign, const std::vector<unsigned char> &corr) {
@@ -578,6 +580,7 @@ public:
     ensure();
     check(acdsp_polyintr_run(h_.get(), d_in, in_stride, n_in, d_out, out_stride, n_out, stream), "acdsp_polyintr_run");
   }
+  // dense host rows [n_channels][n_in] of in_bytes() containers -> rows of out_cap containers of out_bytes()
   void run_host(const void *h_in, int64_t n_in, void *h_out, int64_t out_cap, int64_t *n_out) {
     ensure();
     check(acdsp_polyintr_run_host(h_.get(), h_in, n_in, h_out, out_cap, n_out), "acdsp_polyintr_run_host");

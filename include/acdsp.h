@@ -61,30 +61,36 @@ enum {
 
 /* flags */
 #define ACDSP_FLAG_FORCE_GENERIC 1 /* never pick the MFMA / fast kernels (parity tests) */
-/* acdsp_fir_desc_t::flags, acdsp_polydec_desc_t::flags, acdsp_intgdump_desc_t::flags, acdsp_mvavg_desc_t::flags, and acdsp_cic_desc_t::flags
- * of a decimator (interp == 0).  IN_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE containers: the caller's input rows, the
- * handle's history and the FIR / CIC / poly_dec state blob hold int8_t / uint8_t raw words (acdsp_fir_in_elem_bytes() /
- * acdsp_cic_in_elem_bytes() / acdsp_polydec_in_elem_bytes() / acdsp_intgdump_in_elem_bytes() / acdsp_mvavg_in_elem_bytes() == 1;
- * acdsp_elem_bytes() is not asked for the input).  A flagged ac_poly_dec handle resolves as an unflagged one does: ACDSP_PATH_MFMA_GEN on one
+/* acdsp_fir_desc_t::flags, acdsp_polydec_desc_t::flags, acdsp_polyintr_desc_t::flags, acdsp_intgdump_desc_t::flags, acdsp_mvavg_desc_t::flags,
+ * and acdsp_cic_desc_t::flags of a decimator (interp == 0).  IN_TYPE has W <= 8 (signed or unsigned) and travels in 1-BYTE containers: the
+ * caller's input rows, the handle's history and the FIR / CIC / poly_dec / poly_intr state blob hold int8_t / uint8_t raw words
+ * (acdsp_fir_in_elem_bytes() / acdsp_cic_in_elem_bytes() / acdsp_polydec_in_elem_bytes() / acdsp_polyintr_in_elem_bytes() /
+ * acdsp_intgdump_in_elem_bytes() / acdsp_mvavg_in_elem_bytes() == 1; acdsp_elem_bytes() is not asked for the input).  A flagged ac_poly_dec handle resolves as an unflagged one does: ACDSP_PATH_MFMA_GEN on one
  * sample plane where the ring / window kernels plan the shape, ACDSP_PATH_MFMA_S8 (polydec_s8.hip) on long prototypes, the exact-order kernel
  * elsewhere.  A flagged ac_intg_dump handle keeps no samples: its state blob (the ACC words of temp[]) is that of an unflagged handle and
  * moves both ways; acdsp_intgdump_path below names its kernels.  A flagged ac_mv_avg handle has no state at all; acdsp_mvavg_path below names
- * its kernels (5, the byte-plane streaming kernel, or the container-agnostic 0 / 1).  in_stride stays in elements; the output containers are
+ * its kernels (5, the byte-plane streaming kernel, or the container-agnostic 0 / 1).  A flagged ac_poly_intr handle keeps its history and the
+ * history part of its state blob (kind 7) in 1-byte containers, so its blobs and those of an unflagged handle refuse each other
+ * (ACDSP_EINVAL); acdsp_polyintr_path below names its kernels; its refusals beyond the common ones: more than 2048 taps (the long kernels read
+ * int16 rows): ACDSP_EUNSUPPORTED at create.  in_stride stays in elements; the output containers are
  * unchanged unless ACDSP_FLAG_OUT_BYTES is set as well.  W > 8: ACDSP_EINVAL (every family; the only refusal of ac_intg_dump and ac_mv_avg);
  * ACC_TYPE / OUT_TYPE wider than 64 bits, a CIC interpolator (interp == 1: its input stream is the thin one) and either stage descriptor of
  * acdsp_ddc_create[_ex] / acdsp_node_ddc_create[_ex]: ACDSP_EUNSUPPORTED, all before any device use -- the cascade takes byte rows through its
  * own flag, ACDSP_DDC_IN_BYTES below: the FIR stage reads INT_TYPE words whatever the rows hold, so the container is a property of the
  * composite, not of a stage.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_IN_BYTES 2
-/* acdsp_fir_desc_t::flags and acdsp_mvavg_desc_t::flags, and only together with ACDSP_FLAG_IN_BYTES.  OUT_TYPE has W <= 8 (signed or
+/* acdsp_fir_desc_t::flags, acdsp_mvavg_desc_t::flags and acdsp_polyintr_desc_t::flags, and only together with ACDSP_FLAG_IN_BYTES.  OUT_TYPE has W <= 8 (signed or
  * unsigned) and travels in 1-BYTE containers: the rows acdsp_fir_run / acdsp_node_fir_run / acdsp_mvavg_run / acdsp_node_mvavg_run write and
- * the output of the run_host calls hold int8_t / uint8_t raw words (acdsp_fir_out_elem_bytes() / acdsp_mvavg_out_elem_bytes() == 1), so a
+ * the output of the run_host calls hold int8_t / uint8_t raw words (acdsp_fir_out_elem_bytes() / acdsp_mvavg_out_elem_bytes() /
+ * acdsp_polyintr_out_elem_bytes() == 1; acdsp_polyintr_run / acdsp_node_polyintr_run / acdsp_polyintr_run_host likewise), so a
  * flagged handle's output row feeds a second handle under ACDSP_FLAG_IN_BYTES as it is (mv_avg -> FIR -> CIC decimator without a narrowing
  * pass).  out_stride stays in elements.  FIR rows take 16-byte stores where d_out % 16 == 0 and out_stride % 16 == 0, mv_avg rows 8-byte
- * stores where d_out, out_stride and the outputs per frame are multiples of 8; element stores elsewhere.  The handle resolves exactly as under
+ * stores where d_out, out_stride and the outputs per frame are multiples of 8, ac_poly_intr rows 8-byte stores from the matrix-core kernel where
+ * d_out, out_stride and the call's first output offset are multiples of 4 bytes (the first call of a folded core starts IF outputs in front
+ * of the row: with IF % 4 != 0 that one call runs the exact VALU kernels); element stores elsewhere.  The handle resolves exactly as under
  * ACDSP_FLAG_IN_BYTES alone (path, acdsp_fir_mfma_issued); the FIR state blob holds input history only and moves both ways between handles
- * with and without this flag.  Refusals, in this order and all before any device use: the flag without ACDSP_FLAG_IN_BYTES (the int16-sample
- * kernels have no 1-byte output tile) and the flag on any other family's descriptor -- acdsp_{cic,polydec,polyintr,intgdump}_create, either
+ * with and without this flag, and so does the ac_poly_intr blob (input history + ACC words).  Refusals, in this order and all before any device use: the flag without ACDSP_FLAG_IN_BYTES (the int16-sample
+ * kernels have no 1-byte output tile) and the flag on any other family's descriptor -- acdsp_{cic,polydec,intgdump}_create, either
  * stage of acdsp_ddc_create: ACDSP_EUNSUPPORTED; then out.W > 8: ACDSP_EINVAL.  INTEGRATION.md "Byte samples". */
 #define ACDSP_FLAG_OUT_BYTES 4
 /* ddc_flags of acdsp_ddc_create_ex / acdsp_node_ddc_create_ex (NOT a descriptor flag).  The decimator's IN_TYPE has W <= 8 (signed or unsigned)
@@ -386,7 +392,21 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
 int32_t acdsp_polyintr_run_host(acdsp_polyintr_t h, const void *h_in, int64_t n_in, void *h_out, int64_t out_cap, int64_t *n_out);
 int32_t acdsp_polyintr_reset(acdsp_polyintr_t h);
 int32_t acdsp_polyintr_clone(acdsp_polyintr_t h, acdsp_polyintr_t *out);   /* deep copy, stream state included: "clone" below */
-int32_t acdsp_polyintr_path(acdsp_polyintr_t h);   /* kernel family of the last run(): ACDSP_PATH_GENERIC, _LOSSLESS64, _MFMA_GEN or _MFMA_LONG */
+/* kernel family of the last run(): ACDSP_PATH_GENERIC, _LOSSLESS64, _MFMA_GEN or _MFMA_LONG.  Under ACDSP_FLAG_IN_BYTES: _MFMA_GEN (fir_up_s8.hip:
+ * the interpolating matrix-core kernel on one sample plane) for the exact-accumulation class as without the flag -- signed IN_TYPE, control
+ * words that keep the cores linear and the sums inside ACC_TYPE, IF one of 2 .. 8 or 16, at most two K blocks per phase (NTAPS + lag <= 65 - SPC, SPC = 16, 8, 4, 2 for IF 2, 3 .. 4, 5 .. 8, 16), calls of at least
+ * 544 / 576 samples -- into 1-byte (ACDSP_FLAG_OUT_BYTES) or 2-byte rows, with d_in % 16 == 0, in_stride % 16 == 0 and d_out, out_stride and
+ * the first output offset on 4 bytes; _LOSSLESS64 / _GENERIC elsewhere: unsigned IN_TYPEs (exact-order kernel, bit-exact), OUT_TYPEs in 4- / 8-byte
+ * rows, other alignments, 65 .. 2048 taps per phase; never _MFMA_LONG.  Refusals of acdsp_polyintr_create under the flags, in this order and
+ * all before any device use: in.W > 8 under ACDSP_FLAG_IN_BYTES: ACDSP_EINVAL; ACDSP_FLAG_OUT_BYTES without ACDSP_FLAG_IN_BYTES:
+ * ACDSP_EUNSUPPORTED; out.W > 8 under both: ACDSP_EINVAL; then NTAPS > 2048 under ACDSP_FLAG_IN_BYTES: ACDSP_EUNSUPPORTED. */
+int32_t acdsp_polyintr_path(acdsp_polyintr_t h);
+/* bytes of one INPUT / OUTPUT container of the handle: 1 under ACDSP_FLAG_IN_BYTES / ACDSP_FLAG_OUT_BYTES, else acdsp_elem_bytes(in.W) /
+ * acdsp_elem_bytes(out.W).  The state blob (kind 7) carries the input container width in its header: blobs of handles with and without
+ * ACDSP_FLAG_IN_BYTES refuse each other (ACDSP_EINVAL); its saved sums are ACC words, so blobs move both ways between handles with and
+ * without ACDSP_FLAG_OUT_BYTES. */
+int32_t acdsp_polyintr_in_elem_bytes(acdsp_polyintr_t h);
+int32_t acdsp_polyintr_out_elem_bytes(acdsp_polyintr_t h);
 /* Long sub-filters (NTAPS + lag >= 65 taps per phase, lag = 1 on the folded cores; up to 16384) of the exact-accumulation class on 16-bit
  * types run as IF matrix-core FIRs on the input stream.  Their phase rows go to a scratch buffer owned by the handle, and a second kernel
  * interleaves them into the caller's rows.  A call is walked as channel groups x time slabs so that the scratch stays under a cap (default
