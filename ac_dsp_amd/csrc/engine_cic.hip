@@ -86,7 +86,7 @@ int32_t acdsp_cic_create(const acdsp_cic_desc_t *desc, acdsp_cic_t *out) {
   h->warm = h->hl;
   // FIR identity of both directions: h = z^-(N-1) * boxcar(R*M')^N, all arithmetic mod 2^64 (then mod 2^outW)
   cic2_stage1_taps(desc->R * h->me, desc->N, &h->h_taps);
-  static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
+  const bool no_gen = knob_no_gen();
   FirGenPlan probe;
   std::vector<uint32_t> fr;
   // decimator on the matrix cores through that identity (fir_gen.hip): where the taps have a plan at both ends of the window offsets
@@ -238,8 +238,7 @@ int acdsp::eng::cic_capture_check(const acdsp_cic *h, const void *d_in, int64_t 
     return fail(ACDSP_ESTATE, "cic_run under graph capture: n_in = %lld is not a multiple of R = %d (a replay would repeat the captured decimation phase)",
                 (long long)n_in, d.R);
   }
-  const bool slots = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && in_stride >= (n_in + 15) / 16 * 16;
-  if (!slots) { return ACDSP_OK; }   // the recurrence kernel: no plan
+  if (!rows_in_slots(d_in, in_stride, h->in_eb, n_in)) { return ACDSP_OK; }   // the recurrence kernel: no plan
   const int fm = (int)(((d.R - h->t_total % d.R) % d.R) % 16);
   int st = -1;
   if (h->gen_ok && !h->c2_first) { st = h->gen.state(fm); }
@@ -277,7 +276,8 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   p.in_eb = h->in_eb; p.out_eb = h->out_eb;
   p.hl = h->hl; p.warm_tiles = h->warm / kCicTile;
   p.t_from = 0; p.emit_from = 0;
-  p.vec_ok = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0);
+  p.vec_ok = rows_vec_aligned(d_in, in_stride, h->in_eb);
+  const bool slots = rows_in_slots(d_in, in_stride, h->in_eb, n_in);
   p.out_simple = (p.out.F == p.in.F && p.out.O == ACDSP_WRAP) ? ((p.out.S && p.out.W >= h->it.W) ? 2 : 1) : 0;
   p.in_stride = in_stride; p.out_stride = out_stride; p.n_in = n_in;
   p.x = d_in; p.y = d_out; p.hist = h->hist.cur();
@@ -288,11 +288,11 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
   if (chunk < floor_chunk) { chunk = floor_chunk; }
   p.chunk = (chunk + kCicTile - 1) / kCicTile * kCicTile;
   // decimator on the matrix cores when the FIR identity fits and the rows are slot-aligned
-  bool use_gen = h->gen_ok && !h->c2_first && !d.interp && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
+  bool use_gen = h->gen_ok && !h->c2_first && !d.interp && slots;
   const uint32_t *gfrag = nullptr, *c2frag = nullptr;
   const FirGenPlan *gpl = nullptr, *c2pl = nullptr;
   const int fm = (int)(p.first % 16);
-  if (!capturing && (use_gen || (h->c2_ok && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16))) {
+  if (!capturing && (use_gen || (h->c2_ok && slots))) {
     // plans of this call's window phase, of the next call's and of phase 0: a capture that follows finds them uploaded (cic_capture_check)
     int fms[3];
     decimator_phases(d.R, h->t_total, n_in, fms);
@@ -305,7 +305,7 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
     use_gen = gpl != nullptr;
   }
   // ... or in two stages (R = R1 R2, cic2.hip) where the one-stage window does not fit: complete chunks there, the ragged end on the recurrence kernel
-  bool use_c2 = h->c2_ok && !use_gen && p.vec_ok && in_stride >= (n_in + 15) / 16 * 16;
+  bool use_c2 = h->c2_ok && !use_gen && slots;
   if (use_c2) {
     h->c2.get(fm, &c2pl, &c2frag);
     use_c2 = c2pl != nullptr;
@@ -319,13 +319,8 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
     pw.p = p; pw.out = make_wfmt(d.out);
     e = launch_cic_wide(pw, h->d_taps.get<int64_t>(), (int)h->h_taps.size(), no, s);
   } else if (use_gen) {
-    FirParams k;
-    memset(&k, 0, sizeof k);
-    k.n_ch = d.n_channels;
-    k.in = p.in; k.out = p.out; k.acc = p.out; k.cf = p.in;
-    k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl;
-    k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in;
-    k.x = d_in; k.y = d_out; k.hist = h->hist.cur();
+    FirParams k = fir_params_of(p.in, p.in, p.out, p.out, h->in_eb, h->out_eb, h->hl, d.n_channels, {d_in, in_stride, n_in, d_out, out_stride});
+    k.hist = h->hist.cur();
     e = launch_fir_gen(k, *gpl, gfrag, 1, h->it.W, p.first, no, s);
   } else if (use_intr_fir) {
     // whole steps of 32 input slots on the matrix cores; the head (history, earlier-call phase) and the tail (the call's
@@ -342,10 +337,7 @@ int32_t acdsp_cic_run(acdsp_cic_t h, const void *d_in, int64_t in_stride, int64_
       const int64_t oal = h->out_eb == 4 ? 4 : 8;
       const bool out_ok = ((uintptr_t)d_out % oal == 0) && ((out_stride * h->out_eb) % oal == 0) && ((out_off * h->out_eb) % oal == 0);
       if (n_steps > 0 && out_ok && (int64_t)d.R * (p.t_prev + 16 * slot_a) >= lo) {
-        FirParams k;
-        memset(&k, 0, sizeof k);
-        k.n_ch = d.n_channels; k.in = p.in; k.out = p.out; k.acc = p.out; k.cf = p.in;
-        k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in; k.x = d_in; k.y = d_out;
+        const FirParams k = fir_params_of(p.in, p.in, p.out, p.out, h->in_eb, h->out_eb, 0, d.n_channels, {d_in, in_stride, n_in, d_out, out_stride});
         e = launch_fir_up(k, h->up_plan, h->up_px, h->d_upfrag.get<uint32_t>(), h->d_upcorr.get<int64_t>(), 1, h->it.W, p.out_simple, 0, -1, slot_a, n_steps, out_off, s);
         if (e == hipSuccess) {
           q_a = (int64_t)d.R * (p.t_prev + 16 * slot_a); q_b = (int64_t)d.R * (p.t_prev + 16 * (slot_a + 32 * n_steps));

@@ -5,7 +5,9 @@
 // Building blocks of the handles, each the single owner of what the families used to spell out one by one: DevBuf (one device allocation),
 // History (the ping-pong input history), PhasePlans (per first % 16 fir_gen plans with their fragments), Staging + run_host_staged (the
 // host-buffer calls), sat_free_bound / fits_container (arithmetic of the path decisions), Timer (event ring), byte_rows (the byte-container
-// flags of a descriptor), and for the state blobs StateHdr with history_blob_fits (THE re-length rule), state_blob_get (every _state_get) and
+// flags of a descriptor), rows_in_slots / rows_vec_aligned (the row layout of the matrix-core kernels), fir_params_of (the FirParams of a
+// family that borrows a FIR kernel), long_or_nothing (a set on a long class: plan, upload or the refusal above 2048 taps), LongScratch (the
+// phase-row scratch of the long poly kernels), knob_no_gen / knob_no_sat_free (the shared A/B knobs), and for the state blobs StateHdr with history_blob_fits (THE re-length rule), state_blob_get (every _state_get) and
 // history_state_set (the _state_set of every input-history family).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -69,6 +71,10 @@ inline bool trace_handles() {
   static const bool t = getenv("ACDSP_TRACE") != nullptr;
   return t;
 }
+// A/B knobs more than one family reads, each read once per process.  ACDSP_NO_GEN: no multi-plane matrix-core kernels (fir_gen, fir_up, cic2);
+// ACDSP_NO_SAT_FREE: a saturating accumulator keeps its saturation whatever the coefficient set (sat_free_bound is never asked)
+inline bool knob_no_gen() { static const bool v = getenv("ACDSP_NO_GEN") != nullptr; return v; }
+inline bool knob_no_sat_free() { static const bool v = getenv("ACDSP_NO_SAT_FREE") != nullptr; return v; }
 
 inline int elem_bytes(int W) { return W <= 16 ? 2 : (W <= 32 ? 4 : (W <= 64 ? 8 : 16)); }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -488,6 +494,77 @@ inline int byte_rows(const char *prefix, int flags, const acdsp_fmt_t &in, const
   return ACDSP_OK;
 }
 
+// The row layout the vector loads of the matrix-core kernels want: a 16-byte aligned base and row pitch ...
+inline bool rows_vec_aligned(const void *d_in, int64_t in_stride, int in_eb) { return (uintptr_t)d_in % 16 == 0 && (in_stride * in_eb) % 16 == 0; }
+// ... and rows that lie in whole 16-sample slots: readable up to the next multiple of 16 samples
+inline bool rows_in_slots(const void *d_in, int64_t in_stride, int in_eb, int64_t n) { return rows_vec_aligned(d_in, in_stride, in_eb) && in_stride >= (n + 15) / 16 * 16; }
+
+// The rows of one call, and a zeroed FirParams filled from formats, container bytes, history length, channel count and those rows: what the
+// families that borrow a FIR kernel hand to it (poly_dec, poly_intr, CIC).  Everything else stays zero until the caller sets it.
+struct CallRows { const void *x; int64_t in_stride, n; void *y; int64_t out_stride; };
+inline FirParams fir_params_of(const DFmt &in, const DFmt &cf, const DFmt &acc, const DFmt &out, int in_eb, int out_eb, int hl, int n_ch, const CallRows &r) {
+  FirParams k;
+  memset(&k, 0, sizeof k);
+  k.n_ch = n_ch; k.in = in; k.cf = cf; k.acc = acc; k.out = out; k.in_eb = in_eb; k.out_eb = out_eb; k.hl = hl;
+  k.in_stride = r.in_stride; k.out_stride = r.out_stride; k.n = r.n; k.x = r.x; k.y = r.y;
+  return k;
+}
+
+// A planner of set_coeffs answers kTaken (the set runs on its kernel class, plan and device tables in place), kNotThisClass or an ACDSP_E* code (all positive)
+enum { kNotThisClass = 0, kTaken = -1 };
+
+// A coefficient set on a long matrix-core class (FIR long, FIR byte samples, poly_dec long) -- above 2048 taps the only class there is, so a
+// set that cannot go there is refused ("<what><n>: ...") where up to 2048 taps it is left to the other classes.  A set whose saturating
+// ACC_TYPE is not provably saturation-free (!lossless) cannot; plan(&frag, &corr) builds the family's plan and fragments and its correction
+// constant, with the family's own rule for re-biased samples, and answers false for a tap that does not split into two signed bytes.
+template <typename Plan>
+int long_or_nothing(const char *what, int n, bool lossless, DevBuf &d_frag, DevBuf &d_corr, Plan plan) {
+  if (!lossless) {
+    if (n <= 2048) { return kNotThisClass; }
+    return fail(ACDSP_EUNSUPPORTED, "%s%d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", what, n);
+  }
+  std::vector<uint32_t> frag;
+  int64_t corr = 0;
+  if (!plan(&frag, &corr)) {
+    if (n <= 2048) { return kNotThisClass; }
+    return fail(ACDSP_EUNSUPPORTED, "%s%d: a coefficient of 32640 or more cannot be split into two signed bytes, and more than 2048 taps run on the matrix cores only", what, n);
+  }
+  int rc;
+  if ((rc = d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = d_corr.upload(&corr, sizeof corr))) { return rc; }
+  return kTaken;
+}
+
+// The scratch of the phase rows of a long poly_dec / poly_intr handle: cap, geometry and buffer, sized at create / set_scratch_cap / clone,
+// never in run().  init(): rows of `sample_bytes` per slab sample behind a head of `head` samples, n_ch channels, under the default cap.
+struct LongScratch {
+  uint64_t cap = (uint64_t)128 << 20;
+  LongGeom geo = {0, 0, 0};
+  DevBuf buf;
+  uint64_t sample_bytes = 0, head = 0;   // the rows (init)
+  int n_ch = 0;
+  int init(uint64_t sample_bytes_, uint64_t head_, int n_ch_) {
+    sample_bytes = sample_bytes_; head = head_; n_ch = n_ch_;
+    return size(cap);
+  }
+  // under `new_cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a failure leaves cap,
+  // geometry and scratch as they were
+  int size(uint64_t new_cap) {
+    const LongGeom g = long_geometry(sample_bytes, head, n_ch, new_cap);
+    DevBuf fresh;
+    const int rc = fresh.alloc(g.bytes);
+    if (rc) { return rc; }
+    buf = std::move(fresh);   // (the old buffer goes with `fresh`)
+    geo = g; cap = new_cap;
+    return ACDSP_OK;
+  }
+  // the out-parameters of acdsp_*_long_geometry (null ones skipped); zeros for a handle that is not long
+  void geometry(bool is_long, int64_t *slab, int32_t *group, uint64_t *bytes) const {
+    if (slab) { *slab = is_long ? geo.slab : 0; }
+    if (group) { *group = is_long ? geo.group : 0; }
+    if (bytes) { *bytes = is_long ? geo.bytes : 0; }
+  }
+};
+
 }  // namespace eng
 }  // namespace acdsp
 
@@ -504,7 +581,7 @@ struct acdsp_fir {
   bool use_rt, lossless, coeffs_set;
   // AC_SAT / AC_SAT_SYM / AC_SAT_ZERO accumulators (round 5): lossless_shape = the exact-sum conditions with the overflow mode left out (create);
   // sat_free = no partial sum of the CURRENT coefficient set can reach the type's bounds, so the saturation is dead code and the handle
-  // runs the classes of a wrapping accumulator (set_coeffs; every FirParams of the handle then carries AC_WRAP: fir_acc_fmt)
+  // runs the classes of a wrapping accumulator (set_coeffs; every FirParams of the handle then carries AC_WRAP: fir_params)
   bool lossless_shape = false, sat_free = false;
   bool wide = false;   // ACC_TYPE or OUT_TYPE wider than 64 bits: wide.hip (reg_trans words are then 16 bytes)
   bool small_call = false;   // set by run_host around a call that fits the pinned buffers (launch-bound: see acdsp_fir_run)
@@ -523,24 +600,26 @@ struct acdsp_fir {
   int64_t rt_since = 0;         // samples since the last coefficient change / state load, saturating at n_taps - 1
   int cur_rt = 0;               // rt_hybrid: index of the current reg_trans buffer (the history has its own)
   DevBuf d_coeffs;
-  DevBuf d_frag;                // [n_sets][2][nb][64][4] Toeplitz byte-plane fragments
-  DevBuf d_corr;                // [n_sets] 128 * sum(c)
+  // The selected plan.  `path` names the kernel class that took the current coefficient set (the planners of set_coeffs, engine_fir.hip, tried
+  // in the order below; the first that takes the set ends the sequence), and the plan data of that class is the only plan data that is valid:
+  //   ACDSP_PATH_MFMA_S8     lplan, s8_sum_abs, d_frag, d_corr   (ACDSP_FLAG_IN_BYTES, fir_s8.hip)
+  //   ACDSP_PATH_MFMA_LONG   lplan, d_frag, d_corr, in_flip      (1026 .. 16384 taps, fir_long.hip)
+  //   ACDSP_PATH_MFMA_I8     plan, mfma_cshift, d_frag [n_sets][2][nb][64][4] Toeplitz byte-plane fragments, d_corr [n_sets] 128 * sum(c), in_flip
+  //   ACDSP_PATH_MFMA_GEN    gplan, d_gfrag                      (the generalised multi-plane kernel, fir_gen.hip)
+  //   ACDSP_PATH_MFMA_LOSSY  gplan, d_gfrag, lzp, d_lzcl         (class B, fir_gen_ring.hip: plan of the effective taps + residue table)
+  // At most one class can take a set, by the shapes they admit: byte samples need 1-byte rows, long at least 1026 taps of rows that are not
+  // bytes, int8 MFMA 2-byte rows and at most 33 K-blocks (1025 taps), gen rows of at least 2 bytes, and lossy an accumulator that is NOT
+  // lossless where the other four need a lossless one.  gen admits the shapes of long and int8 MFMA too: it is their fall-back, reached only
+  // when their two-byte split fails.  set_coeffs checks the other pairs on every call ("internal: ...": fir_second_class_admits).
+  DevBuf d_frag, d_corr;
   FirMfmaPlan plan;             // worst case over the coefficient sets (bounds for the epilogue choice)
-  bool mfma_ok = false;
-  int mfma_cshift = 0;          // the fragments hold the coefficients scaled by 2^mfma_cshift (narrow types: engine_fir.hip, set_coeffs)
-  // 1026 .. 16384 taps (fir_long.hip): long_shape = the descriptor is long-eligible (create), long_ok = the current set runs there; d_frag /
-  // d_corr hold its fragments
-  bool long_shape = false, long_ok = false;
+  int mfma_cshift = 0;          // the fragments hold the coefficients scaled by 2^mfma_cshift (narrow types: engine_fir.hip, fir_plan_i8)
+  bool long_shape = false;      // the descriptor is long-eligible (create)
   FirLongPlan lplan;
-  // ACDSP_FLAG_IN_BYTES (fir_s8.hip): in_eb == 1; s8_shape = the descriptor is byte-eligible (create), s8_ok = the current set runs there; lplan,
-  // d_frag / d_corr hold its plan and fragments, s8_sum_abs = sum |c| of the effective taps (the 32-bit epilogue's bound)
-  bool s8_shape = false, s8_ok = false;
-  int64_t s8_sum_abs = 0;
-  DevBuf d_gfrag;               // fragments of the generalised (wide-input) MFMA kernel
+  bool s8_shape = false;        // the descriptor is byte-eligible (create): in_eb == 1
+  int64_t s8_sum_abs = 0;       // sum |c| of the effective taps (the 32-bit epilogue's bound)
+  DevBuf d_gfrag;
   FirGenPlan gplan;
-  bool gen_ok = false;
-  // class B on the matrix cores (fir_gen_ring.hip, LZ ring shapes): gplan / d_gfrag hold the plan of the effective taps, lzp the residue table
-  bool lz_ok = false;
   FirLossyPlan lzp;
   DevBuf d_lzcl;
   int64_t n_runs = 0;             // run() calls that launched kernels (ACDSP_TRACE)

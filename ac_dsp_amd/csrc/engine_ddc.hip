@@ -215,8 +215,7 @@ int32_t acdsp_ddc_run(acdsp_ddc_t h, const void *d_in, int64_t in_stride, int64_
     return rc;
   }
   // fused: alignment is the only per-call requirement
-  if ((uintptr_t)d_in % 16 || (in_stride * h->cic->in_eb) % 16 || in_stride < (n_in + 15) / 16 * 16 || (uintptr_t)d_out % 16 ||
-      (out_stride * h->fir->out_eb) % 16) {
+  if (!rows_in_slots(d_in, in_stride, h->cic->in_eb, n_in) || !rows_vec_aligned(d_out, out_stride, h->fir->out_eb)) {
     return fail(ACDSP_EUNSUPPORTED, "ddc_run (fused): rows must be 16-byte aligned and readable up to a multiple of 16 samples");
   }
   const int R = cd.R;

@@ -4,23 +4,30 @@
 using namespace acdsp;
 using namespace acdsp::eng;
 
-// ACC_TYPE as the kernels see it: a saturating accumulator that cannot saturate for the handle's coefficient set is a wrapping one
-static inline DFmt fir_acc_fmt(const acdsp_fir *h) {
-  DFmt a = make_dfmt(h->d.acc);
-  if (h->sat_free) { a.O = ACDSP_WRAP; }
-  return a;
-}
-
-// the handle's formats as the class queries of the int8 MFMA kernel see them (epilogue class, register residency, MFMAs issued): the
-// fragments hold the coefficients scaled by 2^cshift, so COEFF_TYPE has cshift more fraction bits there (set_coeffs)
-static FirParams fir_class_params(const acdsp_fir *h, int cshift) {
+// The handle-constant half of every FirParams of a handle: formats, container bytes, history length, tap order, the handle's buffers.  What a
+// call adds: its rows, hist_next, t_begin, in_flip.  ACC_TYPE as the kernels see it: a saturating accumulator that cannot saturate for the
+// handle's coefficient set is a wrapping one.  Wider than 64 bits: wide.hip takes ACC_TYPE / OUT_TYPE from FirWideParams, F_acc alone stays
+static FirParams fir_params(const acdsp_fir *h) {
+  const acdsp_fir_desc_t &d = h->d;
   FirParams k;
   memset(&k, 0, sizeof k);
-  k.in = make_dfmt(h->d.in); k.cf = make_dfmt(h->d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(h->d.out);
-  k.cf.F += cshift;
-  k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
+  k.n_taps = d.n_taps; k.ftype = internal_ftype(d.kind, d.ftype); k.n_ch = d.n_channels; k.coeffs_per_channel = d.coeffs_per_channel;
+  k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff);
+  if (h->wide) { k.acc.F = d.acc.W - d.acc.I; }
+  else { k.acc = make_dfmt(d.acc); k.out = make_dfmt(d.out); }
+  if (h->sat_free) { k.acc.O = ACDSP_WRAP; }
+  k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl; k.use_rt = (h->use_rt && !h->rt_hybrid) ? 1 : 0;
+  k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
+  k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>(); k.rt = fir_rt_cur(h);
   return k;
 }
+// ... as the int8 MFMA kernel and its class queries see them (epilogue class, register residency, MFMAs issued): the fragments hold the
+// coefficients scaled by 2^cshift, so COEFF_TYPE has cshift more fraction bits there (fir_plan_i8)
+static FirParams fir_cshifted(FirParams k, int cshift) { k.cf.F += cshift; k.lossless_shift -= cshift; return k; }
+
+static inline bool fir_path_is_mfma(int p) { return p == ACDSP_PATH_MFMA_I8 || p == ACDSP_PATH_MFMA_LONG || p == ACDSP_PATH_MFMA_S8 || p == ACDSP_PATH_MFMA_GEN || p == ACDSP_PATH_MFMA_LOSSY; }
+// A/B knob: the exact-order kernel for every per-tap class (no fir_lossy_kernel / fir_satacc_kernel)
+static inline bool knob_no_lossy_fast() { static const bool v = getenv("ACDSP_NO_LOSSY_FAST") != nullptr; return v; }
 
 // ---------------------------------------------------------------------------------------------
 // FIR
@@ -82,23 +89,13 @@ bool fir_exact_shape(const acdsp_fir_desc_t &d) {
   return ok;
 }
 
-// Long filters (kFirLongMinTaps .. kFirLongMaxTaps, fir_long.hip): the condition a descriptor fails, or nullptr when it is long-eligible
+// The condition a descriptor fails for the long kernel (kFirLongMinTaps .. kFirLongMaxTaps of 16-bit samples, fir_long.hip) or, under
+// ACDSP_FLAG_IN_BYTES, for the byte-sample kernel (1 .. 16384 taps on ACDSP_PATH_MFMA_S8, fir_s8.hip: the same conditions with the sample width
+// taken out); nullptr when it is eligible
 const char *fir_long_refusal(const acdsp_fir_desc_t &d) {
   if (d.coeffs_per_channel) { return "one coefficient set per channel"; }
   if (d.flags & ACDSP_FLAG_FORCE_GENERIC) { return "ACDSP_FLAG_FORCE_GENERIC (the exact-order kernels end at 2048 taps)"; }
-  if (d.in.W > 16) { return "IN_TYPE wider than 16 bits"; }
-  if (d.coeff.S ? d.coeff.W > 16 : d.coeff.W > 15) { return "COEFF_TYPE wider than 16 bits signed / 15 bits unsigned"; }
-  if (d.acc.W > 64 || d.out.W > 64) { return "ACC_TYPE or OUT_TYPE wider than 64 bits"; }
-  if (d.ftype == ACDSP_TRANSPOSED && d.kind != ACDSP_FIR_CONST) { return "TRANSPOSED with loadable coefficients (carried reg_trans partial sums)"; }
-  if (!fir_exact_shape(d)) { return "ACC_TYPE is not an exact-sum accumulator (F_acc >= F_in + F_coeff, shift below 64; FOLD_ODD: the pre-add must fit too)"; }
-  return nullptr;
-}
-
-// Byte samples (ACDSP_FLAG_IN_BYTES, fir_s8.hip): the conditions of fir_long_refusal() with the sample width and the tap range taken out -- the
-// condition a flagged descriptor fails, or nullptr when it is byte-eligible (1 .. 16384 taps on ACDSP_PATH_MFMA_S8)
-const char *fir_bytes_refusal(const acdsp_fir_desc_t &d) {
-  if (d.coeffs_per_channel) { return "one coefficient set per channel"; }
-  if (d.flags & ACDSP_FLAG_FORCE_GENERIC) { return "ACDSP_FLAG_FORCE_GENERIC (the exact-order kernels end at 2048 taps)"; }
+  if (!(d.flags & ACDSP_FLAG_IN_BYTES) && d.in.W > 16) { return "IN_TYPE wider than 16 bits"; }
   if (d.coeff.S ? d.coeff.W > 16 : d.coeff.W > 15) { return "COEFF_TYPE wider than 16 bits signed / 15 bits unsigned"; }
   if (d.acc.W > 64 || d.out.W > 64) { return "ACC_TYPE or OUT_TYPE wider than 64 bits"; }
   if (d.ftype == ACDSP_TRANSPOSED && d.kind != ACDSP_FIR_CONST) { return "TRANSPOSED with loadable coefficients (carried reg_trans partial sums)"; }
@@ -144,18 +141,12 @@ int fir_validate(const acdsp_fir_desc_t &d, int *in_eb, int *out_eb) {
                       in_eb, out_eb))) {
     return rc;
   }
-  if (d.flags & ACDSP_FLAG_IN_BYTES) {
-    if (wide) { return fail(ACDSP_EUNSUPPORTED, "ACDSP_FLAG_IN_BYTES: ACC_TYPE or OUT_TYPE wider than 64 bits not supported"); }
-    // more than 2048 taps: the byte-sample matrix-core kernel or nothing
-    if (d.n_taps > 2048) {
-      if (const char *why = fir_bytes_refusal(d)) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: more than 2048 taps of byte samples run on the byte-sample matrix-core kernel only, which does not take %s", d.n_taps, why); }
-    }
-    return ACDSP_OK;
-  }
-  // more than 2048 taps: the long matrix-core kernel or nothing
-  if (d.n_taps > 2048) {
-    if (const char *why = fir_long_refusal(d)) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: more than 2048 taps run on the long matrix-core kernel only, which does not take %s", d.n_taps, why); }
-  }
+  const bool in_bytes = (d.flags & ACDSP_FLAG_IN_BYTES) != 0;
+  if (in_bytes && wide) { return fail(ACDSP_EUNSUPPORTED, "ACDSP_FLAG_IN_BYTES: ACC_TYPE or OUT_TYPE wider than 64 bits not supported"); }
+  // more than 2048 taps: the long (byte samples: the byte-sample) matrix-core kernel or nothing
+  const char *const why = d.n_taps > 2048 ? fir_long_refusal(d) : nullptr;
+  if (why && in_bytes) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: more than 2048 taps of byte samples run on the byte-sample matrix-core kernel only, which does not take %s", d.n_taps, why); }
+  if (why) { return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: more than 2048 taps run on the long matrix-core kernel only, which does not take %s", d.n_taps, why); }
   return ACDSP_OK;
 }
 
@@ -192,7 +183,7 @@ int32_t acdsp_fir_create(const acdsp_fir_desc_t *desc, acdsp_fir_t *out) {
   const bool lossless = fir_exact_shape(*desc) && (!h->use_rt || h->rt_hybrid) && !h->wide;   // (the overflow mode: below)
   h->lossless_shape = lossless;
   h->long_shape = !in_bytes && desc->n_taps >= kFirLongMinTaps && fir_long_refusal(*desc) == nullptr;
-  h->s8_shape = in_bytes && fir_bytes_refusal(*desc) == nullptr;
+  h->s8_shape = in_bytes && fir_long_refusal(*desc) == nullptr;
   if (h->s8_shape && h->hl < 32 * (long_blocks(desc->n_taps) - 1)) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the byte-sample kernel's reach", h->hl); }
   // the long kernel's first step reaches 32 (NB - 1) samples back
   if (h->long_shape && h->hl < 32 * (long_blocks(desc->n_taps) - 1)) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
@@ -234,15 +225,9 @@ int32_t acdsp_fir_destroy(acdsp_fir_t h) {
 namespace acdsp {
 namespace eng {
 int32_t fir_rt_from_hist(acdsp_fir *h) {
-  const acdsp_fir_desc_t &d = h->d;
-  FirParams k;
-  memset(&k, 0, sizeof k);
-  k.n_taps = d.n_taps; k.ftype = internal_ftype(d.kind, d.ftype); k.n_ch = d.n_channels; k.coeffs_per_channel = d.coeffs_per_channel;
-  k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff); k.acc = fir_acc_fmt(h); k.out = make_dfmt(d.out);
-  k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl; k.use_rt = 1;
-  k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
+  FirParams k = fir_params(h);   // (rt_hybrid: k.rt = d_rt[cur_rt], and never wide)
+  k.use_rt = 1;
   k.x = h->hist.cur(); k.in_stride = h->hl; k.n = h->hl;
-  k.coeffs = h->d_coeffs.get<int64_t>(); k.rt = h->d_rt[h->cur_rt].get<int64_t>();
   const hipError_t e = launch_fir_rt_update(k, h->d_rt[h->cur_rt ^ 1].get<int64_t>(), nullptr);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "reg_trans rebuild failed: %s", hipGetErrorString(e)); }
   HIP_TRY(hipDeviceSynchronize());
@@ -252,22 +237,232 @@ int32_t fir_rt_from_hist(acdsp_fir *h) {
 }
 }  // namespace eng
 }  // namespace acdsp
+
+// ---- acdsp_fir_set_coeffs: the saturation-free proof and one planner per kernel class (their answers: kTaken / kNotThisClass / an error) ----
+// The coefficient sets of one set_coeffs call as the planners see them
+struct FirSets {
+  const int64_t *raw;          // [n][n_taps] raw words as handed in
+  size_t n;                    // 1, or one set per channel
+  std::vector<int64_t> eff;    // [n][n_taps] effective direct-form taps (effective_coeffs)
+  std::vector<int64_t> sum;    // [n] their sums (32768 * sum rides in the correction constant of re-biased unsigned samples)
+};
+
+// Saturating accumulators: |every partial sum, in any order| <= sum|c| max|x| (the folds' pre-added pairs included: effective_coeffs lists
+// both taps of a pair), plus one LSB per tap where a tap's product is quantised.  Inside the type's SYMMETRIC range the three saturating
+// modes never act and equal AC_WRAP.  Signed accumulators, no carried partial sums (reg_trans), at most 64 bits.  ACDSP_NO_SAT_FREE: A/B knob.
+static bool fir_sat_free(const acdsp_fir *h, const FirSets &cs) {
+  const acdsp_fir_desc_t &d = h->d;
+  const int fi = d.in.W - d.in.I, fc = d.coeff.W - d.coeff.I, fa = d.acc.W - d.acc.I;
+  bool sf = !knob_no_sat_free() && d.acc.O != ACDSP_WRAP && d.acc.S && !h->wide && !h->use_rt && d.acc.W >= 2 && d.acc.W <= 64 &&
+            (fa >= fi + fc ? fa - fi - fc < 64 : ((d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && fi + fc - fa < 64));
+  if (sf && is_fold_odd(internal_ftype(d.kind, d.ftype))) {   // the `fold` pre-add variable is an ACC_TYPE too
+    const int need_i = d.in.I + 1 + (!d.in.S ? 1 : 0);
+    sf = fa >= fi && d.acc.I >= need_i;
+  }
+  for (size_t st = 0; st < cs.n && sf; st++) {
+    const unsigned __int128 sa = sum_abs(cs.eff.data() + st * d.n_taps, (size_t)d.n_taps);
+    sf = fa >= fi + fc ? sat_free_bound(sa, d.in, d.acc, fa - fi - fc, 0, 0) : sat_free_bound(sa, d.in, d.acc, 0, fi + fc - fa, (size_t)d.n_taps + 1);
+  }
+  return sf;
+}
+
+// unsigned 16-bit samples go through the int8 MFMA and long kernels as x - 32768 (acdsp_fir::in_flip)
+static bool fir_flip(const acdsp_fir *h) {
+  static const bool no_flip = getenv("ACDSP_NO_UNSIGNED16") != nullptr;   // A/B knob: unsigned 16-bit samples stay on the exact-sum VALU kernel
+  return !h->d.in.S && h->d.in.W == 16 && (!no_flip || h->long_shape) && !h->use_rt;   // (the long kernel has no other way to take them)
+}
+
+// The shapes the int8 MFMA, gen and lossy classes admit, whatever the taps' values (byte samples and long: s8_shape / long_shape of create)
+static bool fir_i8_shape(const acdsp_fir *h) {
+  const acdsp_fir_desc_t &d = h->d;
+  const bool i16_in = d.in.W <= 15 || (d.in.W == 16 && (d.in.S || fir_flip(h)));
+  const bool i16_cf = d.coeff.S ? d.coeff.W <= 16 : d.coeff.W <= 15;
+  return h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && i16_in && i16_cf && h->in_eb == 2 && fir_mfma_plan_blocks(d.n_taps) <= fir_mfma_max_blocks();
+}
+static bool fir_gen_shape(const acdsp_fir *h) {
+  const acdsp_fir_desc_t &d = h->d;
+  return h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel && !knob_no_gen() &&
+         (h->in_eb == 2 || h->in_eb == 4 || h->in_eb == 8) && fits_container(d.in, h->in_eb);
+}
+// (FOLD_ODD holds the pre-add in an ACC_TYPE variable (ac_fir_prog_coeffs.h:213-227): exact when ACC keeps the sample's fraction bits and
+// cannot wrap on the sum of two samples, and the product c * fold then drops the same s bits as an unfolded tap)
+static bool fir_lossy_shape(const acdsp_fir *h, const FirParams &kq) {
+  const acdsp_fir_desc_t &d = h->d;
+  static const bool no_lz = getenv("ACDSP_NO_MFMA_LOSSY") != nullptr;        // A/B knob: class B stays on the VALU kernels
+  // 16-bit types: fir_lossy_kernel (int32 VALU, 12 instructions per tap and four outputs) serves them too; the matrix-core kernel needs 6
+  // (measured 1.7 - 1.8 x faster at 63 / 127 taps, profiles/r5_shapes.txt) and goes first; ACDSP_LOSSY16_FIRST restores round 4's choice (A/B knob)
+  static const bool lz_first = getenv("ACDSP_LOSSY16_FIRST") == nullptr;
+  const int fi = kq.in.F, fa = kq.acc.F, sbits = fi + kq.cf.F - fa;
+  bool ok = !no_lz && !knob_no_gen() && !h->wide && !h->lossless && !h->use_rt && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel &&
+            (d.acc.O == ACDSP_WRAP || h->sat_free) && (d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && d.acc.S && d.acc.W <= 64 && sbits >= 1 && sbits <= 15 &&
+            (h->in_eb == 2 || h->in_eb == 4) && fits_container(d.in, h->in_eb) &&
+            (lz_first || !fir_lossy_fast_ok(kq));
+  if (ok && is_fold_odd(kq.ftype)) {
+    const int need_i = d.in.I + 1 + ((d.acc.S && !d.in.S) ? 1 : 0);
+    ok = fa >= fi && d.acc.I >= need_i;
+  }
+  return ok;
+}
+
+// Exclusivity (the comment at acdsp_fir's plan members): does a class BEHIND `path` in the planner order admit the handle's shape as well?  gen
+// is not asked against the int8 MFMA and long classes: it is their fall-back and admits their shapes by design.
+static bool fir_second_class_admits(const acdsp_fir *h, int path, const FirParams &kq) {
+  if (path == ACDSP_PATH_MFMA_LOSSY) { return false; }   // (nothing stands behind it)
+  if (path == ACDSP_PATH_MFMA_S8 && (h->long_shape || fir_i8_shape(h) || fir_gen_shape(h))) { return true; }
+  if (path == ACDSP_PATH_MFMA_LONG && fir_i8_shape(h)) { return true; }
+  return fir_lossy_shape(h, kq);
+}
+
+// byte samples (ACDSP_FLAG_IN_BYTES): one sample plane on fir_s8.hip for every tap count; above 2048 taps nothing else exists
+static int fir_plan_s8(acdsp_fir *h, const FirSets &cs) {
+  if (!h->s8_shape) { return kNotThisClass; }
+  const acdsp_fir_desc_t &d = h->d;
+  FirLongPlan lp;
+  int64_t sa = 0;
+  const int r = long_or_nothing("n_taps=", d.n_taps, h->lossless, h->d_frag, h->d_corr, [&](std::vector<uint32_t> *frag, int64_t *corr) {
+    if (!long_plan_blocks(cs.eff.data(), d.n_taps, &lp, frag, &sa)) { return false; }
+    if (d.in.S) { lp.corr = 0; }   // (128 * sum(c) undoes the x - 128 of UNSIGNED samples; signed ones are the B operand as they are)
+    *corr = lp.corr;
+    return true;
+  });
+  if (r == kTaken) { h->lplan = lp; h->s8_sum_abs = sa; }
+  return r;
+}
+
+// 1026 .. 16384 taps: the split of the int8 class on the long kernel (fir_long.hip), whatever the epilogue class.  Above 2048 taps nothing else
+// exists: a set that cannot go there is refused, and the handle stays without a set.
+static int fir_plan_long(acdsp_fir *h, const FirSets &cs) {
+  if (!h->long_shape) { return kNotThisClass; }
+  const acdsp_fir_desc_t &d = h->d;
+  const bool flip = fir_flip(h);
+  FirLongPlan lp;
+  const int r = long_or_nothing("n_taps=", d.n_taps, h->lossless, h->d_frag, h->d_corr, [&](std::vector<uint32_t> *frag, int64_t *corr) {
+    if (!fir_long_plan(cs.eff.data(), d.n_taps, &lp, frag)) { return false; }
+    if (flip) { lp.corr += 32768 * cs.sum[0]; }   // + 32768 * sum(c): the samples go through the kernel as x - 32768
+    *corr = lp.corr;
+    return true;
+  });
+  if (r == kTaken) { h->lplan = lp; h->in_flip = flip; }
+  return r;
+}
+
+// up to 1025 taps of 16-bit types: the int8 split on fir_mfma.hip, one plan per coefficient set
+static int fir_plan_i8(acdsp_fir *h, const FirSets &cs) {
+  if (!fir_i8_shape(h)) { return kNotThisClass; }
+  const acdsp_fir_desc_t &d = h->d;
+  const bool flip = fir_flip(h);
+  const size_t per_set = (size_t)2 * fir_mfma_plan_blocks(d.n_taps) * 64 * 4;
+  std::vector<uint32_t> frag(cs.n * per_set, 0u);
+  std::vector<int64_t> corr(cs.n, 0), sc((size_t)d.n_taps);
+  FirMfmaPlan worst;
+  bool ok = true;
+  // cshift: the sets go through the kernel scaled by 2^cshift (see below); one attempt with the shift the formats ask for, one without
+  auto build = [&](int cshift) {
+    std::fill(frag.begin(), frag.end(), 0u);
+    memset(&worst, 0, sizeof worst);
+    ok = true;
+    for (size_t st = 0; st < cs.n && ok; st++) {
+      for (int i = 0; i < d.n_taps; i++) { sc[i] = (int64_t)((uint64_t)cs.eff[st * d.n_taps + i] << cshift); }
+      FirMfmaPlan pl;
+      ok = fir_mfma_build_fragments(sc.data(), d.n_taps, &pl, frag.data() + st * per_set);
+      if (!ok) { break; }
+      if (flip) {   // + 32768 * sum(c): the samples go through the kernel as x - 32768
+        pl.corr += 32768 * (int64_t)((uint64_t)cs.sum[st] << cshift);
+        // the kernel sees signed 16-bit samples (|x| <= 2^15) but the recombined sum is the UNSIGNED dot product, |y| <= 65535 * sum|c|:
+        // the no-wrap proof of the fast epilogues (fir_mfma_epilogue_class: sum_abs * x_max against ACC's range) must use that bound
+        pl.sum_abs *= 2;
+      }
+      corr[st] = pl.corr;
+      worst.nb = pl.nb;
+      worst.hi_mask |= pl.hi_mask; worst.lo_mask |= pl.lo_mask;
+      if (pl.sum_abs > worst.sum_abs) { worst.sum_abs = pl.sum_abs; }
+      if (pl.sum_abs_hi > worst.sum_abs_hi) { worst.sum_abs_hi = pl.sum_abs_hi; }
+      if (pl.sum_abs_lo > worst.sum_abs_lo) { worst.sum_abs_lo = pl.sum_abs_lo; }
+      const int64_t ca = pl.corr < 0 ? -pl.corr : pl.corr, wa = worst.corr < 0 ? -worst.corr : worst.corr;
+      if (st == 0 || ca > wa) { worst.corr = pl.corr; }
+    }
+  };
+  // Narrow types (<8,1> samples and coefficients into an <8,1> output: 7 dropped bits) leave the 32-bit epilogue classes less than one bit
+  // to shift by once the 16 - W_out bits of the packed finish are taken off (fir_mfma_epilogue_class: rse >= 1), and ran the generic
+  // epilogue with element-wise stores (0.18 of the roofline).  The sum is linear in the set: the fragments are built from c << cshift and the
+  // kernel is told F_coeff + cshift -- every bound scales with it, and the classes are asked again with the scaled plan.
+  h->mfma_cshift = 0;
+  const int nar_d = (h->out_eb == 2 && d.out.W >= 2 && d.out.W < 16) ? 16 - d.out.W : 0;
+  const int rse = (d.in.W - d.in.I) + (d.coeff.W - d.coeff.I) - (d.out.W - d.out.I) - nar_d;
+  static const bool no_cshift = getenv("ACDSP_NO_CSHIFT") != nullptr;   // A/B knob
+  const int want = (h->out_eb == 2 && rse < 1 && rse > -14 && !no_cshift) ? 1 - rse : 0;
+  if (want > 0) {
+    build(want);
+    const int epi = ok ? fir_mfma_epilogue_class(fir_cshifted(fir_params(h), want), worst) : 0;
+    if (epi == 1 || epi == 2) { h->mfma_cshift = want; }
+  }
+  if (!h->mfma_cshift) { build(0); }
+  if (ok && d.coeffs_per_channel && worst.nb > fir_mfma_max_reg_blocks()) {
+    // a set per channel needs the register-resident kernels: beyond 9 K-blocks only band-limited sets with the fast int16 epilogue
+    ok = fir_mfma_register_resident(fir_cshifted(fir_params(h), h->mfma_cshift), worst);
+  }
+  if (!ok) { return kNotThisClass; }
+  int rc;
+  if ((rc = h->d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = h->d_corr.upload(corr.data(), corr.size() * sizeof(int64_t)))) { return rc; }
+  h->plan = worst;
+  h->in_flip = flip;
+  return kTaken;
+}
+
+// wide inputs (more than 16 bits) / other misses of the int8 and long classes: generalised multi-plane MFMA kernel
+static int fir_plan_gen(acdsp_fir *h, const FirSets &cs) {
+  if (!fir_gen_shape(h)) { return kNotThisClass; }
+  std::vector<uint32_t> gfrag;
+  if (!fir_gen_plan(cs.eff.data(), h->d.n_taps, 1, 0, &h->gplan, &gfrag)) { return kNotThisClass; }
+  const int rc = h->d_gfrag.upload(gfrag.data(), gfrag.size() * sizeof(uint32_t));
+  return rc ? rc : kTaken;
+}
+
+// Class B (lossy accumulator, AC_TRN / AC_RND into AC_WRAP) on the matrix cores: sum_k Q(p_k) = (sum_k p_k + N h - sum_k ((p_k + h) mod 2^s)) >> s.
+// The exact sum is class A on the effective taps; the residues need the low s bits of every (folded) sample and coefficient (fir_gen_kernels.hpp: fir_gen_ring_kernel, LZ).
+static int fir_plan_lossy(acdsp_fir *h, const FirSets &cs, const FirParams &kq) {
+  if (!fir_lossy_shape(h, kq)) { return kNotThisClass; }
+  const acdsp_fir_desc_t &d = h->d;
+  const int ift = kq.ftype, sbits = kq.in.F + kq.cf.F - kq.acc.F;
+  const bool fold_odd = is_fold_odd(ift), fold_even = ift == ACDSP_FOLD_EVEN || ift == kRsFoldEven || ift == kRsFoldEvenAnti;
+  const bool anti = ift == kRsFoldEvenAnti || ift == kRsFoldOddAnti;
+  const int n_pair = fold_odd ? (d.n_taps - 1) / 2 : (fold_even ? d.n_taps / 2 : 0);
+  const int n_single = fold_odd ? 1 : (fold_even ? 0 : d.n_taps);
+  std::vector<uint32_t> gfrag, tab;
+  if (n_pair + n_single < 1 || !fir_gen_plan(cs.eff.data(), d.n_taps, 1, 0, &h->gplan, &gfrag)) { return kNotThisClass; }
+  // the exact sum must not leave int64 (the shift by s follows it), unless ACC_TYPE only keeps bits that survive a wrap of 2^64
+  const int xb = d.in.W - (d.in.S ? 1 : 0);
+  const bool bounded = h->gplan.sum_abs_h < (int64_t(1) << 61) && xb <= 61 && h->gplan.sum_abs_h <= ((int64_t(1) << 61) >> xb);
+  int acc_bits = d.acc.W;       // |acc| <= sum|c| 2^xb / 2^s + 1 when the sum is bounded: lets a 64-bit ACC_TYPE round into OUT_TYPE in int64
+  if (bounded) {
+    int sb = 0;
+    while (sb < 62 && (int64_t(1) << sb) <= h->gplan.sum_abs_h) { sb++; }
+    const int vb = sb + xb - sbits + 2;
+    if (vb < acc_bits) { acc_bits = vb < 2 ? 2 : vb; }
+  }
+  const int single0 = fold_odd ? (d.n_taps - 1) / 2 : 0;
+  if (!(d.acc.W + sbits <= 64 || bounded) || !fir_gen_lossy_shape_ok(kq, h->gplan, acc_bits) ||
+      !fir_gen_lossy_table(h->gplan, cs.raw, d.n_taps, n_pair, n_single, single0, anti ? 1 : 0, sbits, d.acc.Q == ACDSP_RND, &h->lzp, &tab)) {
+    return kNotThisClass;
+  }
+  h->lzp.d_tab = h->d_lzcl.get<uint32_t>(); h->lzp.acc_bits = acc_bits;
+  int rc;
+  if ((rc = h->d_gfrag.upload(gfrag.data(), gfrag.size() * sizeof(uint32_t))) || (rc = h->d_lzcl.upload(tab.data(), tab.size() * sizeof(uint32_t)))) { return rc; }
+  return kTaken;
+}
+
 extern "C" {
 
 int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
   if (!h || !coeffs) { return fail(ACDSP_EINVAL, "null argument"); }
   const acdsp_fir_desc_t &d = h->d;
-  if (d.kind == ACDSP_FIR_CONST && h->coeffs_set && d.ftype == ACDSP_TRANSPOSED) {
-    return fail(ACDSP_ESTATE, "const-coefficient TRANSPOSED filter: coefficients are bound once");
-  }
+  if (d.kind == ACDSP_FIR_CONST && h->coeffs_set && d.ftype == ACDSP_TRANSPOSED) { return fail(ACDSP_ESTATE, "const-coefficient TRANSPOSED filter: coefficients are bound once"); }
   int rc = check_device(d.device);
   if (rc) { return rc; }
   const size_t n_sets = d.coeffs_per_channel ? (size_t)d.n_channels : 1;
   const acdsp::DFmt cf = make_dfmt(d.coeff);
   for (size_t i = 0; i < n_sets * d.n_taps; i++) {
-    if (coeffs[i] < cf.lo || coeffs[i] > cf.hi) {
-      return fail(ACDSP_EINVAL, "coefficient %zu = %lld is not a COEFF_TYPE raw word", i, (long long)coeffs[i]);
-    }
+    if (coeffs[i] < cf.lo || coeffs[i] > cf.hi) { return fail(ACDSP_EINVAL, "coefficient %zu = %lld is not a COEFF_TYPE raw word", i, (long long)coeffs[i]); }
   }
   // the same set again (ac_fir_prog_coeffs hands its coefficients to every one-sample call): nothing changes, no state event
   if (h->coeffs_set && h->h_coeffs.size() == n_sets * d.n_taps && memcmp(h->h_coeffs.data(), coeffs, n_sets * d.n_taps * sizeof(int64_t)) == 0) { return ACDSP_OK; }
@@ -283,230 +478,31 @@ int32_t acdsp_fir_set_coeffs(acdsp_fir_t h, const int64_t *coeffs) {
   h->coeffs_set = false;
   h->h_coeffs.clear();
   if ((rc = h->d_coeffs.upload(coeffs, n_sets * d.n_taps * sizeof(int64_t)))) { return rc; }
-  h->mfma_ok = false;
   h->in_flip = false;
-  {
-    // Saturating accumulators: |every partial sum, in any order| <= sum|c| max|x| (the folds' pre-added pairs included: effective_coeffs lists
-    // both taps of a pair), plus one LSB per tap where a tap's product is quantised.  Inside the type's SYMMETRIC range the three saturating
-    // modes never act and equal AC_WRAP.  Signed accumulators, no carried partial sums (reg_trans), at most 64 bits.  ACDSP_NO_SAT_FREE: A/B knob.
-    static const bool no_sat_free = getenv("ACDSP_NO_SAT_FREE") != nullptr;
-    const int fi_ = d.in.W - d.in.I, fc_ = d.coeff.W - d.coeff.I, fa_ = d.acc.W - d.acc.I;
-    bool sf = !no_sat_free && d.acc.O != ACDSP_WRAP && d.acc.S && !h->wide && !h->use_rt && d.acc.W >= 2 && d.acc.W <= 64 &&
-              (fa_ >= fi_ + fc_ ? fa_ - fi_ - fc_ < 64 : ((d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && fi_ + fc_ - fa_ < 64));
-    const int ift_ = internal_ftype(d.kind, d.ftype);
-    if (sf && is_fold_odd(ift_)) {   // the `fold` pre-add variable is an ACC_TYPE too
-      const int need_i = d.in.I + 1 + (!d.in.S ? 1 : 0);
-      sf = fa_ >= fi_ && d.acc.I >= need_i;
-    }
-    for (size_t st = 0; st < n_sets && sf; st++) {
-      const std::vector<int64_t> eff = effective_coeffs(coeffs + st * d.n_taps, d.n_taps, ift_);
-      const unsigned __int128 sa = sum_abs(eff.data(), eff.size());
-      sf = fa_ >= fi_ + fc_ ? sat_free_bound(sa, d.in, d.acc, fa_ - fi_ - fc_, 0, 0) : sat_free_bound(sa, d.in, d.acc, 0, fi_ + fc_ - fa_, eff.size() + 1);
-    }
-    h->sat_free = sf;
-    h->lossless = h->lossless_shape && (d.acc.O == ACDSP_WRAP || sf);
+  FirSets cs = {coeffs, n_sets, {}, {}};
+  for (size_t st = 0; st < n_sets; st++) {
+    const std::vector<int64_t> e = effective_coeffs(coeffs + st * d.n_taps, d.n_taps, internal_ftype(d.kind, d.ftype));
+    cs.eff.insert(cs.eff.end(), e.begin(), e.end());
+    cs.sum.push_back(0);
+    for (int64_t v : e) { cs.sum[st] += v; }
   }
-  static const bool no_flip = getenv("ACDSP_NO_UNSIGNED16") != nullptr;   // A/B knob: unsigned 16-bit samples stay on the exact-sum VALU kernel
-  const bool flip = !d.in.S && d.in.W == 16 && (!no_flip || h->long_shape) && !h->use_rt;   // (the long kernel has no other way to take them)
-  const bool i16_in = d.in.W <= 15 || (d.in.W == 16 && (d.in.S || flip));
-  const bool i16_cf = d.coeff.S ? d.coeff.W <= 16 : d.coeff.W <= 15;
-  if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && i16_in && i16_cf && h->in_eb == 2 &&
-      fir_mfma_plan_blocks(d.n_taps) <= fir_mfma_max_blocks()) {
-    const int nb = fir_mfma_plan_blocks(d.n_taps);
-    const size_t per_set = (size_t)2 * nb * 64 * 4;
-    std::vector<uint32_t> frag(n_sets * per_set, 0u);
-    std::vector<int64_t> corr(n_sets, 0);
-    FirMfmaPlan worst;
-    bool ok = true;
-    // cshift: the sets go through the kernel scaled by 2^cshift (see below); one attempt with the shift the formats ask for, one without
-    auto build = [&](int cshift) {
-      std::fill(frag.begin(), frag.end(), 0u);
-      memset(&worst, 0, sizeof worst);
-      ok = true;
-      for (size_t st = 0; st < n_sets && ok; st++) {
-        std::vector<int64_t> eff = effective_coeffs(coeffs + st * d.n_taps, d.n_taps, internal_ftype(d.kind, d.ftype));
-        for (int64_t &v : eff) { v = (int64_t)((uint64_t)v << cshift); }
-        FirMfmaPlan pl;
-        ok = fir_mfma_build_fragments(eff.data(), d.n_taps, &pl, frag.data() + st * per_set);
-        if (!ok) { break; }
-        if (flip) {   // + 32768 * sum(c): the samples go through the kernel as x - 32768
-          int64_t sc = 0;
-          for (int64_t v : eff) { sc += v; }
-          pl.corr += 32768 * sc;
-          // the kernel sees signed 16-bit samples (|x| <= 2^15) but the recombined sum is the UNSIGNED dot product, |y| <= 65535 * sum|c|:
-          // the no-wrap proof of the fast epilogues (fir_mfma_epilogue_class: sum_abs * x_max against ACC's range) must use that bound
-          pl.sum_abs *= 2;
-        }
-        corr[st] = pl.corr;
-        worst.nb = pl.nb;
-        worst.hi_mask |= pl.hi_mask; worst.lo_mask |= pl.lo_mask;
-        if (pl.sum_abs > worst.sum_abs) { worst.sum_abs = pl.sum_abs; }
-        if (pl.sum_abs_hi > worst.sum_abs_hi) { worst.sum_abs_hi = pl.sum_abs_hi; }
-        if (pl.sum_abs_lo > worst.sum_abs_lo) { worst.sum_abs_lo = pl.sum_abs_lo; }
-        const int64_t ca = pl.corr < 0 ? -pl.corr : pl.corr, wa = worst.corr < 0 ? -worst.corr : worst.corr;
-        if (st == 0 || ca > wa) { worst.corr = pl.corr; }
-      }
-    };
-    // Narrow types (<8,1> samples and coefficients into an <8,1> output: 7 dropped bits) leave the 32-bit epilogue classes less than one bit
-    // to shift by once the 16 - W_out bits of the packed finish are taken off (fir_mfma_epilogue_class: rse >= 1), and ran the generic
-    // epilogue with element-wise stores (0.18 of the roofline).  The sum is linear in the set: the fragments are built from c << cshift and the
-    // kernel is told F_coeff + cshift -- every bound scales with it, and the classes are asked again with the scaled plan.
-    h->mfma_cshift = 0;
-    {
-      const int fi_ = d.in.W - d.in.I, fc_ = d.coeff.W - d.coeff.I, fo_ = d.out.W - d.out.I;
-      const int nar_d = (h->out_eb == 2 && d.out.W >= 2 && d.out.W < 16) ? 16 - d.out.W : 0, rse = fi_ + fc_ - fo_ - nar_d;
-      static const bool no_cshift = getenv("ACDSP_NO_CSHIFT") != nullptr;   // A/B knob
-      const int want = (h->out_eb == 2 && rse < 1 && rse > -14 && !no_cshift) ? 1 - rse : 0;
-      if (want > 0) {
-        build(want);
-        const int epi = ok ? fir_mfma_epilogue_class(fir_class_params(h, want), worst) : 0;
-        if (epi == 1 || epi == 2) { h->mfma_cshift = want; }
-      }
-      if (!h->mfma_cshift) { build(0); }
-    }
-    if (ok && d.coeffs_per_channel && worst.nb > fir_mfma_max_reg_blocks()) {
-      // a set per channel needs the register-resident kernels: beyond 9 K-blocks only band-limited sets with the fast int16 epilogue
-      ok = fir_mfma_register_resident(fir_class_params(h, h->mfma_cshift), worst);
-    }
-    if (ok) {
-      if ((rc = h->d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = h->d_corr.upload(corr.data(), corr.size() * sizeof(int64_t)))) { return rc; }
-      h->plan = worst;
-      h->mfma_ok = true;
-      h->in_flip = flip;
-    }
-  }
-  // 1026 .. 16384 taps: the same split on the long kernel (fir_long.hip), whatever the epilogue class.  Above 2048 taps nothing else exists:
-  // a set that cannot go there is refused, and the handle stays without a set.
-  h->long_ok = false;
-  if (h->long_shape) {
-    if (!h->lossless) {
-      if (d.n_taps > 2048) {
-        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", d.n_taps);
-      }
-    } else {
-      const std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
-      std::vector<uint32_t> frag;
-      FirLongPlan lp;
-      if (fir_long_plan(eff.data(), d.n_taps, &lp, &frag)) {
-        if (flip) {   // + 32768 * sum(c): the samples go through the kernel as x - 32768
-          int64_t sc = 0;
-          for (int64_t v : eff) { sc += v; }
-          lp.corr += 32768 * sc;
-        }
-        if ((rc = h->d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = h->d_corr.upload(&lp.corr, sizeof(int64_t)))) { return rc; }
-        h->lplan = lp;
-        h->long_ok = true;
-        h->in_flip = flip;
-      } else if (d.n_taps > 2048) {
-        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: a coefficient of 32640 or more cannot be split into two signed bytes, and more than 2048 taps run on the matrix cores only", d.n_taps);
-      }
-    }
-  }
-  // byte samples (ACDSP_FLAG_IN_BYTES): one sample plane on fir_s8.hip for every tap count; above 2048 taps nothing else exists
-  h->s8_ok = false;
-  if (h->s8_shape) {
-    if (!h->lossless) {
-      if (d.n_taps > 2048) {
-        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", d.n_taps);
-      }
-    } else {
-      const std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
-      std::vector<uint32_t> frag;
-      FirLongPlan lp;
-      int64_t sa = 0;
-      if (long_plan_blocks(eff.data(), d.n_taps, &lp, &frag, &sa)) {
-        if (d.in.S) { lp.corr = 0; }   // (128 * sum(c) undoes the x - 128 of UNSIGNED samples; signed ones are the B operand as they are)
-        if ((rc = h->d_frag.upload(frag.data(), frag.size() * sizeof(uint32_t))) || (rc = h->d_corr.upload(&lp.corr, sizeof(int64_t)))) { return rc; }
-        h->lplan = lp;
-        h->s8_sum_abs = sa;
-        h->s8_ok = true;
-      } else if (d.n_taps > 2048) {
-        return fail(ACDSP_EUNSUPPORTED, "n_taps=%d: a coefficient of 32640 or more cannot be split into two signed bytes, and more than 2048 taps run on the matrix cores only", d.n_taps);
-      }
-    }
-  }
-  // wide inputs (more than 16 bits) / other misses of the int16 kernel: generalised multi-plane MFMA kernel
-  h->gen_ok = false;
-  static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
-  if (!h->mfma_ok && !h->long_ok && h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel && !no_gen &&
-      (h->in_eb == 2 || h->in_eb == 4 || h->in_eb == 8) && fits_container(d.in, h->in_eb)) {
-    std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, internal_ftype(d.kind, d.ftype));
-    std::vector<uint32_t> gfrag;
-    if (fir_gen_plan(eff.data(), d.n_taps, 1, 0, &h->gplan, &gfrag)) {
-      if ((rc = h->d_gfrag.upload(gfrag.data(), gfrag.size() * sizeof(uint32_t)))) { return rc; }
-      h->gen_ok = true;
-    }
-  }
-  // Class B (lossy accumulator, AC_TRN / AC_RND into AC_WRAP) on the matrix cores: sum_k Q(p_k) = (sum_k p_k + N h - sum_k ((p_k + h) mod 2^s)) >> s.
-  // The exact sum is class A on the effective taps; the residues need the low s bits of every (folded) sample and coefficient (fir_gen_kernels.hpp: fir_gen_ring_kernel, LZ).
-  // FOLD_ODD holds the pre-add in an ACC_TYPE variable (ac_fir_prog_coeffs.h:213-227): exact when ACC keeps the sample's fraction bits and
-  // cannot wrap on the sum of two samples, and the product c * fold then drops the same s bits as an unfolded tap.
-  h->lz_ok = false;
-  FirParams kq;
-  memset(&kq, 0, sizeof kq);
-  kq.n_taps = d.n_taps; kq.ftype = internal_ftype(d.kind, d.ftype); kq.n_ch = d.n_channels; kq.coeffs_per_channel = d.coeffs_per_channel;
-  kq.in = make_dfmt(d.in); kq.cf = make_dfmt(d.coeff);
-  if (!h->wide) { kq.acc = fir_acc_fmt(h); kq.out = make_dfmt(d.out); }
-  kq.in_eb = h->in_eb; kq.out_eb = h->out_eb; kq.hl = h->hl; kq.use_rt = (h->use_rt && !h->rt_hybrid) ? 1 : 0;
-  kq.lossless_shift = kq.acc.F - kq.in.F - kq.cf.F;
-  static const bool no_lz = getenv("ACDSP_NO_MFMA_LOSSY") != nullptr;        // A/B knob: class B stays on the VALU kernels
-  // 16-bit types: fir_lossy_kernel (int32 VALU, 12 instructions per tap and four outputs) serves them too; the matrix-core kernel needs 6
-  // (measured 1.7 - 1.8 x faster at 63 / 127 taps, profiles/r5_shapes.txt) and goes first; ACDSP_LOSSY16_FIRST restores round 4's choice (A/B knob)
-  static const bool lz_first = getenv("ACDSP_LOSSY16_FIRST") == nullptr;
-  {
-    const int ift = internal_ftype(d.kind, d.ftype);
-    const int fi = kq.in.F, fc = kq.cf.F, fa = kq.acc.F, sbits = fi + fc - fa;
-    const bool fold_odd = is_fold_odd(ift), fold_even = ift == ACDSP_FOLD_EVEN || ift == kRsFoldEven || ift == kRsFoldEvenAnti;
-    const bool anti = ift == kRsFoldEvenAnti || ift == kRsFoldOddAnti;
-    bool ok = !no_lz && !no_gen && !h->wide && !h->lossless && !h->use_rt && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !d.coeffs_per_channel &&
-              (d.acc.O == ACDSP_WRAP || h->sat_free) && (d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && d.acc.S && d.acc.W <= 64 && sbits >= 1 && sbits <= 15 &&
-              (h->in_eb == 2 || h->in_eb == 4) && fits_container(d.in, h->in_eb) &&
-              (lz_first || !fir_lossy_fast_ok(kq));
-    if (ok && fold_odd) {
-      const int need_i = d.in.I + 1 + ((d.acc.S && !d.in.S) ? 1 : 0);
-      ok = fa >= fi && d.acc.I >= need_i;
-    }
-    const int n_pair = fold_odd ? (d.n_taps - 1) / 2 : (fold_even ? d.n_taps / 2 : 0);
-    const int n_single = fold_odd ? 1 : (fold_even ? 0 : d.n_taps);
-    ok = ok && n_pair + n_single >= 1;
-    if (ok) {
-      std::vector<int64_t> eff = effective_coeffs(coeffs, d.n_taps, ift);
-      std::vector<uint32_t> gfrag, tab;
-      ok = fir_gen_plan(eff.data(), d.n_taps, 1, 0, &h->gplan, &gfrag);
-      // the exact sum must not leave int64 (the shift by s follows it), unless ACC_TYPE only keeps bits that survive a wrap of 2^64
-      const int xb = d.in.W - (d.in.S ? 1 : 0);
-      const bool bounded = ok && h->gplan.sum_abs_h < (int64_t(1) << 61) && xb <= 61 && h->gplan.sum_abs_h <= ((int64_t(1) << 61) >> xb);
-      ok = ok && (d.acc.W + sbits <= 64 || bounded);
-      int acc_bits = d.acc.W;       // |acc| <= sum|c| 2^xb / 2^s + 1 when the sum is bounded: lets a 64-bit ACC_TYPE round into OUT_TYPE in int64
-      if (bounded) {
-        int sb = 0;
-        while (sb < 62 && (int64_t(1) << sb) <= h->gplan.sum_abs_h) { sb++; }
-        const int vb = sb + xb - sbits + 2;
-        if (vb < acc_bits) { acc_bits = vb < 2 ? 2 : vb; }
-      }
-      ok = ok && fir_gen_lossy_shape_ok(kq, h->gplan, acc_bits);
-      const int single0 = fold_odd ? (d.n_taps - 1) / 2 : 0;
-      ok = ok && fir_gen_lossy_table(h->gplan, coeffs, d.n_taps, n_pair, n_single, single0, anti ? 1 : 0, sbits, d.acc.Q == ACDSP_RND, &h->lzp, &tab);
-      if (ok) {
-        h->lzp.d_tab = h->d_lzcl.get<uint32_t>(); h->lzp.acc_bits = acc_bits;
-        if ((rc = h->d_gfrag.upload(gfrag.data(), gfrag.size() * sizeof(uint32_t))) || (rc = h->d_lzcl.upload(tab.data(), tab.size() * sizeof(uint32_t)))) { return rc; }
-        h->lz_ok = true;
-      }
-    }
-  }
+  h->sat_free = fir_sat_free(h, cs);
+  h->lossless = h->lossless_shape && (d.acc.O == ACDSP_WRAP || h->sat_free);
+  const FirParams kq = fir_params(h);   // (behind sat_free: ACC_TYPE as the kernels see it)
+  // the planners in priority order; the first that takes the set names the path
+  int path = ACDSP_PATH_MFMA_S8, r = fir_plan_s8(h, cs);
+  if (r == kNotThisClass) { path = ACDSP_PATH_MFMA_LONG; r = fir_plan_long(h, cs); }
+  if (r == kNotThisClass) { path = ACDSP_PATH_MFMA_I8; r = fir_plan_i8(h, cs); }
+  if (r == kNotThisClass) { path = ACDSP_PATH_MFMA_GEN; r = fir_plan_gen(h, cs); }
+  if (r == kNotThisClass) { path = ACDSP_PATH_MFMA_LOSSY; r = fir_plan_lossy(h, cs, kq); }
+  if (r > 0) { return r; }
+  if (r == kTaken && fir_second_class_admits(h, path, kq)) { return fail(ACDSP_EHIP, "internal: a second kernel class admits the coefficient set that path %d took", path); }
   h->path = h->wide ? ACDSP_PATH_WIDE
-            : h->s8_ok ? ACDSP_PATH_MFMA_S8
-            : h->long_ok ? ACDSP_PATH_MFMA_LONG
-            : h->mfma_ok ? ACDSP_PATH_MFMA_I8
-            : h->gen_ok ? ACDSP_PATH_MFMA_GEN
-            : h->lz_ok ? ACDSP_PATH_MFMA_LOSSY
-                        : ((h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC)) ? ACDSP_PATH_LOSSLESS64 : ACDSP_PATH_GENERIC);
-  {
-    static const bool no_lossy = getenv("ACDSP_NO_LOSSY_FAST") != nullptr;
-    h->kclass = h->path;
-    if (h->path == ACDSP_PATH_GENERIC && !no_lossy && !(d.flags & ACDSP_FLAG_FORCE_GENERIC)) {
-      h->kclass = fir_lossy_fast_ok(kq) ? ACDSP_KCLASS_LOSSY16 : (fir_satacc_fast_ok(kq) ? ACDSP_KCLASS_SATACC16 : ACDSP_PATH_GENERIC);
-    }
+            : r == kTaken ? path
+                          : ((h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC)) ? ACDSP_PATH_LOSSLESS64 : ACDSP_PATH_GENERIC);
+  h->kclass = h->path;
+  if (h->path == ACDSP_PATH_GENERIC && !knob_no_lossy_fast() && !(d.flags & ACDSP_FLAG_FORCE_GENERIC)) {
+    h->kclass = fir_lossy_fast_ok(kq) ? ACDSP_KCLASS_LOSSY16 : (fir_satacc_fast_ok(kq) ? ACDSP_KCLASS_SATACC16 : ACDSP_PATH_GENERIC);
   }
   h->coeffs_set = true;
   h->h_coeffs.assign(coeffs, coeffs + n_sets * d.n_taps);
@@ -540,10 +536,9 @@ static bool fir_rows_aligned(const acdsp_fir *h, const void *d_in, int64_t in_st
   const int path = h->path;
   // byte rows (fir_s8.hip) may start anywhere: a row must be readable up to the next multiple of 16 samples = 16 bytes
   if (path == ACDSP_PATH_MFMA_S8) { return in_stride >= (n + 15) / 16 * 16; }
-  bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) &&
-                 (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || in_stride >= (n + 15) / 16 * 16);
-  if (!aligned && !aligned_only && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG) && in_stride >= (n + 7) / 8 * 8) { aligned = true; }
-  return aligned;
+  // the int8 and long kernels take any element-aligned row that is readable up to the next multiple of 8 samples; fir_gen wants whole slots
+  if (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG) { return rows_vec_aligned(d_in, in_stride, h->in_eb) || (!aligned_only && in_stride >= (n + 7) / 8 * 8); }
+  return rows_in_slots(d_in, in_stride, h->in_eb, n);
 }
 
 // What acdsp_fir_run refuses while its stream is capturing, decided before the call touches the stream or the handle
@@ -554,8 +549,7 @@ int acdsp::eng::fir_capture_check(const acdsp_fir *h, const void *d_in, int64_t 
       return fail(ACDSP_ESTATE, "fir_run under graph capture: a TRANSPOSED filter within n_taps - 1 samples of a coefficient change keeps host-side state; run %lld more samples before capturing", (long long)m_rt);
     }
   }
-  const int path = h->path;
-  if (!h->wide && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_S8 || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) && !fir_rows_aligned(h, d_in, in_stride, n)) {
+  if (fir_path_is_mfma(h->path) && !fir_rows_aligned(h, d_in, in_stride, n)) {
     // rows the matrix-core kernels do not take as they are go through the aligned staging image, which is allocated on growth
     const size_t need = (size_t)h->d.n_channels * ((n + 15) / 16 * 16) * h->in_eb;
     if (need > h->st.cap_in) {
@@ -582,18 +576,9 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   hipStream_t s = (hipStream_t)stream;
   const bool capturing = stream_is_capturing(s);
   if (capturing && (rc = fir_capture_check(h, d_in, in_stride, n))) { return rc; }
-  FirParams k;
-  k.hist_next = nullptr; k.t_begin = 0; k.in_flip = 0;
-  k.n_taps = d.n_taps; k.ftype = internal_ftype(d.kind, d.ftype); k.n_ch = d.n_channels; k.coeffs_per_channel = d.coeffs_per_channel;
-  k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff);
-  if (h->wide) { memset(&k.acc, 0, sizeof k.acc); memset(&k.out, 0, sizeof k.out); k.acc.F = d.acc.W - d.acc.I; }
-  else { k.acc = fir_acc_fmt(h); k.out = make_dfmt(d.out); }
+  FirParams k = fir_params(h);
   const bool hyb = h->rt_hybrid;
-  k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl; k.use_rt = (h->use_rt && !hyb) ? 1 : 0;
-  k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
-  k.in_stride = in_stride; k.out_stride = out_stride; k.n = n;
-  k.x = d_in; k.y = d_out;
-  k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>(); k.rt = fir_rt_cur(h);
+  k.in_stride = in_stride; k.out_stride = out_stride; k.n = n; k.x = d_in; k.y = d_out;
   // rt_hybrid: the first m outputs still carry partial sums of the previous coefficient set
   int64_t m_rt = 0;
   if (hyb) {
@@ -617,7 +602,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     return ACDSP_OK;
   }
   FirParams kraw = k;   // the state kernels always see the caller's samples
-  const bool flipped = h->in_flip && (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG);
+  const bool flipped = h->in_flip;   // (set by the planners of ACDSP_PATH_MFMA_I8 and ACDSP_PATH_MFMA_LONG alone)
   if (flipped) {
     // unsigned 16-bit samples: the kernel flips the top bit of every sample as it splits the rows and the history into byte planes
     // (FirParams::in_flip; round 4 and the first half of round 5 wrote a flipped image of both first: a second pass over the call's input,
@@ -625,7 +610,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
     k.in_flip = 1;
     k.in.S = 1; k.in.lo = -32768; k.in.hi = 32767;
   }
-  if (path == ACDSP_PATH_MFMA_I8 || path == ACDSP_PATH_MFMA_LONG || path == ACDSP_PATH_MFMA_S8 || path == ACDSP_PATH_MFMA_GEN || path == ACDSP_PATH_MFMA_LOSSY) {
+  if (fir_path_is_mfma(path)) {
     // The matrix-core kernels read rows with 16-byte vector loads (fir_gen: in whole 16-sample slots).  gfx950 serves a vector
     // access at any ELEMENT-aligned address, so the int8 kernel takes unaligned rows as they are (round 3: a row stride of 2^20 + 3
     // samples costs +12 %, profiles/r3_unaligned.txt; the staging copy below -- hipMemcpy2DAsync of misaligned rows -- cost 6.4 ms
@@ -651,9 +636,8 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   if (!small) { HIP_TRY(hipEventRecord(h->tm.start(), s)); }
   hipError_t e;
   if (path == ACDSP_PATH_MFMA_I8) {
-    FirParams km = k;    // (the fragments hold c << mfma_cshift: the kernel's shifts follow; the state kernels below keep the handle's formats)
-    km.cf.F += h->mfma_cshift; km.lossless_shift -= h->mfma_cshift;
-    e = launch_fir_mfma(km, h->plan, d.coeffs_per_channel, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s);
+    // (the fragments hold c << mfma_cshift: the kernel's shifts follow; the state kernels below keep the handle's formats)
+    e = launch_fir_mfma(fir_cshifted(k, h->mfma_cshift), h->plan, d.coeffs_per_channel, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s);
   }
   else if (path == ACDSP_PATH_MFMA_LONG) { e = launch_fir_long(k, h->lplan, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s); }
   else if (path == ACDSP_PATH_MFMA_S8) { e = launch_fir_s8(k, h->lplan, h->s8_sum_abs, h->d_frag.get<uint32_t>(), h->d_corr.get<int64_t>(), s); }
@@ -666,7 +650,7 @@ int32_t acdsp_fir_run(acdsp_fir_t h, const void *d_in, int64_t in_stride, int64_
   }
   else if (path == ACDSP_PATH_LOSSLESS64) { e = launch_fir_lossless64(k, s); }
   else {
-    static const bool no_lossy = getenv("ACDSP_NO_LOSSY_FAST") != nullptr;   // A/B knob: the exact-order kernel for every per-tap class
+    const bool no_lossy = knob_no_lossy_fast();
     e = (!no_lossy && fir_lossy_fast_ok(k)) ? launch_fir_lossy(k, s) : ((!no_lossy && fir_satacc_fast_ok(k)) ? launch_fir_satacc(k, s) : launch_fir_generic(k, s));
   }
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "FIR kernel launch failed: %s", hipGetErrorString(e)); }
@@ -746,7 +730,7 @@ int32_t acdsp_fir_kernel_stats(acdsp_fir_t h, int32_t last_k, float *avg_ms, flo
 
 int32_t acdsp_fir_mfma_epilogue(acdsp_fir_t h) {
   if (!h || !h->coeffs_set || h->path != ACDSP_PATH_MFMA_I8) { return -1; }
-  return fir_mfma_epilogue_class(fir_class_params(h, h->mfma_cshift), h->plan) | (h->mfma_cshift << 8) | (h->in_flip ? 1 << 16 : 0);
+  return fir_mfma_epilogue_class(fir_cshifted(fir_params(h), h->mfma_cshift), h->plan) | (h->mfma_cshift << 8) | (h->in_flip ? 1 << 16 : 0);
 }
 
 int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples) {
@@ -754,7 +738,7 @@ int32_t acdsp_fir_mfma_issued(acdsp_fir_t h, int32_t *per_1024_samples) {
   if (!h->coeffs_set) { return fail(ACDSP_ESTATE, "acdsp_fir_mfma_issued before acdsp_fir_set_coeffs"); }
   *per_1024_samples = 0;
   if (h->path == ACDSP_PATH_MFMA_I8) {
-    *per_1024_samples = fir_mfma_issued_per_step(fir_class_params(h, h->mfma_cshift), h->plan);
+    *per_1024_samples = fir_mfma_issued_per_step(fir_cshifted(fir_params(h), h->mfma_cshift), h->plan);
   } else if (h->path == ACDSP_PATH_MFMA_LONG) {
     *per_1024_samples = fir_long_issued_per_step(h->lplan);
   } else if (h->path == ACDSP_PATH_MFMA_S8) {

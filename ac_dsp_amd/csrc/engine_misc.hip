@@ -162,8 +162,7 @@ int32_t acdsp_intgdump_run(acdsp_intgdump_t h, const void *d_in, int64_t in_stri
   // dumps and nothing is carried in, so a sum has at most max-rounds terms of at most max|x| each.
   bool sat_free = false;
   if (d.acc.O != ACDSP_WRAP && !h->pending && grp == n_blocks && p.acc.F >= p.in.F && p.acc.F - p.in.F < 64 - d.in.W && (d.acc.S || !d.in.S)) {
-    static const bool no_sat_free = getenv("ACDSP_NO_SAT_FREE") != nullptr;   // A/B knob
-    sat_free = !no_sat_free && sat_free_bound((unsigned __int128)h->tbl_max_rounds, d.in, d.acc, p.acc.F - p.in.F, 0, 0);
+    sat_free = !knob_no_sat_free() && sat_free_bound((unsigned __int128)h->tbl_max_rounds, d.in, d.acc, p.acc.F - p.in.F, 0, 0);
   }
   p.lossless = (d.acc.O == ACDSP_WRAP || sat_free) && p.acc.F >= p.in.F && p.acc.F - p.in.F < 64 - d.in.W;
   p.tile_ok = p.lossless && !h->pending && h->temp_zero && grp == n_blocks;
@@ -418,9 +417,8 @@ int32_t acdsp_mvavg_run(acdsp_mvavg_t h, const void *d_in, int64_t in_stride, in
   // A saturating ACC_TYPE that cannot saturate is a wrapping one (cf. acdsp_fir::sat_free): the cast of a sample is exact, and every partial sum
   // is bounded by sum|c| max|x| 2^d / 2^sh plus one LSB per tap, inside the type's symmetric range.  The kernels then see AC_WRAP.
   if (d.acc.O != ACDSP_WRAP && d.acc.S && !h->h_coeffs.empty() && !p.force_generic && (d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && d.acc.W <= 64) {
-    static const bool no_sat_free = getenv("ACDSP_NO_SAT_FREE") != nullptr;   // A/B knob
     const int dc = p.acc.F - p.in.F, sh = p.cf.F, i_in = d.in.I + (d.in.S ? 0 : 1);
-    if (!no_sat_free && dc >= 0 && dc < 40 && sh >= 0 && sh < 64 && d.acc.I >= i_in) {
+    if (!knob_no_sat_free() && dc >= 0 && dc < 40 && sh >= 0 && sh < 64 && d.acc.I >= i_in) {
       if (sat_free_bound(sum_abs(h->h_coeffs.data(), h->h_coeffs.size()), d.in, d.acc, dc, sh, h->h_coeffs.size() + 1)) { p.acc.O = ACDSP_WRAP; }
     }
   }

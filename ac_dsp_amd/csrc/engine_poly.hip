@@ -4,6 +4,22 @@
 using namespace acdsp;
 using namespace acdsp::eng;
 
+// acdsp_poly{dec,intr}_set_scratch_cap / _long_geometry: the LongScratch of a long-eligible handle (long_shape)
+template <typename H>
+static int poly_set_scratch_cap(H *h, uint64_t bytes) {
+  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
+  if (!h->long_shape) { return ACDSP_OK; }
+  if (const int rc = check_device(h->d.device)) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  return h->scratch.size(bytes);
+}
+template <typename H>
+static int poly_long_geometry(H *h, int64_t *slab, int32_t *group_channels, uint64_t *scratch_bytes) {
+  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
+  h->scratch.geometry(h->long_shape, slab, group_channels, scratch_bytes);
+  return ACDSP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // polyphase decimator
 // ---------------------------------------------------------------------------------------------
@@ -16,12 +32,11 @@ struct acdsp_polydec {
   DevBuf d_coeffs, d_gfrag;
   FirGenPlan gplan;
   // long prototypes (polydec_long.hip): long_shape = the descriptor is long-eligible and the ring kernel has no plan for its shape (create);
-  // long_ok = the current set runs there.  The scratch of the phase streams is sized at create / set_scratch_cap, never in run()
+  // long_ok = the current set runs there.  scratch: the phase streams
   bool long_shape = false, long_ok = false, in_flip = false;
   PolyDecLongPlan lplan;
-  LongGeom lgeo = {0, 0, 0};
-  uint64_t scratch_cap = (uint64_t)128 << 20;
-  DevBuf d_lfrag, d_lcorr, d_scratch;
+  LongScratch scratch;
+  DevBuf d_lfrag, d_lcorr;
   int last_path = ACDSP_PATH_GENERIC;
   int32_t last_ring = 0;   // ring-shape id of the last run(), 0 when no ring row ran
   Staging st;
@@ -40,21 +55,6 @@ const char *polydec_long_refusal(const acdsp_polydec_desc_t &d) {
   const int fi = d.in.W - d.in.I, fc = d.coeff.W - d.coeff.I, fa = d.acc.W - d.acc.I;
   if (fa < fi + fc || fa - fi - fc >= 64) { return "ACC_TYPE is not an exact-sum accumulator (F_acc >= F_in + F_coeff, shift below 64)"; }
   return nullptr;
-}
-
-// scratch of a long handle under `cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a
-// failure leaves cap, geometry and scratch as they were
-int polydec_size_scratch(acdsp_polydec *h, uint64_t cap) {
-  // phase rows of IN containers (int16, or bytes under ACDSP_FLAG_IN_BYTES): df * in_eb bytes per slab output, in front of them the reach of
-  // 32 (nb - 1) samples
-  const LongGeom geo = long_geometry((uint64_t)h->d.df * (uint64_t)h->in_eb, 32 * (uint64_t)(long_blocks(h->d.n_taps) - 1), h->d.n_channels, cap);
-  DevBuf fresh;
-  const int rc = fresh.alloc(geo.bytes);
-  if (rc) { return rc; }
-  h->d_scratch = std::move(fresh);   // (the old buffer goes with `fresh`)
-  h->lgeo = geo;
-  h->scratch_cap = cap;
-  return ACDSP_OK;
 }
 
 }  // namespace
@@ -105,8 +105,10 @@ int32_t acdsp_polydec_create(const acdsp_polydec_desc_t *desc, acdsp_polydec_t *
     // unsigned 16-bit samples: read as x - 32768, 32768 * sum(c) rides in the correction constant; unsigned bytes (ACDSP_FLAG_IN_BYTES,
     // polydec_s8.hip): read as x - 128, 128 * sum(c)
     h->in_flip = !desc->in.S && (in_bytes || desc->in.W == 16);
+    // scratch: phase rows of IN containers (int16, or bytes under ACDSP_FLAG_IN_BYTES), df * in_eb bytes per slab output, in front of them the
+    // reach of 32 (nb - 1) samples
     if ((rc = h->d_lfrag.alloc((size_t)2 * desc->df * long_blocks(desc->n_taps) * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc(sizeof(int64_t))) ||
-        (rc = polydec_size_scratch(h.get(), h->scratch_cap))) {
+        (rc = h->scratch.init((uint64_t)desc->df * (uint64_t)in_eb, 32 * (uint64_t)(long_blocks(desc->n_taps) - 1), desc->n_channels))) {
       return rc;
     }
   }
@@ -137,15 +139,13 @@ int32_t acdsp_polydec_set_coeffs(acdsp_polydec_t h, const int64_t *coeffs) {
   {
     // |every partial sum of an output| <= sum|c| max|x| over all NTAPS * DF coefficients: inside the symmetric range of a signed saturating
     // ACC_TYPE the saturation never acts (ACDSP_NO_SAT_FREE: A/B knob)
-    static const bool no_sat_free = getenv("ACDSP_NO_SAT_FREE") != nullptr;
-    const bool sf = !no_sat_free && d.acc.O != ACDSP_WRAP && d.acc.S && h->lossless_shape && d.acc.W >= 2 && d.acc.W <= 64 &&
+    const bool sf = !knob_no_sat_free() && d.acc.O != ACDSP_WRAP && d.acc.S && h->lossless_shape && d.acc.W >= 2 && d.acc.W <= 64 &&
                     sat_free_bound(sum_abs(coeffs, (size_t)n), d.in, d.acc, (d.acc.W - d.acc.I) - (d.in.W - d.in.I) - (d.coeff.W - d.coeff.I), 0, 0);
     h->sat_free = sf;
     h->lossless = h->lossless_shape && (d.acc.O == ACDSP_WRAP || sf);
   }
-  static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
   const bool in_bytes = (d.flags & ACDSP_FLAG_IN_BYTES) != 0;   // (a byte container holds every IN_TYPE the flag admits, unsigned ones re-biased)
-  if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !no_gen && (in_bytes || fits_container(d.in, h->in_eb))) {
+  if (h->lossless && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && !knob_no_gen() &&(in_bytes || fits_container(d.in, h->in_eb))) {
     // decimating FIR  y[g] = sum_k hh[k] x[g*DF + DF-1 - k],  hh[df + tp*DF] = c[tp + NTAPS*df]
     std::vector<int64_t> hh((size_t)n, 0);
     for (int df = 0; df < d.df; df++) { for (int tp = 0; tp < d.n_taps; tp++) { hh[df + tp * d.df] = coeffs[tp + d.n_taps * df]; } }
@@ -161,23 +161,18 @@ int32_t acdsp_polydec_set_coeffs(acdsp_polydec_t h, const int64_t *coeffs) {
   // handle stays without a set.
   h->long_ok = false;
   if (h->long_shape) {
-    std::vector<uint32_t> fr;
-    if (!h->lossless) {
-      if (n > 2048) {
-        h->coeffs_set = false;
-        return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %d: the saturating ACC_TYPE cannot be proven saturation-free for this coefficient set, and more than 2048 taps have no exact-order kernel", n);
-      }
-    } else if (polydec_long_plan(coeffs, d.n_taps, d.df, &h->lplan, &fr)) {
+    rc = long_or_nothing("poly_dec: NTAPS*DF = ", n, h->lossless, h->d_lfrag, h->d_lcorr, [&](std::vector<uint32_t> *fr, int64_t *corr) {
+      if (!polydec_long_plan(coeffs, d.n_taps, d.df, &h->lplan, fr)) { return false; }
       int64_t sc = 0;
       for (int i = 0; i < n; i++) { sc += coeffs[i]; }
       if (in_bytes) { h->lplan.corr = h->in_flip ? 128 * sc : 0; }   // one sample plane: no low plane to re-bias
       else if (h->in_flip) { h->lplan.corr += 32768 * sc; }
-      if ((rc = h->d_lfrag.upload(fr.data(), fr.size() * sizeof(uint32_t))) || (rc = h->d_lcorr.upload(&h->lplan.corr, sizeof(int64_t)))) { return rc; }
-      h->long_ok = true;
-    } else if (n > 2048) {
-      h->coeffs_set = false;
-      return fail(ACDSP_EUNSUPPORTED, "poly_dec: NTAPS*DF = %d: a coefficient of 32640 or more cannot be split into two signed bytes, and more than 2048 taps run on the matrix cores only", n);
-    }
+      *corr = h->lplan.corr;
+      return true;
+    });
+    h->long_ok = rc == kTaken;
+    if (rc == ACDSP_EUNSUPPORTED) { h->coeffs_set = false; }   // (a refusal: the handle stays without a set)
+    if (rc > 0) { return rc; }
   }
   h->coeffs_set = true;
   return ACDSP_OK;
@@ -187,21 +182,9 @@ int32_t acdsp_polydec_path(acdsp_polydec_t h) { return h ? h->last_path : -1; }
 int32_t acdsp_polydec_in_elem_bytes(acdsp_polydec_t h) { return h ? h->in_eb : -1; }
 int32_t acdsp_polydec_ring_shape(acdsp_polydec_t h) { return h ? h->last_ring : -1; }
 
-int32_t acdsp_polydec_set_scratch_cap(acdsp_polydec_t h, uint64_t bytes) {
-  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
-  if (!h->long_shape) { return ACDSP_OK; }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());
-  return polydec_size_scratch(h, bytes);
-}
-
+int32_t acdsp_polydec_set_scratch_cap(acdsp_polydec_t h, uint64_t bytes) { return poly_set_scratch_cap(h, bytes); }
 int32_t acdsp_polydec_long_geometry(acdsp_polydec_t h, int64_t *slab_outputs, int32_t *group_channels, uint64_t *scratch_bytes) {
-  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
-  if (slab_outputs) { *slab_outputs = h->long_shape ? h->lgeo.slab : 0; }
-  if (group_channels) { *group_channels = h->long_shape ? h->lgeo.group : 0; }
-  if (scratch_bytes) { *scratch_bytes = h->long_shape ? h->lgeo.bytes : 0; }
-  return ACDSP_OK;
+  return poly_long_geometry(h, slab_outputs, group_channels, scratch_bytes);
 }
 
 int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride,
@@ -216,26 +199,23 @@ int32_t acdsp_polydec_run(acdsp_polydec_t h, const void *d_in, int64_t in_stride
   int rc = check_device(d.device);
   if (rc) { return rc; }
   hipStream_t s = (hipStream_t)stream;
-  FirParams k;
-  memset(&k, 0, sizeof k);
-  k.n_taps = d.n_taps * d.df; k.ftype = ACDSP_SHIFT_REG; k.n_ch = d.n_channels;
-  k.in = make_dfmt(d.in); k.cf = make_dfmt(d.coeff); k.acc = make_dfmt(d.acc); k.out = make_dfmt(d.out);
+  FirParams k = fir_params_of(make_dfmt(d.in), make_dfmt(d.coeff), make_dfmt(d.acc), make_dfmt(d.out), h->in_eb, h->out_eb, h->hl, d.n_channels,
+                              {d_in, in_stride, n_in, d_out, out_stride});
+  k.n_taps = d.n_taps * d.df; k.ftype = ACDSP_SHIFT_REG;
   if (h->sat_free) { k.acc.O = ACDSP_WRAP; }
-  k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl;
   k.lossless_shift = k.acc.F - k.in.F - k.cf.F;
-  k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in;
-  k.x = d_in; k.y = d_out; k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>();
-  const bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && in_stride >= (n_in + 15) / 16 * 16;
+  k.hist = h->hist.cur(); k.coeffs = h->d_coeffs.get<int64_t>();
+  const bool aligned = rows_in_slots(d_in, in_stride, h->in_eb, n_in);
   hipError_t e;
   h->last_ring = 0;
   if (h->long_ok) {   // every call, whatever its length or alignment
     k.in_flip = h->in_flip;
     if (h->in_eb == 1) {
       h->last_path = ACDSP_PATH_MFMA_S8;
-      e = launch_polydec_s8(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_scratch.get(), n_out, s);
+      e = launch_polydec_s8(k, h->lplan, h->scratch.geo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->scratch.buf.get(), n_out, s);
     } else {
       h->last_path = ACDSP_PATH_MFMA_LONG;
-      e = launch_polydec_long(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_scratch.get(), n_out, s);
+      e = launch_polydec_long(k, h->lplan, h->scratch.geo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->scratch.buf.get(), n_out, s);
     }
   } else if (h->gen_ok && aligned) {
     h->last_path = ACDSP_PATH_MFMA_GEN;
@@ -279,7 +259,7 @@ int32_t acdsp_polydec_clone(acdsp_polydec_t h, acdsp_polydec_t *out) {
   int rc = acdsp_polydec_create(&h->d, &c);
   if (rc) { return rc; }
   std::unique_ptr<acdsp_polydec, int32_t (*)(acdsp_polydec_t)> guard(c, acdsp_polydec_destroy);
-  if (c->long_shape && h->scratch_cap != c->scratch_cap && (rc = polydec_size_scratch(c, h->scratch_cap))) { return rc; }
+  if (c->long_shape && h->scratch.cap != c->scratch.cap && (rc = c->scratch.size(h->scratch.cap))) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
   if (h->coeffs_set) {
     std::vector<int64_t> cf((size_t)h->d.n_taps * h->d.df);
@@ -343,12 +323,11 @@ struct acdsp_polyintr {
   int64_t up_max_abs = -1;      // bound on |z| of the folded taps (enables the 32-bit epilogue)
   DevBuf d_upfrag, d_upcorr;
   // long sub-filters (polyintr_long.hip): long_shape = the descriptor is long-capable (create); long_ok = the current control words run
-  // there.  The scratch of the phase rows is sized at create / set_scratch_cap, never in run()
+  // there.  scratch: the phase rows
   bool long_shape = false, long_ok = false;
   PolyIntrLongPlan lplan;
-  LongGeom lgeo = {0, 0, 0};
-  uint64_t scratch_cap = (uint64_t)128 << 20;
-  DevBuf d_lfrag, d_lcorr, d_lhalve, d_scratch;
+  LongScratch scratch;
+  DevBuf d_lfrag, d_lcorr, d_lhalve;
   int last_path = ACDSP_PATH_GENERIC;
   Staging st;
 };
@@ -377,20 +356,6 @@ const char *polyintr_long_refusal(const acdsp_polyintr_desc_t &d) {
   }
   if ((int64_t)d.ifac * long_blocks(nt) > kPolyIntrLongMaxBlocks) { return "IF * K-blocks per phase above the K-block budget of 1024"; }
   return nullptr;
-}
-
-// scratch of a long handle under `cap` (the caller has drained the device when a buffer is live).  The new buffer is allocated first: a
-// failure leaves cap, geometry and scratch as they were
-int polyintr_size_scratch(acdsp_polyintr *h, uint64_t cap) {
-  // phase rows of OUT containers: ifac * out_eb bytes per slab input sample, no head
-  const LongGeom geo = long_geometry((uint64_t)h->d.ifac * h->out_eb, 0, h->d.n_channels, cap);
-  DevBuf fresh;
-  const int rc = fresh.alloc(geo.bytes);
-  if (rc) { return rc; }
-  h->d_scratch = std::move(fresh);   // (the old buffer goes with `fresh`)
-  h->lgeo = geo;
-  h->scratch_cap = cap;
-  return ACDSP_OK;
 }
 
 // Per-phase taps of ac_poly_intr as one linear filter of the input (host side; see fir_up.hip).  E[j][k] multiplies
@@ -508,13 +473,13 @@ int32_t acdsp_polyintr_create(const acdsp_polyintr_desc_t *desc, acdsp_polyintr_
     const int nb = long_blocks(d.n_taps + polyintr_lag(d));
     // a step reaches 32 (nb - 1) samples back: inside the history as far as real taps go (nt - 1 <= NTAPS), beyond it over zero-padded taps only
     if (h->hl < d.n_taps || h->hl % 32 || 32 * (nb - 1) > h->hl) { return fail(ACDSP_EHIP, "internal: history of %d samples is shorter than the long kernel's reach", h->hl); }
+    // scratch: phase rows of OUT containers, ifac * out_eb bytes per slab input sample, no head
     if ((rc = h->d_lfrag.alloc((size_t)2 * d.ifac * nb * 64 * 4 * sizeof(uint32_t))) || (rc = h->d_lcorr.alloc((size_t)d.ifac * sizeof(int64_t))) ||
-        (rc = h->d_lhalve.alloc((size_t)d.ifac)) || (rc = polyintr_size_scratch(h.get(), h->scratch_cap))) {
+        (rc = h->d_lhalve.alloc((size_t)d.ifac)) || (rc = h->scratch.init((uint64_t)d.ifac * out_eb, 0, d.n_channels))) {
       if (d.n_taps > 2048) { return rc; }
       // up to 2048 taps the handle existed without these buffers: it stays what it was, on the exact kernels
       h->long_shape = false;
-      h->d_lfrag = DevBuf(); h->d_lcorr = DevBuf(); h->d_lhalve = DevBuf(); h->d_scratch = DevBuf();
-      h->lgeo = {0, 0, 0};
+      h->d_lfrag = DevBuf(); h->d_lcorr = DevBuf(); h->d_lhalve = DevBuf(); h->scratch = LongScratch();
       (void)hipGetLastError();
     }
   }
@@ -586,13 +551,12 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
   // matrix-core path: exact-accumulation class, int16 / int32 samples or int8 rows (ACDSP_FLAG_IN_BYTES: one plane), control words that keep the cores linear, and an
   // accumulator that cannot wrap (the symmetric-pair halving (t1 -/+ t2) >> 1 does not commute with a wrap)
   h->up_ok = false;
-  static const bool no_gen = getenv("ACDSP_NO_GEN") != nullptr;
   // (a 64-bit ACC_TYPE -- the header's own usage example, ac_poly_intr.h:45-48: <32,16> samples and coefficients into <64,32> -- belongs to
   // the class when the control words bound every sub-filter sum to 62 bits: nothing can wrap and the pair sum t1 -/+ t2 stays inside int64)
   h->acc64_ok = lossless && d.acc.W == 64 && no_wrap;
   const int upx = h->in_eb;
   // (a long-capable handle has nt >= 65 taps per phase: fir_up_plan has no plan there)
-  if (!h->long_shape && no_wrap && !no_gen && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && (h->in_eb == 1 || h->in_eb == 2 || h->in_eb == 4) && d.ifac <= 32) {
+  if (!h->long_shape && no_wrap && !knob_no_gen() && !(d.flags & ACDSP_FLAG_FORCE_GENERIC) && (h->in_eb == 1 || h->in_eb == 2 || h->in_eb == 4) && d.ifac <= 32) {
     std::vector<uint32_t> frag;
     std::vector<int64_t> ucorr;
     FirUpPlan pl;
@@ -614,21 +578,9 @@ int32_t acdsp_polyintr_set_ctrl(acdsp_polyintr_t h, const int64_t *coeffs, const
   return ACDSP_OK;
 }
 
-int32_t acdsp_polyintr_set_scratch_cap(acdsp_polyintr_t h, uint64_t bytes) {
-  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
-  if (!h->long_shape) { return ACDSP_OK; }
-  int rc = check_device(h->d.device);
-  if (rc) { return rc; }
-  HIP_TRY(hipDeviceSynchronize());
-  return polyintr_size_scratch(h, bytes);
-}
-
+int32_t acdsp_polyintr_set_scratch_cap(acdsp_polyintr_t h, uint64_t bytes) { return poly_set_scratch_cap(h, bytes); }
 int32_t acdsp_polyintr_long_geometry(acdsp_polyintr_t h, int64_t *slab_inputs, int32_t *group_channels, uint64_t *scratch_bytes) {
-  if (!h) { return fail(ACDSP_EINVAL, "null handle"); }
-  if (slab_inputs) { *slab_inputs = h->long_shape ? h->lgeo.slab : 0; }
-  if (group_channels) { *group_channels = h->long_shape ? h->lgeo.group : 0; }
-  if (scratch_bytes) { *scratch_bytes = h->long_shape ? h->lgeo.bytes : 0; }
-  return ACDSP_OK;
+  return poly_long_geometry(h, slab_inputs, group_channels, scratch_bytes);
 }
 
 int64_t acdsp_polyintr_out_count(acdsp_polyintr_t h, int64_t n_in) {
@@ -667,6 +619,7 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
                  d.acc.I >= d.in.I + 1 && (d.acc.W <= 63 || h->acc64_ok) && (d.in.O == ACDSP_WRAP || d.in.O == ACDSP_SAT || d.in.O == ACDSP_SAT_SYM || d.in.O == ACDSP_SAT_ZERO);
   }
   p.in_stride = in_stride; p.out_stride = out_stride; p.n = n_in; p.n_out = no;
+  const CallRows rows = {d_in, in_stride, n_in, d_out, out_stride};
   const int nxt = h->hist.next(false);   // (always the other buffer: the saved sums flip with it)
   int64_t *const saved_next = h->d_saved[nxt].get<int64_t>();
   p.x = d_in; p.y = d_out; p.hist = h->hist.cur();
@@ -690,11 +643,9 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
       if (ef != hipSuccess) { return fail(ACDSP_EHIP, "poly_intr side stream: %s", hipGetErrorString(ef)); }
       forked = true;
     }
-    FirParams k;
-    memset(&k, 0, sizeof k);
-    k.n_ch = d.n_channels; k.in = p.in; k.cf = p.cf; k.acc = p.acc; k.out = p.out; k.in_eb = h->in_eb; k.out_eb = h->out_eb; k.hl = h->hl;
-    k.lossless_shift = p.lossless_shift; k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in; k.x = d_in; k.y = d_out; k.hist = p.hist;
-    e = launch_polyintr_long(k, h->lplan, h->lgeo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_lhalve.get<uint8_t>(), h->d_scratch.get(),
+    FirParams k = fir_params_of(p.in, p.cf, p.acc, p.out, h->in_eb, h->out_eb, h->hl, d.n_channels, rows);
+    k.lossless_shift = p.lossless_shift; k.hist = p.hist;
+    e = launch_polyintr_long(k, h->lplan, h->scratch.geo, h->d_lfrag.get<uint32_t>(), h->d_lcorr.get<int64_t>(), h->d_lhalve.get<uint8_t>(), h->scratch.buf.get(),
                              p.skip, o_lo, no, s);
     if (e != hipSuccess) {
       if (forked) { (void)h->side.join(s); }
@@ -709,7 +660,7 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
     // first call one input's outputs = 4 bytes into the 8-byte grid.  1-byte rows: the first call of a folded core starts IF bytes in front
     // of the row, so a factor that is no multiple of 4 leaves THAT call on the VALU kernels (later calls have out_off = 0)
     const int64_t oal = h->out_eb >= 8 ? 8 : 4;
-    const bool aligned = ((uintptr_t)d_in % 16 == 0) && ((in_stride * h->in_eb) % 16 == 0) && ((uintptr_t)d_out % oal == 0) &&
+    const bool aligned = rows_vec_aligned(d_in, in_stride, h->in_eb) && ((uintptr_t)d_out % oal == 0) &&
                          ((out_stride * h->out_eb) % oal == 0) && ((out_off * h->out_eb) % oal == 0);
     if (aligned && n_steps > 0) {
       // the head and the tail of the call (two launches of a few thousand waves, 16 us each, + the saved sums) neither feed nor follow the
@@ -719,10 +670,8 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
         if (ef != hipSuccess) { return fail(ACDSP_EHIP, "poly_intr side stream: %s", hipGetErrorString(ef)); }
         forked = true;
       }
-      FirParams k;
-      memset(&k, 0, sizeof k);
-      k.n_ch = d.n_channels; k.in = p.in; k.cf = p.cf; k.acc = p.acc; k.out = p.out; k.in_eb = h->in_eb; k.out_eb = h->out_eb;
-      k.lossless_shift = p.lossless_shift; k.in_stride = in_stride; k.out_stride = out_stride; k.n = n_in; k.x = d_in; k.y = d_out;
+      FirParams k = fir_params_of(p.in, p.cf, p.acc, p.out, h->in_eb, h->out_eb, 0, d.n_channels, rows);   // (no history: whole steps inside the call)
+      k.lossless_shift = p.lossless_shift;
       e = launch_fir_up(k, h->up_plan, h->up_px, h->d_upfrag.get<uint32_t>(), h->d_upcorr.get<int64_t>(), 0, 0, 0, h->up_shmask, h->up_max_abs, slot_a, n_steps, out_off, s);
       if (e == hipSuccess) {
         o_a = 16 * slot_a * L + out_off; o_b = 16 * (slot_a + 32 * n_steps) * L + out_off;
@@ -744,9 +693,8 @@ int32_t acdsp_polyintr_run(acdsp_polyintr_t h, const void *d_in, int64_t in_stri
   }
   hipError_t eh = hipSuccess;
   if (e == hipSuccess) {
-    FirParams k;
-    memset(&k, 0, sizeof k);
-    k.n_ch = d.n_channels; k.in = p.in; k.in_eb = h->in_eb; k.hl = h->hl; k.in_stride = in_stride; k.n = n_in; k.x = d_in; k.hist = p.hist;
+    FirParams k = fir_params_of(p.in, DFmt(), DFmt(), DFmt(), h->in_eb, 0, h->hl, d.n_channels, {d_in, in_stride, n_in, nullptr, 0});   // (input side only)
+    k.hist = p.hist;
     eh = launch_fir_hist_update(k, h->hist.at(nxt), vs);   // (never in place -- so it may run beside the main kernel too)
   }
   if (forked) {   // (always joined, used or not: an unjoined fork is an error under stream capture)
@@ -795,7 +743,7 @@ int32_t acdsp_polyintr_clone(acdsp_polyintr_t h, acdsp_polyintr_t *out) {
   if (rc) { return rc; }
   std::unique_ptr<acdsp_polyintr, int32_t (*)(acdsp_polyintr_t)> guard(c, acdsp_polyintr_destroy);
   if (c->long_shape != h->long_shape) { return fail(ACDSP_EHIP, "polyintr_clone: the buffers of the long kernels could not be allocated a second time"); }
-  if (c->long_shape && h->scratch_cap != c->scratch_cap && (rc = polyintr_size_scratch(c, h->scratch_cap))) { return rc; }
+  if (c->long_shape && h->scratch.cap != c->scratch.cap && (rc = c->scratch.size(h->scratch.cap))) { return rc; }
   HIP_TRY(hipDeviceSynchronize());
   if (h->ctrl_set) {
     std::vector<int64_t> cf((size_t)h->d.coeff_sz);

@@ -71,6 +71,11 @@ def grid():
                             yield key, (nt, ftype, fin, fc, fa, fo, kind, per_ch, sname)
 
 
+def _resolved(fir):
+    e = fir.mfma_epilogue()
+    return "%s/%d" % (fir.kernel, fir.mfma_issued()) + ("" if e is None else "/e%d%s%s" % (e[0], "+c%d" % e[1] if e[1] else "", "+flip" if e[2] else ""))
+
+
 def resolve(args):
     nt, ftype, fin, fc, fa, fo, kind, per_ch, sname = args
     try:
@@ -82,5 +87,56 @@ def resolve(args):
         fir.set_coeffs(np.stack([c, c]) if per_ch else c)
     except A.AcdspError:
         return "rejected_set"
-    e = fir.mfma_epilogue()
-    return "%s/%d" % (fir.kernel, fir.mfma_issued()) + ("" if e is None else "/e%d%s%s" % (e[0], "+c%d" % e[1] if e[1] else "", "+flip" if e[2] else ""))
+    return _resolved(fir)
+
+
+# ---- the second grid (tests/golden/path_map_fir_rows.json): what the first one leaves out -- the tap counts around the long kernel's range
+# (1026 .. 16384; above 2048 taps a set runs on the matrix cores or is refused) and 1-byte rows.  Creation and set_coeffs only.
+ROW_TAPS = [1, 33, 1025, 1026, 2048, 2049, 16384]
+_O16, _O8 = F(16, 2, True, "RND", "SAT"), F(8, 1, True, "RND", "SAT")
+ROW_TYPES = {
+    # name: (IN, COEFF, ACC, OUT, in_bytes, out_bytes)
+    "i16_exact": TYPES["i16_exact"] + (_O16, False, False),
+    "u16": TYPES["u16"] + (_O16, False, False),
+    "i16_sat_acc": TYPES["i16_sat_acc"] + (_O16, False, False),      # "small" is saturation-free, "dense" is not
+    # exact-sum shapes under a saturating accumulator: above 2048 taps a set that is not provably saturation-free is refused
+    "i16_exact_sat": (F(16, 2), F(16, 2), F(40, 12, True, "TRN", "SAT"), _O16, False, False),
+    "s8_in_bytes_sat": (F(8, 1), F(8, 1), F(22, 7, True, "TRN", "SAT"), _O16, True, False),
+    "s8_in_bytes": (F(8, 1), F(8, 1), F(22, 7), _O16, True, False),
+    "u8_in_bytes": (F(8, 1, False), F(8, 1), F(22, 7), _O16, True, False),
+    "s8_in_out_bytes": (F(8, 1), F(8, 1), F(22, 7), _O8, True, True),
+    "u8_in_out_bytes": (F(8, 1, False), F(8, 1), F(22, 7), _O8, True, True),
+}
+ROW_KINDS_FTYPES = [("load", "SHIFT_REG"), ("const", "FOLD_EVEN"), ("load", "TRANSPOSED"), ("reg_share", "FOLD_ODD_ANTI")]
+ROW_PER_CH_TAPS = [63, 2049]
+
+
+def row_coeffs_of(kind_of_set, n_taps, fc):
+    """coeffs_of, with a full-scale first tap in every "dense" set: a 16-bit raw word of 32640 or more is what the two-byte split refuses"""
+    c = coeffs_of(kind_of_set, n_taps, fc).copy()
+    if kind_of_set == "dense":
+        c[0] = (1 << (fc.W - 1)) - 1
+    return c
+
+
+def grid_rows():
+    """yields (key, arguments of resolve_rows); the tap counts go in as they are (FOLD_EVEN on an odd count included)"""
+    for tname, (fin, fc, fa, fo, in_b, out_b) in ROW_TYPES.items():
+        for kind, ftype in ROW_KINDS_FTYPES:
+            for n_taps in ROW_TAPS:
+                for sname in SETS:
+                    yield "%s|%d|%s|%s|%s|0" % (tname, n_taps, kind, ftype, sname), (n_taps, ftype, fin, fc, fa, fo, kind, False, sname, in_b, out_b)
+        for n_taps in ROW_PER_CH_TAPS:
+            yield "%s|%d|load|SHIFT_REG|sinc|1" % (tname, n_taps), (n_taps, "SHIFT_REG", fin, fc, fa, fo, "load", True, "sinc", in_b, out_b)
+
+
+def resolve_rows(args):
+    """as resolve(); a refused create or set is recorded with the library's message"""
+    nt, ftype, fin, fc, fa, fo, kind, per_ch, sname, in_b, out_b = args
+    c = row_coeffs_of(sname, nt, fc)
+    try:
+        fir = A.Fir(nt, ftype, fin, fc, fa, fo, n_channels=2, kind=kind, coeffs_per_channel=per_ch, in_bytes=in_b, out_bytes=out_b)
+        fir.set_coeffs(np.stack([c, c]) if per_ch else c)
+    except A.AcdspError as e:
+        return "rejected: " + str(e).split(": ", 1)[1]
+    return _resolved(fir)

@@ -13,6 +13,7 @@ import pathmap_ops as GO
 pytestmark = pytest.mark.gpu
 TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "path_map.json")
 TABLE_OPS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "path_map_ops.json")
+TABLE_ROWS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "path_map_fir_rows.json")
 
 
 def test_every_descriptor_of_the_grid_resolves_as_committed():
@@ -22,6 +23,19 @@ def test_every_descriptor_of_the_grid_resolves_as_committed():
     assert set(got) == set(want), "grid changed: regenerate tests/golden/path_map.json (tools/gen_path_map.py)"
     diff = ["%s: committed %s, now %s" % (k, want[k], got[k]) for k in sorted(got) if got[k] != want[k]]
     assert not diff, "%d of %d descriptors resolve differently:\n%s" % (len(diff), len(got), "\n".join(diff[:40]))
+
+
+def test_every_long_and_byte_row_descriptor_resolves_as_committed():
+    """The second grid of tests/pathmap_grid.py: 1 .. 16384 taps around the long kernel's limits, 16-bit and 1-byte rows, shared and per-channel
+    sets.  A refused create or set is pinned with its message."""
+    with open(TABLE_ROWS) as f:
+        want = json.load(f)
+    got = {k: G.resolve_rows(a) for k, a in G.grid_rows()}
+    assert set(got) == set(want), "grid changed: regenerate tests/golden/path_map_fir_rows.json (tools/gen_path_map.py)"
+    diff = ["%s: committed %s, now %s" % (k, want[k], got[k]) for k in sorted(got) if got[k] != want[k]]
+    assert not diff, "%d of %d descriptors resolve differently:\n%s" % (len(diff), len(got), "\n".join(diff[:40]))
+    fams = {v.split("/")[0] for v in want.values() if not v.startswith("rejected")}
+    assert {"mfma_i8", "mfma_long", "mfma_s8", "lossless64", "generic"} <= fams, fams
 
 
 def test_the_grid_reaches_every_family():

@@ -24,6 +24,18 @@ for v in table.values():
 print("%d descriptors -> %s" % (len(table), out))
 print(json.dumps(fam, sort_keys=True))
 
+# the long tap counts and the byte rows (grid_rows): creation and set_coeffs only, refusals with their messages
+out1 = os.path.join(os.path.dirname(out), "path_map_fir_rows.json")
+t1 = {k: G.resolve_rows(a) for k, a in G.grid_rows()}
+with open(out1, "w") as f:
+    json.dump(t1, f, indent=0, sort_keys=True)
+fam1 = {}
+for v in t1.values():
+    key = "rejected" if v.startswith("rejected") else v.split("/")[0]
+    fam1[key] = fam1.get(key, 0) + 1
+print("%d descriptors -> %s" % (len(t1), out1))
+print(json.dumps(fam1, sort_keys=True))
+
 # the other families (tests/pathmap_ops.py): one small call per descriptor
 import pathmap_ops as GO  # noqa: E402
 out2 = os.path.join(os.path.dirname(out), "path_map_ops.json")
