@@ -130,6 +130,7 @@ SYMBOLS = {
     "acdsp_node_cic_run": (_i32, [_vp, C.POINTER(_vp), _i64, _i64, C.POINTER(_vp), _i64, C.POINTER(_i64)]),
     "acdsp_node_ddc_create": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), _i32, C.POINTER(_i32), C.POINTER(_vp)]),
     "acdsp_node_ddc_create_ex": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), _i32, _i32, C.POINTER(_i32), C.POINTER(_vp)]),
+    "acdsp_node_ddc_create_polydec": (_i32, [C.POINTER(CicDesc), C.POINTER(PolyDecDesc), _i32, _i32, C.POINTER(_i32), C.POINTER(_vp)]),
     "acdsp_node_ddc_set_coeffs": (_i32, [_vp, C.POINTER(_i64)]),
     "acdsp_node_ddc_out_count": (_i64, [_vp, _i64]),
     "acdsp_node_ddc_run": (_i32, [_vp, C.POINTER(_vp), _i64, _i64, C.POINTER(_vp), _i64, C.POINTER(_i64)]),
@@ -249,6 +250,7 @@ SYMBOLS = {
     "acdsp_stream_read": (_i32, [C.c_char_p, _vp, C.c_uint64]),
     "acdsp_ddc_create": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), C.POINTER(_vp)]),
     "acdsp_ddc_create_ex": (_i32, [C.POINTER(CicDesc), C.POINTER(FirDesc), _i32, C.POINTER(_vp)]),
+    "acdsp_ddc_create_polydec": (_i32, [C.POINTER(CicDesc), C.POINTER(PolyDecDesc), _i32, C.POINTER(_vp)]),
     "acdsp_ddc_in_elem_bytes": (_i32, [_vp]),
     "acdsp_ddc_destroy": (_i32, [_vp]),
     "acdsp_ddc_set_coeffs": (_i32, [_vp, C.POINTER(_i64)]),

@@ -449,15 +449,23 @@ int32_t acdsp_cic_state_set(acdsp_cic_t h, const void *buf, uint64_t bytes) {
 
 // DDC cascade.  Fused mode: the input history + input count are the whole state (stage B's window is recomputed from it):
 // one kind-4 blob.  Two-kernel mode: a kind-5 header followed by the stage blobs (CIC, then FIR).
+// Polydec cascade (acdsp_ddc_create_polydec): kinds 9 (fused; the queued words are recomputed from history and count) and 10 (two kernels: the
+// CIC blob, the ac_poly_dec blob and [channel][DF - 1] queued INT_TYPE words, the first t_total of each row valid); p3 = NTAPS and the high
+// half of `reserved` = DF, so a FIR cascade and a polydec cascade refuse each other's blobs by kind and by parameters.
+static uint64_t ddc_queue_bytes(const acdsp_ddc *h) { return h->pd ? (uint64_t)h->cic->d.n_channels * (uint64_t)(h->df - 1) * (uint64_t)h->cic->out_eb : 0; }
+static int64_t ddc_stage_b_state_size(const acdsp_ddc *h) { return h->pd ? acdsp_polydec_state_size(h->pd) : acdsp_fir_state_size(h->fir); }
+
 static StateHdr ddc_state_hdr(const acdsp_ddc *h) {
-  StateHdr s = state_hdr(h->fused ? 4 : 5, 0, 0, 0);
+  StateHdr s = state_hdr(h->pd ? (h->fused ? 9 : 10) : (h->fused ? 4 : 5), 0, 0, 0);
   s.n_channels = (uint32_t)h->cic->d.n_channels;
-  s.p0 = (uint32_t)h->cic->d.R; s.p1 = (uint32_t)h->cic->d.M; s.p2 = (uint32_t)h->cic->d.N; s.p3 = (uint32_t)h->fir->d.n_taps;
+  s.p0 = (uint32_t)h->cic->d.R; s.p1 = (uint32_t)h->cic->d.M; s.p2 = (uint32_t)h->cic->d.N; s.p3 = (uint32_t)(h->pd ? h->pd->d.n_taps : h->fir->d.n_taps);
+  if (h->pd) { s.reserved = (uint64_t)h->df << 32; }
   if (h->fused) { s.elem_bytes = (uint32_t)h->cic->in_eb; s.per_channel = (uint64_t)h->hl; s.t_total = h->t_total; }
-  else {   // payload = the two stage blobs; per_channel x elem_bytes x n_channels must give its size
+  else {   // payload = the two stage blobs (+ the queue); per_channel x elem_bytes x n_channels must give its size
     s.elem_bytes = 1; s.n_channels = 1;
-    s.per_channel = (uint64_t)(acdsp_cic_state_size(h->cic) + acdsp_fir_state_size(h->fir));
-    s.reserved = (uint64_t)h->cic->d.n_channels;
+    s.per_channel = (uint64_t)(acdsp_cic_state_size(h->cic) + ddc_stage_b_state_size(h)) + ddc_queue_bytes(h);
+    s.reserved |= (uint64_t)h->cic->d.n_channels;
+    if (h->pd) { s.t_total = h->n_q; }
   }
   return s;
 }
@@ -470,9 +478,33 @@ int32_t acdsp_ddc_state_get(acdsp_ddc_t h, void *buf, uint64_t cap_bytes) {
   // (two-kernel mode: the payload is the two stage blobs, which the stage functions write)
   int rc = state_blob_get("ddc", h->cic->d.device, s, {{h->fused ? h->hist.cur() : nullptr, state_payload(s)}}, buf, cap_bytes);
   if (rc || h->fused) { return rc; }
-  const uint64_t nc = (uint64_t)acdsp_cic_state_size(h->cic);
+  const uint64_t nc = (uint64_t)acdsp_cic_state_size(h->cic), nb = (uint64_t)ddc_stage_b_state_size(h);
   if ((rc = acdsp_cic_state_get(h->cic, (char *)buf + sizeof s, nc))) { return rc; }
-  return acdsp_fir_state_get(h->fir, (char *)buf + sizeof s + nc, state_payload(s) - nc);
+  if (!h->pd) { return acdsp_fir_state_get(h->fir, (char *)buf + sizeof s + nc, nb); }
+  if ((rc = acdsp_polydec_state_get(h->pd, (char *)buf + sizeof s + nc, nb))) { return rc; }
+  char *q = (char *)buf + sizeof s + nc + nb;
+  memset(q, 0, ddc_queue_bytes(h));
+  if (h->n_q > 0) {
+    const size_t eb = (size_t)h->cic->out_eb;
+    HIP_TRY(hipMemcpy2D(q, (size_t)(h->df - 1) * eb, h->d_mid.get(), (size_t)h->mid_cap * eb, (size_t)h->n_q * eb, (size_t)h->cic->d.n_channels, hipMemcpyDeviceToHost));
+  }
+  return ACDSP_OK;
+}
+
+// The three parts of a two-kernel polydec blob -- CIC blob, ac_poly_dec blob, n_q queued words per channel in rows of DF - 1 -- into the handle,
+// whose intermediate rows hold ddc_queue_cap(DF) words at least
+static int ddc_polydec_state_apply(acdsp_ddc *h, int64_t n_q, const char *pay, uint64_t nc, uint64_t nb) {
+  int rc;
+  if ((rc = acdsp_cic_state_set(h->cic, pay, nc)) || (rc = acdsp_polydec_state_set(h->pd, pay + nc, nb))) { return rc; }
+  HIP_TRY(hipDeviceSynchronize());
+  h->n_q = 0;
+  if (n_q > 0) {
+    const size_t eb = (size_t)h->cic->out_eb;
+    HIP_TRY(hipMemcpy2D(h->d_mid.get(), (size_t)h->mid_cap * eb, pay + nc + nb, (size_t)(h->df - 1) * eb, (size_t)n_q * eb, (size_t)h->cic->d.n_channels,
+                        hipMemcpyHostToDevice));
+    h->n_q = n_q;
+  }
+  return ACDSP_OK;
 }
 
 int32_t acdsp_ddc_state_set(acdsp_ddc_t h, const void *buf, uint64_t bytes) {
@@ -488,11 +520,27 @@ int32_t acdsp_ddc_state_set(acdsp_ddc_t h, const void *buf, uint64_t bytes) {
     h->t_total = s.t_total;
     return ACDSP_OK;
   }
-  if (!state_compatible(s, mine) || bytes != sizeof s + state_payload(mine) || s.t_total < 0) { return fail(ACDSP_EINVAL, "ddc_state_set: %s", kRefusal); }
+  if (!state_compatible(s, mine) || bytes != sizeof s + state_payload(mine) || s.t_total < 0 || (h->pd && s.t_total >= h->df)) {
+    return fail(ACDSP_EINVAL, "ddc_state_set: %s", kRefusal);
+  }
   if ((rc = check_device(h->cic->d.device))) { return rc; }
-  const uint64_t nc = (uint64_t)acdsp_cic_state_size(h->cic);
-  if ((rc = acdsp_cic_state_set(h->cic, (const char *)buf + sizeof s, nc))) { return rc; }
-  return acdsp_fir_state_set(h->fir, (const char *)buf + sizeof s + nc, state_payload(mine) - nc);
+  const uint64_t nc = (uint64_t)acdsp_cic_state_size(h->cic), nb = (uint64_t)ddc_stage_b_state_size(h);
+  const char *pay = (const char *)buf + sizeof s;
+  if (!h->pd) {
+    if ((rc = acdsp_cic_state_set(h->cic, pay, nc))) { return rc; }
+    return acdsp_fir_state_set(h->fir, pay + nc, nb);
+  }
+  // Polydec cascade.  Rows for every word that can wait (DF - 1 of them) first, while nothing is changed yet; then the handle's own state is
+  // kept, so that a blob whose outer header fits and whose inner stage blob is refused leaves the handle as it was
+  if ((rc = ddc_mid_reserve(h, ddc_queue_cap(h->df), nullptr))) { return rc; }
+  std::vector<unsigned char> keep((size_t)(sizeof s + state_payload(mine)));
+  if ((rc = acdsp_ddc_state_get(h, keep.data(), keep.size()))) { return rc; }
+  if ((rc = ddc_polydec_state_apply(h, s.t_total, pay, nc, nb))) {
+    const std::string why = acdsp_last_error();
+    (void)ddc_polydec_state_apply(h, mine.t_total, (const char *)keep.data() + sizeof s, nc, nb);
+    return fail(rc, "%s", why.c_str());
+  }
+  return ACDSP_OK;
 }
 
 }  // extern "C"

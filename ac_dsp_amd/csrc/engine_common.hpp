@@ -371,13 +371,14 @@ struct StateHdr {
   uint32_t version;         // 1
   uint32_t kind;            // 1: FIR input history, 2: FIR reg_trans partial sums, 3: CIC input history + input count,
                             // 4: fused DDC input history + input count, 5: two-kernel DDC (CIC blob + FIR blob follow),
-                            // 6: ac_poly_dec input history, 7: ac_poly_intr input history + input count + saved sums, 8: ac_intg_dump temp[]
+                            // 6: ac_poly_dec input history, 7: ac_poly_intr input history + input count + saved sums, 8: ac_intg_dump temp[],
+                            // 9: fused polydec DDC input history + input count, 10: two-kernel polydec DDC (CIC blob + ac_poly_dec blob + queued words)
   uint32_t n_channels;
   uint32_t elem_bytes;      // bytes per state word (IN container; reg_trans: 8, or 16 for an ACC_TYPE wider than 64 bits; temp[]: 8)
   uint64_t per_channel;     // state words per channel
-  int64_t t_total;          // CIC, poly_intr: inputs consumed so far (decimation / interpolation phase, "first sample" of the folded cores); else 0
+  int64_t t_total;          // (two-kernel polydec DDC: queued words per channel)  CIC, poly_intr: inputs consumed so far (decimation / interpolation phase, "first sample" of the folded cores); else 0
   uint32_t p0, p1, p2, p3;  // FIR: n_taps, ftype, class, 0;  CIC: R, M, N, interp;  poly_dec: NTAPS, DF;  poly_intr: NTAPS, IF, ftype, COEFFSZ;  intg_dump: NS, CHN
-  uint64_t reserved;        // two-kernel DDC: channel count;  intg_dump: bit 0 = pending (the stream stands behind a block that did not dump)
+  uint64_t reserved;        // two-kernel DDC: channel count;  polydec DDC: DF in the high half;  intg_dump: bit 0 = pending (the stream stands behind a block that did not dump)
 };
 static_assert(sizeof(StateHdr) == 64, "state header is 64 bytes");
 
@@ -574,6 +575,7 @@ using acdsp::eng::Staging;
 using acdsp::eng::DevBuf;
 using acdsp::eng::History;
 using acdsp::eng::PhasePlans;
+using acdsp::eng::LongScratch;
 
 struct acdsp_fir {
   acdsp_fir_desc_t d;
@@ -659,7 +661,28 @@ struct acdsp_cic {
   Staging st;
 };
 
+// ac_poly_dec handle (engine_poly.hip; stage B of the polydec cascade: engine_ddc.hip)
+struct acdsp_polydec {
+  acdsp_polydec_desc_t d;
+  int in_eb, out_eb, hl;
+  bool lossless = false, coeffs_set = false, gen_ok = false;
+  bool lossless_shape = false, sat_free = false;   // a saturating ACC_TYPE no partial sum of the current set can reach is a wrapping one (cf. acdsp_fir::sat_free)
+  History hist;
+  DevBuf d_coeffs, d_gfrag;
+  FirGenPlan gplan;
+  // long prototypes (polydec_long.hip): long_shape = the descriptor is long-eligible and the ring kernel has no plan for its shape (create);
+  // long_ok = the current set runs there.  scratch: the phase streams
+  bool long_shape = false, long_ok = false, in_flip = false;
+  PolyDecLongPlan lplan;
+  LongScratch scratch;
+  DevBuf d_lfrag, d_lcorr;
+  int last_path = ACDSP_PATH_GENERIC;
+  int32_t last_ring = 0;   // ring-shape id of the last run(), 0 when no ring row ran
+  Staging st;
+};
+
 // DDC cascade handle (engine_ddc.hip; the state blobs of engine.hip read it)
+constexpr int kDdcMaxFusedDf = 2;   // decimation of the fused polydec cascade's stage B (fir_gen_cascade_dec.hip)
 struct acdsp_ddc {
   acdsp_cic_t cic = nullptr;     // stage A: parameter checks, INT_TYPE, FIR-identity taps; runs the stage in two-kernel mode
   acdsp_fir_t fir = nullptr;     // stage B: coefficient checks; runs the stage in two-kernel mode
@@ -683,6 +706,15 @@ struct acdsp_ddc {
   bool captured = false;         // a call of this handle has been recorded into a graph, which holds d_mid's address: growing the buffer
   std::vector<DevBuf> retired;   // later (eager) keeps the old one here instead of freeing it
   Timer tm;
+  // polydec cascade (acdsp_ddc_create_polydec): stage B is the decimating ac_poly_dec `pd` and `fir` stays null.  df = its DF (0: FIR cascade).
+  // A call consumes whole groups of DF intermediate words; the q < DF words behind the last whole group wait for the next call.  Fused mode
+  // recomputes them from the input history (q = ceil(t_total / R) % DF); two-kernel mode keeps them at the front of d_mid (n_q of them).
+  acdsp_polydec_t pd = nullptr;
+  acdsp_polydec_desc_t pd_desc;
+  int df = 0;
+  int64_t n_q = 0;
+  FirGenPlan planBq[kDdcMaxFusedDf];   // fused: the prototype's plan at window phase first = DF - 1 - q; fragments in d_fragB, kGenFragWords apart
+  std::vector<int64_t> h_pd_coeffs;     // last [NTAPS*DF] set (for clone)
 };
 
 namespace acdsp {
@@ -692,6 +724,11 @@ inline int64_t *fir_rt_cur(const acdsp_fir *h) { return h->d_rt[h->rt_hybrid ? h
 // refusals of acdsp_cic_run / acdsp_fir_run while the stream is capturing (ACDSP_ESTATE with the message set), else ACDSP_OK: no side effects
 int cic_capture_check(const acdsp_cic *h, const void *d_in, int64_t in_stride, int64_t n_in);
 int fir_capture_check(const acdsp_fir *h, const void *d_in, int64_t in_stride, int64_t n);
+// two-kernel DDC: intermediate rows of at least `cap` words, the queued words of a polydec cascade kept (engine_ddc.hip; the state blobs load into them)
+int ddc_mid_reserve(acdsp_ddc *h, int64_t cap, hipStream_t s);
+// ... and the capacity that holds every word that can wait between two calls of a polydec cascade (DF - 1), as run() would round it: what a
+// clone and a loaded blob reserve before they copy the queue in
+inline int64_t ddc_queue_cap(int df) { return ((int64_t)df + 15) / 16 * 16 + 16; }
 // FIR helpers other families use (engine_fir.hip)
 std::vector<int64_t> effective_coeffs(const int64_t *c, int N, int ftype);
 int internal_ftype(int kind, int ftype);

@@ -23,24 +23,7 @@ static int poly_long_geometry(H *h, int64_t *slab, int32_t *group_channels, uint
 // ---------------------------------------------------------------------------------------------
 // polyphase decimator
 // ---------------------------------------------------------------------------------------------
-struct acdsp_polydec {
-  acdsp_polydec_desc_t d;
-  int in_eb, out_eb, hl;
-  bool lossless = false, coeffs_set = false, gen_ok = false;
-  bool lossless_shape = false, sat_free = false;   // a saturating ACC_TYPE no partial sum of the current set can reach is a wrapping one (cf. acdsp_fir::sat_free)
-  History hist;
-  DevBuf d_coeffs, d_gfrag;
-  FirGenPlan gplan;
-  // long prototypes (polydec_long.hip): long_shape = the descriptor is long-eligible and the ring kernel has no plan for its shape (create);
-  // long_ok = the current set runs there.  scratch: the phase streams
-  bool long_shape = false, long_ok = false, in_flip = false;
-  PolyDecLongPlan lplan;
-  LongScratch scratch;
-  DevBuf d_lfrag, d_lcorr;
-  int last_path = ACDSP_PATH_GENERIC;
-  int32_t last_ring = 0;   // ring-shape id of the last run(), 0 when no ring row ran
-  Staging st;
-};
+// (struct acdsp_polydec: engine_common.hpp -- the polydec cascade of engine_ddc.hip reads it)
 
 namespace {
 

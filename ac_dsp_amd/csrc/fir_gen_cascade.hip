@@ -12,8 +12,8 @@ namespace acdsp {
 // The compiled shapes and conversions of the cascade: plans, plane counts, slot count, conversion constants and re-bias corrections of both
 // stages.  plb == nullptr: stage A and the formats only (what a handle knows before its coefficients).  Two families on the same stage-A plan
 // class (R, K blocks, digit planes): int16 rows -- two sample planes, an INT_TYPE of 33 .. 40 bits on five planes -- and 1-byte rows -- one
-// sample plane, 25 .. 32 bits on four planes.
-static bool cascade_args(const FirParams &pa, const FirGenPlan &pla, int w_int, const FirParams &pb, const FirGenPlan *plb, GenArgs &a, GenArgs &b) {
+// sample plane, 25 .. 32 bits on four planes.  (fir_gen_cascade_dec.hip asks with plb == nullptr and adds its own, decimating, stage B.)
+bool cascade_args(const FirParams &pa, const FirGenPlan &pla, int w_int, const FirParams &pb, const FirGenPlan *plb, GenArgs &a, GenArgs &b) {
   memset(&a, 0, sizeof a); memset(&b, 0, sizeof b);
   const bool bytes = pa.in_eb == 1;          // one plane whatever the sign: unsigned bytes are re-biased on the way into LDS
   a.pl = pla;

@@ -1152,6 +1152,10 @@ int gen_slot_map(GenArgs &a, int R, int n);
 bool gen_conv_params(const FirParams &p, int out_mode, int w_int, GenArgs *a, int src_bits = 0);
 int64_t gen_rebias_corr(int px, int64_t sum_h);
 
+// fir_gen_cascade.hip: the arguments of both cascade stages, false for shapes and formats outside the compiled families (plb == nullptr: stage A
+// and the formats only); fir_gen_cascade_dec.hip builds on it
+bool cascade_args(const FirParams &pa, const FirGenPlan &pla, int w_int, const FirParams &pb, const FirGenPlan *plb, GenArgs &a, GenArgs &b);
+
 // fir_gen_cascade_s8.hip: starts cascade_kernel<int8_t, 1, 3, 6, 5, 4, 2, 3, guard, limb, part> for launch_cascade (the byte-row family)
 hipError_t launch_cascade_s8(bool guard, bool limb, int part, dim3 grid, size_t lds_bytes, hipStream_t s, const FirParams &pa, const FirParams &pb,
                              const v4i *fa, const v4i *fb, const GenArgs &a, const GenArgs &b);

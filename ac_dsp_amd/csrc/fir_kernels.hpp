@@ -203,6 +203,13 @@ hipError_t launch_cascade(const FirParams &pa, const FirGenPlan &pla, const uint
 // does launch_cascade have a compiled shape and a branch-free conversion for these formats and plans (the per-call fields of pa / pb are not
 // read)?  plb == nullptr: stage A and the formats only -- what a handle knows before its coefficients
 bool cascade_shape_ok(const FirParams &pa, const FirGenPlan &pla, int w_int, const FirParams &pb, const FirGenPlan *plb);
+// The same cascade with a decimating stage B (fir_gen_cascade_dec.hip; acdsp_ddc_create_polydec): plb = fir_gen_plan of the prototype
+// h[tp DF + df] = c[tp + NTAPS df] at decimation df and window phase first_b = df - 1 - q, q < df the words of the stream that wait in front
+// of the call; n_out = the final outputs of the call.  int16 rows, df = 2, NTAPS*DF <= 128.
+bool cascade_dec_plan_ok(const FirGenPlan &plb, int df, int first_b);
+bool cascade_dec_shape_ok(const FirParams &pa, const FirGenPlan &pla, int w_int, const FirParams &pb, const FirGenPlan *plb, int df, int first_b);
+hipError_t launch_cascade_dec(const FirParams &pa, const FirGenPlan &pla, const uint32_t *d_fragA, int w_int, int64_t first, const FirParams &pb,
+                              const FirGenPlan &plb, const uint32_t *d_fragB, int df, int first_b, int64_t n_out, hipStream_t s);
 
 // Interpolating polyphase FIR on the matrix cores (fir_up.hip): z[n L + j] = sum_k E_j[k] x[n - k] mod 2^64.
 struct FirUpPlan {
@@ -285,6 +292,8 @@ int set_error(int code, const char *msg);
 // ddc_flags, a byte flag on a stage descriptor, ACDSP_DDC_IN_BYTES on samples wider than 8 bits.  acdsp_node_ddc_create_ex asks in front of its
 // threads and streams.
 int ddc_flag_refusals(const acdsp_cic_desc_t &cic, const acdsp_fir_desc_t &fir, int32_t ddc_flags);
+// ... and of acdsp_ddc_create_polydec, whose stage B is an ac_poly_dec descriptor
+int ddc_flag_refusals(const acdsp_cic_desc_t &cic, const acdsp_polydec_desc_t &pd, int32_t ddc_flags);
 
 // Measurement kernels of acdsp_diag_* (diag.hip): a plain 16-byte-per-thread copy, and the stream + issued-MFMA envelope of a FIR row.
 hipError_t launch_diag_copy(const void *src, void *dst, int64_t bytes, hipStream_t s);

@@ -382,6 +382,30 @@ int32_t acdsp_node_ddc_create_ex(const acdsp_cic_desc_t *cic, const acdsp_fir_de
   return ACDSP_OK;
 }
 
+// ... and the polydec cascade (acdsp_ddc_create_polydec): the same node kind, so set_coeffs / out_count / run above serve it
+int32_t acdsp_node_ddc_create_polydec(const acdsp_cic_desc_t *cic, const acdsp_polydec_desc_t *pd, int32_t ddc_flags, int32_t n_devices, const int32_t *devices,
+                                      acdsp_node_t *out) {
+  if (!cic || !pd) { return set_error(ACDSP_EINVAL, "node_ddc_create_polydec: null descriptor"); }
+  int rc = ddc_flag_refusals(*cic, *pd, ddc_flags);   // (in front of the threads and streams: before any device use)
+  if (rc) { return rc; }
+  acdsp_node *h = nullptr;
+  if ((rc = make_node(kNodeDdc, cic->n_channels, n_devices, devices, &h))) { return rc; }
+  h->n_taps = pd->n_taps * pd->df;
+  struct Stages { acdsp_cic_desc_t cic; acdsp_polydec_desc_t pd; int32_t ddc_flags; int32_t n_channels, device; };
+  const Stages both = {*cic, *pd, ddc_flags, 0, 0};
+  rc = create_shards<Stages, acdsp_ddc_t>(h, both, &Stages::n_channels, [](const Stages *st, acdsp_ddc_t *e) {
+    acdsp_cic_desc_t c = st->cic;
+    acdsp_polydec_desc_t p = st->pd;
+    c.n_channels = p.n_channels = st->n_channels; c.device = p.device = st->device;
+    return acdsp_ddc_create_polydec(&c, &p, st->ddc_flags, e);
+  });
+  if (rc) { return rc; }
+  h->in_eb = acdsp_ddc_in_elem_bytes((acdsp_ddc_t)h->shards[0].handle);
+  h->out_eb = acdsp_elem_bytes(pd->out.W);
+  *out = h;
+  return ACDSP_OK;
+}
+
 int32_t acdsp_node_ddc_set_coeffs(acdsp_node_t h, const int64_t *coeffs) {
   int rc = check_node(h, kNodeDdc, "not a DDC node handle");
   if (rc) { return rc; }

@@ -497,6 +497,31 @@ class Ddc(_Stateful):
         return a.value, m.value
 
 
+class DdcPolyDec(Ddc):
+    """n_channels independent cascades ac_cic_dec_full(R, M, N) -> ac_poly_dec(NTAPS, DF) on the decimator's lossless INT_TYPE words
+    (acdsp_ddc_create_polydec; every other call is Ddc's): one fused kernel for the config-5 class at DF = 2 with NTAPS*DF <= 128, the two
+    stage kernels otherwise.  A call emits the whole groups of DF words; the rest waits for the next call."""
+
+    def __init__(self, R, M, N, fin, n_taps, df, fcoeff, facc, fout, n_channels=1, device=0, in_bytes=False, flags=0):
+        """in_bytes: as for Ddc (ACDSP_DDC_IN_BYTES); `flags` lands on both stage descriptors"""
+        self.fin, self.fout, self.n_channels, self.n_taps, self.df = fin, fout, n_channels, n_taps, df
+        self.in_bytes = bool(in_bytes)
+        probe = CicDesc(0, R, M, N, n_channels, fin, fin, device, flags)
+        it = Fmt()
+        check(lib.acdsp_cic_int_type(C.byref(probe), C.byref(it)))
+        self.int_type = Fmt(it.W, it.I, True)
+        cd = CicDesc(0, R, M, N, n_channels, fin, self.int_type, device, flags)
+        pd = PolyDecDesc(n_taps, df, n_channels, self.int_type, fcoeff, facc, fout, device, flags)
+        self._h = C.c_void_p()
+        check(lib.acdsp_ddc_create_polydec(C.byref(cd), C.byref(pd), _lib.DDC_IN_BYTES if in_bytes else 0, C.byref(self._h)))
+
+    def set_coeffs(self, coeffs):
+        """[NTAPS*DF] STR_COEFF raw words, ordered as PolyDec.set_coeffs takes them"""
+        c = np.ascontiguousarray(coeffs, dtype=np.int64)
+        assert c.shape == (self.n_taps * self.df,)
+        check(lib.acdsp_ddc_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
+
+
 POLY_FTYPES = {"FOLD_EVEN": 0, "FOLD_ODD": 1, "FOLD_ANTI": 2}   # the enum of ac_poly_intr.h:71
 
 
@@ -843,6 +868,30 @@ class NodeDdc(_Node):
         n_out = C.c_int64()
         check(lib.acdsp_node_ddc_run(self._h, pin, sin, n_in, pout, sout, C.byref(n_out)))
         return [o[:, :n_out.value] for o in outs]
+
+
+class NodeDdcPolyDec(NodeDdc):
+    """A DdcPolyDec bank sharded over `devices` (acdsp_node_ddc_create_polydec; set_coeffs / out_count / run are acdsp_node_ddc_*)."""
+
+    def __init__(self, R, M, N, fin, n_taps, df, fcoeff, facc, fout, n_channels, devices, in_bytes=False):
+        self.fin, self.fout, self.n_channels, self.n_taps, self.df = fin, fout, n_channels, n_taps, df
+        self.in_bytes = bool(in_bytes)
+        probe = CicDesc(0, R, M, N, n_channels, fin, fin, 0, 0)
+        it = Fmt()
+        check(lib.acdsp_cic_int_type(C.byref(probe), C.byref(it)))
+        self.int_type = Fmt(it.W, it.I, True)
+        cd = CicDesc(0, R, M, N, n_channels, fin, self.int_type, 0, 0)
+        pd = PolyDecDesc(n_taps, df, n_channels, self.int_type, fcoeff, facc, fout, 0, 0)
+        self._h = C.c_void_p()
+        check(lib.acdsp_node_ddc_create_polydec(C.byref(cd), C.byref(pd), _lib.DDC_IN_BYTES if in_bytes else 0, len(devices), self._dev_array(devices),
+                                                C.byref(self._h)))
+        self._finish_create(devices)
+
+    def set_coeffs(self, coeffs):
+        """[NTAPS*DF] STR_COEFF raw words, ordered as PolyDec.set_coeffs takes them; replicated to every shard"""
+        c = np.ascontiguousarray(coeffs, dtype=np.int64)
+        assert c.shape == (self.n_taps * self.df,)
+        check(lib.acdsp_node_ddc_set_coeffs(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))))
 
 
 class NodePolyDec(_Node):

@@ -485,6 +485,48 @@ private:
   int n_taps_, ddc_flags_;
 };
 
+// DDC cascade with a decimating second stage: n_channels x { ac_cic_dec_full<IN, INT, R, M, N> -> ac_poly_dec<INT, COEFF, ., ACC, OUT, NTAPS, DF> },
+// INT = the decimator's INT_TYPE taken from the engine (acdsp_cic_int_type).  One fused kernel for the config-5 class at DF = 2 with
+// NTAPS*DF <= 128, the two stage kernels otherwise; a call emits the whole groups of DF words and the rest waits for the next call.
+// Copyable through acdsp_ddc_clone like ddc_engine: a copy carries coefficients, kernel mode, both stages' stream and the waiting words.
+template <class IN_TYPE, class COEFF_TYPE, class ACC_TYPE, class OUT_TYPE>
+class ddc_polydec_engine {
+public:
+  ddc_polydec_engine(unsigned R, unsigned M, unsigned N, int n_taps, int df, int n_channels = 1, int device = -1, int ddc_flags = 0)
+      : n_coeffs_(n_taps * df), ddc_flags_(ddc_flags) {
+    acdsp_cic_desc_t c;
+    c.interp = 0; c.R = (int32_t)R; c.M = (int32_t)M; c.N = (int32_t)N; c.n_channels = n_channels;
+    c.in = fmt_of<IN_TYPE>(); c.out = c.in; c.device = device < 0 ? default_device() : device; c.flags = 0;
+    check(acdsp_cic_int_type(&c, &int_type_), "acdsp_cic_int_type");
+    c.out = int_type_;
+    acdsp_polydec_desc_t p;
+    p.n_taps = n_taps; p.df = df; p.n_channels = n_channels;
+    p.in = int_type_; p.coeff = fmt_of<COEFF_TYPE>(); p.acc = fmt_of<ACC_TYPE>(); p.out = fmt_of<OUT_TYPE>();
+    p.device = c.device; p.flags = 0;
+    check(acdsp_ddc_create_polydec(&c, &p, ddc_flags, h_.slot()), "acdsp_ddc_create_polydec");
+  }
+  int in_bytes() const { return (ddc_flags_ & ACDSP_DDC_IN_BYTES) ? 1 : acdsp_elem_bytes(IN_TYPE::width); }
+  acdsp_fmt_t int_type() const { return int_type_; }
+  // [NTAPS*DF] STR_COEFF words in the order of ac_poly_dec's coefficient struct
+  void set_coeffs(const COEFF_TYPE *c) {
+    std::vector<int64_t> r((size_t)n_coeffs_);
+    for (size_t i = 0; i < r.size(); i++) { r[i] = raw_of(c[i]); }
+    check(acdsp_ddc_set_coeffs(h_.get(), r.data()), "acdsp_ddc_set_coeffs");
+  }
+  int64_t out_count(int64_t n_in) { return acdsp_ddc_out_count(h_.get(), n_in); }
+  bool fused() { return acdsp_ddc_path(h_.get()) == 1; }
+  void run_device(const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride, int64_t *n_out, void *stream = 0) {
+    check(acdsp_ddc_run(h_.get(), d_in, in_stride, n_in, d_out, out_stride, n_out, stream), "acdsp_ddc_run");
+  }
+  void reset() { check(acdsp_ddc_reset(h_.get()), "acdsp_ddc_reset"); }
+  acdsp_ddc_t handle() { return h_.get(); }
+
+private:
+  cloned_handle<acdsp_ddc_t, acdsp_ddc_clone, acdsp_ddc_destroy> h_;
+  acdsp_fmt_t int_type_;
+  int n_coeffs_, ddc_flags_;
+};
+
 // ---------------------------------------------------------------------------------------------
 // Batched ac_poly_dec / ac_poly_intr / ac_intg_dump / ac_mv_avg: rows = channels (objects) behind one engine handle, in the shape of
 // cic_engine.  The descriptor comes from the template types; run() takes raw device rows (containers of in_bytes() / out_bytes(), strides in

@@ -368,9 +368,28 @@ int32_t acdsp_polydec_long_geometry(acdsp_polydec_t h, int64_t *slab_outputs, in
  * everything acdsp_ddc_create checks.  Fused rows obey the 16-byte rule in units of the 1-byte container (ACDSP_EUNSUPPORTED otherwise). */
 int32_t acdsp_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, acdsp_ddc_t *out);
 int32_t acdsp_ddc_create_ex(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t ddc_flags, acdsp_ddc_t *out);
+/* The cascade with a DECIMATING second stage, `cic.run(in, mid); polydec.run(mid, out, coeffs);`: ac_cic_dec_full -> ac_poly_dec on the INT_TYPE
+ * words (cic->out and pd->in must both be the INT_TYPE).  The handle is an acdsp_ddc_t and every call of this section and of the state / clone
+ * sections serves it; acdsp_ddc_set_coeffs takes the [NTAPS*DF] array in the order of acdsp_polydec_set_coeffs.  Results are bit-identical to
+ * acdsp_cic_run followed by acdsp_polydec_run on whole groups of DF words: the fewer-than-DF words behind the last whole group of a call wait
+ * for the next one, as they would in the reference's ac_channel (ac_poly_dec.h:110), so output m of the stream leaves with word m DF + DF - 1
+ * and a call with fewer than DF words returns *n_out = 0 with ACDSP_OK.  Refusals, in this order and before any device use: null arguments;
+ * unknown ddc_flags bits: ACDSP_EINVAL; a byte flag on either stage descriptor: ACDSP_EUNSUPPORTED; ACDSP_DDC_IN_BYTES with cic->in.W > 8:
+ * ACDSP_EINVAL; cic->interp: ACDSP_EINVAL; channel count / device mismatch: ACDSP_EINVAL; cic->out or pd->in not the INT_TYPE: ACDSP_EINVAL;
+ * then whatever acdsp_cic_create and acdsp_polydec_create refuse.
+ * Fused (acdsp_ddc_path = 1): int16 rows, the config-5 decimator class (R 16 N 5 and its neighbours, INT_TYPE of 33 .. 40 bits), DF = 2,
+ * NTAPS*DF <= 128, coefficients in two digit planes, an exact-sum ACC_TYPE, int32 output containers, 16-byte aligned rows.  A step of 256
+ * outputs runs DF stage-A sub-steps into a ring of 32 DF slots and one decimating stage B on it; the words never reach HBM.  Everything else
+ * (byte rows, other DF, longer prototypes, ACDSP_NO_FUSE, ACDSP_FLAG_FORCE_GENERIC on a stage, a coefficient set outside the plan) runs the
+ * two stage kernels through the handle's intermediate rows, the waiting words at their front.  Under graph capture a call whose word count
+ * is not a multiple of DF (fused: n_in % (R DF) != 0) is ACDSP_ESTATE: a replay would repeat the captured queue length.
+ * Measured on 4096 x 2^20 int16 samples (R 16 N 5, NTAPS 64 x DF 2; profiles/ddc_polydec_shapes.txt): the fused composite takes 0.784 of the time of a
+ * Cic + PolyDec pair and 0.957 of the full-rate fused cascade with the same 128 taps; 512 streams: 0.873 and 0.947; two runs of one arm differ by
+ * 0.1 - 0.7 %.  DESIGN.md 4.25. */
+int32_t acdsp_ddc_create_polydec(const acdsp_cic_desc_t *cic, const acdsp_polydec_desc_t *pd, int32_t ddc_flags, acdsp_ddc_t *out);
 int32_t acdsp_ddc_in_elem_bytes(acdsp_ddc_t h);                         /* 1 under ACDSP_DDC_IN_BYTES, else acdsp_elem_bytes(cic->in.W); -1 on a null handle */
 int32_t acdsp_ddc_destroy(acdsp_ddc_t h);
-int32_t acdsp_ddc_set_coeffs(acdsp_ddc_t h, const int64_t *coeffs);   /* FIR coefficients, raw COEFF_TYPE words [n_taps] */
+int32_t acdsp_ddc_set_coeffs(acdsp_ddc_t h, const int64_t *coeffs);   /* FIR coefficients, raw COEFF_TYPE words [n_taps]; polydec cascade: [NTAPS*DF], as acdsp_polydec_set_coeffs */
 int64_t acdsp_ddc_out_count(acdsp_ddc_t h, int64_t n_in);
 int32_t acdsp_ddc_run(acdsp_ddc_t h, const void *d_in, int64_t in_stride, int64_t n_in, void *d_out, int64_t out_stride,
                       int64_t *n_out, void *stream);
@@ -517,7 +536,11 @@ int32_t acdsp_cic_state_get(acdsp_cic_t h, void *h_buf, uint64_t cap_bytes);
 int32_t acdsp_cic_state_set(acdsp_cic_t h, const void *h_buf, uint64_t bytes);
 /* cascade (acdsp_ddc_*): the input history and input count of the fused kernel (its FIR window is recomputed from them), or
  * the two stage blobs behind one header when the handle runs the stages as two kernels.  Under ACDSP_DDC_IN_BYTES the history words are
- * 1-byte containers: such a blob moves between byte cascades of the same descriptors and is refused by every other handle (and theirs by it) */
+ * 1-byte containers: such a blob moves between byte cascades of the same descriptors and is refused by every other handle (and theirs by it).
+ * Polydec cascade (acdsp_ddc_create_polydec): the same in fused mode -- the waiting words are recomputed from history and count --, and the two
+ * stage blobs plus the waiting INT_TYPE words in two-kernel mode; the header carries NTAPS and DF, and a FIR cascade and a polydec cascade refuse
+ * each other's blobs (ACDSP_EINVAL).  A refused blob leaves a polydec cascade as it was, also when the outer header fits and a stage blob inside it
+ * is refused: the handle's own state is put back. */
 int64_t acdsp_ddc_state_size(acdsp_ddc_t h);
 int32_t acdsp_ddc_state_get(acdsp_ddc_t h, void *h_buf, uint64_t cap_bytes);
 int32_t acdsp_ddc_state_set(acdsp_ddc_t h, const void *h_buf, uint64_t bytes);
@@ -564,6 +587,9 @@ int32_t acdsp_node_ddc_create(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_
 /* ... with the ddc_flags of acdsp_ddc_create_ex (acdsp_node_ddc_create = flags 0): every shard is created from these descriptors and flags */
 int32_t acdsp_node_ddc_create_ex(const acdsp_cic_desc_t *cic, const acdsp_fir_desc_t *fir, int32_t ddc_flags, int32_t n_devices,
                                  const int32_t *devices, acdsp_node_t *out);
+/* ... and the polydec cascade of acdsp_ddc_create_polydec: the other acdsp_node_ddc_* calls serve the handle */
+int32_t acdsp_node_ddc_create_polydec(const acdsp_cic_desc_t *cic, const acdsp_polydec_desc_t *pd, int32_t ddc_flags, int32_t n_devices,
+                                      const int32_t *devices, acdsp_node_t *out);
 int32_t acdsp_node_ddc_set_coeffs(acdsp_node_t h, const int64_t *coeffs);
 int64_t acdsp_node_ddc_out_count(acdsp_node_t h, int64_t n_in);
 int32_t acdsp_node_ddc_run(acdsp_node_t h, const void *const *d_in, int64_t in_stride, int64_t n_in, void *const *d_out, int64_t out_stride,
