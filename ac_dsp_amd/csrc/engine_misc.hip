@@ -1,5 +1,6 @@
 // engine_misc.hip -- acdsp_intgdump_* / acdsp_mvavg_*: ac_intg_dump and ac_mv_avg behind the C ABI
 #include "engine_common.hpp"
+#include "mv_avg_plan.hpp"
 
 using namespace acdsp;
 using namespace acdsp::eng;
@@ -291,9 +292,7 @@ struct acdsp_mvavg {
   DevBuf d_coeffs;
   std::vector<int64_t> h_coeffs;
   DevBuf d_frag;                // matrix-core form of the streaming kernel: fragments of the coefficient set (mv_avg_build_frags)
-  int frag_nb = 0;
-  int64_t frag_csum = 0;
-  int frag_gran = 8, frag_hi = 0;   // halo granularity of the fragments (16 under ACDSP_FLAG_IN_BYTES: mv_avg_s8_kernel's geometry); a high digit exists
+  MvSetPlan plan;               // what the descriptor and the coefficient set decide (mv_avg_plan.hpp); rebuilt by every set_coeffs
   int last_path = 0;
   Staging st;
 };
@@ -324,7 +323,6 @@ int32_t acdsp_mvavg_create(const acdsp_mvavg_desc_t *desc, acdsp_mvavg_t *out) {
   std::unique_ptr<acdsp_mvavg> h(new acdsp_mvavg());   // (check_device has made the device current: a failure below frees there)
   h->d = *desc;
   h->in_eb = in_eb; h->out_eb = out_eb;
-  h->frag_gran = in_eb == 1 ? 16 : 8;
   if ((rc = h->d_coeffs.alloc((size_t)desc->taps * sizeof(int64_t))) || (rc = h->d_frag.alloc((size_t)kMvAvgFragWords * sizeof(uint32_t)))) { return rc; }
   *out = h.release();
   return ACDSP_OK;
@@ -361,11 +359,9 @@ int32_t acdsp_mvavg_set_coeffs(acdsp_mvavg_t h, const int64_t *coeffs) {
   HIP_TRY(hipDeviceSynchronize());
   if ((rc = h->d_coeffs.upload(coeffs, (size_t)h->d.taps * sizeof(int64_t)))) { return rc; }
   h->h_coeffs.assign(coeffs, coeffs + h->d.taps);
-  {
-    std::vector<uint32_t> fr((size_t)kMvAvgFragWords, 0u);
-    h->frag_nb = mv_avg_build_frags(coeffs, h->d.taps, h->d.win_mode, h->frag_gran, fr.data(), &h->frag_csum, &h->frag_hi);
-    if (h->frag_nb > 0 && (rc = h->d_frag.upload(fr.data(), fr.size() * sizeof(uint32_t)))) { return rc; }
-  }
+  std::vector<uint32_t> fr((size_t)kMvAvgFragWords, 0u);
+  h->plan = mv_avg_plan_set(h->d, h->in_eb, h->out_eb, coeffs, h->d_coeffs.get<int64_t>(), h->d_frag.get<uint32_t>(), fr.data());
+  if (h->plan.p.frag_nb > 0 && (rc = h->d_frag.upload(fr.data(), fr.size() * sizeof(uint32_t)))) { return rc; }
   h->coeffs_set = true;
   return ACDSP_OK;
 }
@@ -381,10 +377,7 @@ int32_t acdsp_mvavg_frags_host(const int64_t *coeffs, int32_t taps, int32_t win_
   static_assert(ACDSP_MVAVG_FRAG_WORDS == kMvAvgFragWords, "the header's fragment size");
   memset(out, 0, (size_t)kMvAvgFragWords * sizeof(uint32_t));
   *csum = 0; *hi_any = 0;
-  int hi = 0;
-  const int nb = mv_avg_build_frags(coeffs, taps, win_mode, in_bytes ? 16 : 8, out, csum, &hi);
-  *hi_any = hi;
-  return nb;
+  return mv_avg_build_frags(coeffs, taps, win_mode, in_bytes ? 16 : 8, out, csum, hi_any);
 }
 
 int64_t acdsp_mvavg_out_per_frame(acdsp_mvavg_t h, int64_t n_sample) {
@@ -405,46 +398,13 @@ int32_t acdsp_mvavg_run(acdsp_mvavg_t h, const void *d_in, int64_t in_stride, in
   if (n_frames == 0) { return ACDSP_OK; }
   if (!d_in || in_stride < n_sample * n_frames) { return fail(ACDSP_EINVAL, "mv_avg run: bad input arguments"); }
   if (no > 0 && (!d_out || out_stride < no)) { return fail(ACDSP_EINVAL, "mv_avg run: output buffer too small for %lld outputs", (long long)no); }
-  const acdsp_mvavg_desc_t &d = h->d;
-  int rc = check_device(d.device);
+  int rc = check_device(h->d.device);
   if (rc) { return rc; }
-  MvAvgParams p;
-  memset(&p, 0, sizeof p);
-  p.taps = d.taps; p.win_mode = d.win_mode; p.n_obj = d.n_objects;
-  p.in = make_dfmt(d.in); p.cf = make_dfmt(d.coeff); p.acc = make_dfmt(d.acc); p.out = make_dfmt(d.out);
-  p.in_eb = h->in_eb; p.out_eb = h->out_eb;
-  p.force_generic = (d.flags & ACDSP_FLAG_FORCE_GENERIC) != 0;
-  // A saturating ACC_TYPE that cannot saturate is a wrapping one (cf. acdsp_fir::sat_free): the cast of a sample is exact, and every partial sum
-  // is bounded by sum|c| max|x| 2^d / 2^sh plus one LSB per tap, inside the type's symmetric range.  The kernels then see AC_WRAP.
-  if (d.acc.O != ACDSP_WRAP && d.acc.S && !h->h_coeffs.empty() && !p.force_generic && (d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && d.acc.W <= 64) {
-    const int dc = p.acc.F - p.in.F, sh = p.cf.F, i_in = d.in.I + (d.in.S ? 0 : 1);
-    if (!knob_no_sat_free() && dc >= 0 && dc < 40 && sh >= 0 && sh < 64 && d.acc.I >= i_in) {
-      if (sat_free_bound(sum_abs(h->h_coeffs.data(), h->h_coeffs.size()), d.in, d.acc, dc, sh, h->h_coeffs.size() + 1)) { p.acc.O = ACDSP_WRAP; }
-    }
-  }
-  // order-free class: products (ACC_TYPE) w[j] * coeffs[j] inside 2^62.  The cast sample has at most min(W_acc, W_in + max(F_acc - F_in, 0))
-  // bits and the coefficients as many as the set on the handle needs (round 5: the bound by W_acc + W_coeff sent <32,16> samples into a
-  // <56,30> accumulator to the 128-bit per-tap kernel)
-  int cbits = d.coeff.W;
-  if (!h->h_coeffs.empty()) {
-    cbits = 1;
-    for (int64_t c : h->h_coeffs) {
-      const uint64_t m = (uint64_t)(c < 0 ? ~c : c);
-      int b = 1;
-      while (b < 64 && (m >> (b - 1)) != 0) { b++; }
-      if (b > cbits) { cbits = b; }
-    }
-    if (!d.coeff.S) { cbits++; }
-  }
-  const int dcast = p.acc.F - p.in.F, xbits_in = d.in.W + (d.in.S ? 0 : 1) + (dcast > 0 ? dcast : 0);
-  const int xbits = xbits_in < d.acc.W + (d.acc.S ? 0 : 1) ? xbits_in : d.acc.W + (d.acc.S ? 0 : 1);
-  p.fast = !p.force_generic && p.acc.O == ACDSP_WRAP && (d.acc.Q == ACDSP_TRN || d.acc.Q == ACDSP_RND) && p.cf.F >= 0 &&
-           p.cf.F < 62 && xbits + cbits <= 62;
-  p.n_sample = n_sample; p.n_frames = n_frames; p.out_per_frame = opf; p.in_stride = in_stride; p.out_stride = out_stride;
-  p.x = d_in; p.y = d_out; p.coeffs = h->d_coeffs.get<int64_t>(); p.h_coeffs = h->h_coeffs.data();
-  p.frag = h->frag_nb > 0 ? h->d_frag.get<uint32_t>() : nullptr; p.frag_nb = h->frag_nb; p.frag_csum = h->frag_csum;
-  p.frag_gran = h->frag_gran; p.frag_hi = h->frag_hi;
-  hipError_t e = launch_mv_avg(p, (hipStream_t)stream, &h->last_path);
+  MvAvgParams p = h->plan.p;   // the general kernels' argument: the set plan's fields and this call's rows
+  p.n_sample = n_sample; p.n_frames = n_frames; p.out_per_frame = opf; p.in_stride = in_stride; p.out_stride = out_stride; p.x = d_in; p.y = d_out;
+  const MvCall c = mv_avg_plan_call(h->plan, p);
+  if (c.path >= 0) { h->last_path = c.path; }
+  hipError_t e = launch_mv_avg(c, (hipStream_t)stream);
   if (e != hipSuccess) { return fail(ACDSP_EHIP, "mv_avg kernel launch failed: %s", hipGetErrorString(e)); }
   return ACDSP_OK;
 }

@@ -273,7 +273,7 @@ struct MvAvgParams {
   int64_t n_sample, n_frames, out_per_frame, in_stride, out_stride;
   const void *x; void *y;
   const int64_t *coeffs;      // [taps]
-  const int64_t *h_coeffs;    // host copy (the streaming kernel takes its coefficients as kernel arguments)
+  const int64_t *unused_;     // (held a host pointer once; the slot stays: the kernels' argument offsets depend on it)
   const uint32_t *frag;       // device: Toeplitz fragments of the matrix-core form (mv_avg_build_frags), frag_nb K blocks (0: none), frag_csum = sum of the coefficients
   int32_t frag_nb;
   int16_t frag_gran, frag_hi; // halo granularity the fragments were built for (8: 16-bit rows, 16: byte rows); some coefficient has a high digit
@@ -281,8 +281,7 @@ struct MvAvgParams {
   int64_t frag_csum;
 };
 static_assert(sizeof(MvAvgParams) % 8 == 0 && offsetof(MvAvgParams, frag_csum) == offsetof(MvAvgParams, frag_nb) + 8, "MvAvgParams: layout of the kernel argument");
-hipError_t launch_mv_avg(const MvAvgParams &p, hipStream_t s, int *path);   // *path: 0 exact order, 1 int64 sums, 2 streaming kernel, 3 32-bit samples, 4 streaming kernel on the matrix cores, 5 byte-plane streaming kernel
-bool mv_avg_try_s8(const MvAvgParams &p, hipStream_t s);                    // mv_avg_s8.hip: true = launched (in_eb == 1 and its class)
+// (the two plans that decide a call and launch_mv_avg: mv_avg_plan.hpp)
 constexpr int kMvAvgFragWords = 2 * 2 * 2 * 64 * 4;   // [m][b][plane][lane][4]
 int mv_avg_build_frags(const int64_t *c, int taps, int win_mode, int gran, uint32_t *out, int64_t *csum, int *hi_any);
 

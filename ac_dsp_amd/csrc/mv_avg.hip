@@ -12,16 +12,16 @@
 // Two arithmetic classes: per-tap requantisation in 128 bits (any Q / O), and, for AC_TRN / AC_RND + AC_WRAP accumulators
 // whose products fit 63 bits, the order-free form acc = sum_j ((xq_j * c_j + rnd) >> F_c) mod 2^W_acc in int64.
 // Streaming op: 2 + 2 bytes per sample at 16-bit containers; bound by HBM for short windows.
-#include <cstdlib>
+// Host side: launch_mv_avg (at the end) launches what mv_avg_plan.hip decided -- a set plan per coefficient set, a call plan per run (mv_avg_plan.hpp).
 #include <cstring>
 
-#include "fir_kernels.hpp"
+#include "mv_avg_plan.hpp"
 
 namespace acdsp {
 
 namespace {
 
-constexpr int kTile = 256;
+constexpr int kTile = kMvTile;
 
 __device__ inline i128 shl128_(i128 v, int s) { return (i128)((u128)v << s); }
 
@@ -92,31 +92,7 @@ __global__ void __launch_bounds__(kTile) mv_avg_kernel(MvAvgParams p) {
 // patched in from their source samples, every lane reads its 8 + TAPS - 1 window samples back with (unaligned) 16-byte
 // reads, computes 8 consecutive outputs -- coefficients sit in SGPRs -- converts them (32-bit shift / clamp when nothing
 // can wrap, else the 64-bit branch-free form) and stores 16 bytes per instruction.  The loads of the next tile are issued
-// before the arithmetic of the current one.  No workgroup barrier: waves never share data.
-struct MvStreamArgs {
-  int16_t c16[66];            // coefficients, zero padded (pairs (c[2q], c[2q+1]) are the v_dot2 operands of even outputs)
-  int16_t c16o[66];           // the same behind one zero: pairs (c[2q-1], c[2q]) for odd outputs, whose windows start in a high half
-  int32_t taps, h, hb, off, mode, nxg;
-  int32_t linear, ls, e, rnd_e;
-  int32_t pk16;               // 32-bit epilogue into a signed 16-bit AC_SAT output at aligned frames: saturating packs
-  int32_t cv32, s32, r32, lo32, hi32, ko32;   // 32-bit epilogue: q = (S + r32) >> s32, clamp, wrap (ko32 = 32 - W_out or 0)
-  int32_t ka, rs, ls2, ko;    // 64-bit epilogue (see IdConv in intg_dump.hip)
-  uint64_t am, om;
-  int64_t rnd, lo, hi;
-  int32_t out_eb, vec_ok, run_ok;   // vec_ok: every lane's eight outputs are an aligned 16 / 32 / 64 bytes; else run_ok: tiles leave through the image as aligned pieces
-  int64_t n_sample, n_frames, opf, in_stride, out_stride, tpf, n_tiles, tiles_per_wave;
-  const int16_t *x;
-  void *y;
-  int32_t xcd_map;   // XCD-affine block order (acdsp_dev.hpp: xcd_remap)
-  // packed short frames (round 5, PK instantiations): pk_n = samples per frame (64 / 128 / 256; 0 = off), pk_pitch = image samples per frame
-  // (n + 2 hb); the tile loads then start at the tile, not hb samples in front of it: every halo is a patch
-  int32_t pk_n, pk_pitch, pk_sh;
-  int32_t row_n, row_opf;   // ROW instantiations: samples / outputs per frame (the kernel's n_sample / opf are then the ROW's lengths, n_frames = 1); row_n 0: off
-  // matrix-core instantiations (MF = K blocks of 64 samples): Toeplitz fragments [m][b][plane][lane] x 16 bytes (mv_avg_build_frags), and
-  // 128 sum(c), what the re-biased low sample plane leaves out
-  const uint32_t *frag;
-  int32_t kbias;
-};
+// before the arithmetic of the current one.  No workgroup barrier: waves never share data.  (Argument: MvStreamArgs, mv_avg_plan.hpp.)
 
 typedef short v2s_t __attribute__((ext_vector_type(2)));
 typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
@@ -139,7 +115,7 @@ typedef int v4i_mv __attribute__((ext_vector_type(4)));
 // orders: row i of fragment set m is output 32 j' + 8 (i >> 2) + (i & 3) + 4 m.  A lane's accumulator rows are then outputs 8 v .. 8 v + 7 of
 // the tile, v = 4 (lane & 15) + (lane >> 4): eight consecutive outputs, the same epilogue and 16-byte stores as the v_dot2 form, a whole KB
 // per store instruction.  8 MF MFMAs per 512 outputs (4 plane products x 2 row orders), 2 MF 16-byte LDS reads per lane instead of NR.
-template <int NR, bool LINEAR, bool CV32, bool EDGE, bool PK = false, int MF = 0, bool RUN = false, int ROW = 0>   // ROW: tiles walk the ROW, frame edges fall inside them (a.row_n; 1: AC_CLIP / AC_MIRROR, 2: AC_WIN; see try_stream); RUN: output tiles that start off a 16-byte boundary leave as aligned runs (a.run_ok; as a run-time branch it cost the bench row 12 VGPRs and two waves per SIMD: -8 %); PK: packed short frames (MvStreamArgs::pk_*; as run-time branches they cost the bench row 1.4 %)
+template <int NR, bool LINEAR, bool CV32, bool EDGE, bool PK = false, int MF = 0, bool RUN = false, int ROW = 0>   // ROW: tiles walk the ROW, frame edges fall inside them (a.row_n; 1: AC_CLIP / AC_MIRROR, 2: AC_WIN; see plan_stream in mv_avg_plan.hip); RUN: output tiles that start off a 16-byte boundary leave as aligned runs (a.run_ok; as a run-time branch it cost the bench row 12 VGPRs and two waves per SIMD: -8 %); PK: packed short frames (MvStreamArgs::pk_*; as run-time branches they cost the bench row 1.4 %)
 __global__ void __launch_bounds__(256) mv_avg_stream_kernel(MvStreamArgs a) {
   static_assert(MF == 0 || (LINEAR && !PK), "matrix-core form: linear class, whole-frame tiles");
   static_assert(ROW == 0 || (!PK && MF == 0 && !RUN && EDGE == (ROW == 1)), "row walk: v_dot2 form, aligned outputs");
@@ -519,12 +495,7 @@ __global__ void __launch_bounds__(256) mv_avg_stream_kernel(MvStreamArgs a) {
 // A 256-thread block takes a tile of 1024 outputs of one (object, frame): the 1024 + TAPS - 1 window samples go to LDS as int32 with
 // the boundary rule applied (coalesced loads), a thread owns four consecutive outputs and slides an eight-register window over the taps
 // -- one aligned 16-byte LDS read per four taps; coefficients are uniform reads -- then converts (requant64: any OUT_TYPE) and
-// stores its four outputs as one or two 16-byte vectors.  Before: 128-bit per-tap kernel, 0.034 of the roofline on <32,16> samples.
-struct MvW32Args {
-  int32_t d, sh, linear, ls, e; int64_t rnd_e; int32_t vec_ok;
-  // branch-free ACC -> OUT (CONV instantiations; IdConv's form in intg_dump.hip): wrap to ACC_TYPE, rounding shift, clamp, wrap to OUT_TYPE
-  int32_t ka, rs, ls2, ko; uint64_t am, om; int64_t rnd, lo, hi;
-};
+// stores its four outputs as one or two 16-byte vectors.  Before: 128-bit per-tap kernel, 0.034 of the roofline on <32,16> samples.  (Arguments: MvAvgParams and MvW32Args, mv_avg_plan.hpp.)
 
 template <bool LINEAR, bool CONV>   // LINEAR: d >= sh, the products add up unshifted (one v_mad_i64_i32 per tap and output); CONV: TRN / RND into WRAP / SAT
 __global__ void __launch_bounds__(256) mv_avg_w32_kernel(MvAvgParams p, MvW32Args a) {
@@ -604,284 +575,36 @@ __global__ void __launch_bounds__(256) mv_avg_w32_kernel(MvAvgParams p, MvW32Arg
 
 }  // namespace
 
-// true: launched (mv_avg_w32_kernel's class and shape conditions)
-static bool try_w32(const MvAvgParams &p, hipStream_t s) {
-  static const bool off = getenv("ACDSP_NO_MVAVG_W32") != nullptr;   // A/B knob
-  if (off || p.force_generic || !p.h_coeffs || (p.in_eb != 4 && p.in_eb != 2) || !(p.in.S || p.in.W <= 31) || p.taps > 1025) { return false; }
-  if (p.acc.O != ACDSP_WRAP || (p.acc.Q != ACDSP_TRN && p.acc.Q != ACDSP_RND) || p.cf.F >= 62) { return false; }   // order-free class
-  const int d = p.acc.F - p.in.F, sh = p.cf.F;
-  const int i_in = p.in.W - p.in.F, i_acc = p.acc.W - p.acc.F;
-  if (d < 0 || sh < 0) { return false; }
-  if (p.in.S ? (!p.acc.S || i_acc < i_in) : (i_acc < i_in + (p.acc.S ? 1 : 0))) { return false; }   // the cast (ACC_TYPE) w[j] is exact
-  int cbits = 1;
-  for (int i = 0; i < p.taps; i++) {
-    const int64_t c = p.h_coeffs[i];
-    if (c < INT32_MIN || c > INT32_MAX) { return false; }
-    const uint64_t m = (uint64_t)(c < 0 ? ~c : c);
-    int b = 1;
-    while (b < 64 && (m >> (b - 1)) != 0) { b++; }
-    if (b > cbits) { cbits = b; }
-  }
-  MvW32Args a;
-  memset(&a, 0, sizeof a);
-  a.d = d; a.sh = sh; a.linear = d >= sh; a.ls = a.linear ? d - sh : 0; a.e = a.linear ? 0 : sh - d;
-  // linear: the 32 x 32-bit products add up mod 2^64 and the shift comes once, after the sum; per tap: |x c| + rnd inside int64
-  if (a.ls > 62 || a.e > 62) { return false; }
-  a.rnd_e = (!a.linear && p.acc.Q == ACDSP_RND) ? (int64_t(1) << (a.e - 1)) : 0;
-  if (a.e > 0 && p.in.W + cbits > 61) { return false; }
-  a.vec_ok = p.out_per_frame % 4 == 0 && p.out_stride % 4 == 0 && ((uintptr_t)p.y % 16) == 0 && (p.out_eb == 2 || p.out_eb == 4 || p.out_eb == 8);
-  const int64_t pairs = (int64_t)p.n_obj * p.n_frames;
-  dim3 grid((unsigned)((p.out_per_frame + 1023) / 1024), (unsigned)(pairs < 65535 ? pairs : 65535));
-  const int nwin = (1024 + p.taps - 1 + 3 + 4) & ~3;
-  const size_t lds = (size_t)(nwin + p.taps) * sizeof(int32_t);
-  // ACC -> OUT without branches where the modes and the 64-bit arithmetic allow it (the conditions of intg_dump.hip: make_conv)
-  const int rs = p.acc.F - p.out.F;
-  const bool wrap_o = p.out.O == ACDSP_WRAP;
-  a.ka = 64 - p.acc.W; a.am = p.acc.S ? ~uint64_t(0) : (~uint64_t(0) >> (64 - p.acc.W));
-  a.rs = rs > 0 ? rs : 0; a.ls2 = rs < 0 ? -rs : 0;
-  a.rnd = (p.out.Q == ACDSP_RND && rs > 0) ? (int64_t(1) << (rs - 1)) : 0;
-  if (p.out.O == ACDSP_SAT) { a.lo = p.out.lo; a.hi = p.out.hi; a.ko = 0; a.om = ~uint64_t(0); }
-  else { a.lo = INT64_MIN; a.hi = INT64_MAX; a.ko = 64 - p.out.W; a.om = p.out.S ? ~uint64_t(0) : (~uint64_t(0) >> (64 - p.out.W)); }
-  const bool conv = (p.out.Q == ACDSP_TRN || p.out.Q == ACDSP_RND) && (wrap_o || p.out.O == ACDSP_SAT) && a.rs <= 60 && a.ls + a.ka < 64 &&
-                    (a.rnd == 0 || p.acc.W <= 61) && (a.ls2 == 0 || p.acc.W + a.ls2 <= 61 || wrap_o) &&
-                    (p.acc.S || p.acc.W <= 62 || (rs == 0 && wrap_o)) && (wrap_o || p.out.S ? p.out.W <= 64 : p.out.W <= 62);
-  if (a.linear) {
-    if (conv) { hipLaunchKernelGGL((mv_avg_w32_kernel<true, true>), grid, dim3(256), lds, s, p, a); }
-    else { hipLaunchKernelGGL((mv_avg_w32_kernel<true, false>), grid, dim3(256), lds, s, p, a); }
-  } else {
-    if (conv) { hipLaunchKernelGGL((mv_avg_w32_kernel<false, true>), grid, dim3(256), lds, s, p, a); }
-    else { hipLaunchKernelGGL((mv_avg_w32_kernel<false, false>), grid, dim3(256), lds, s, p, a); }
-  }
-  return true;
-}
-
-// true: launched.  Class and shape conditions of the streaming kernel (see above).
-static bool try_stream(const MvAvgParams &p, hipStream_t s, bool *mfma) {
-  *mfma = false;
-  static const bool off = getenv("ACDSP_NO_MVAVG_STREAM") != nullptr;   // A/B knob
-  if (off || p.force_generic || !p.h_coeffs || p.taps > 65 || p.in_eb != 2 || !(p.in.S || p.in.W <= 15)) { return false; }
-  if (p.n_sample < p.taps || p.n_sample % 8 != 0 || p.in_stride % 8 != 0 || ((uintptr_t)p.x % 16) != 0) { return false; }
-  // the cast (ACC_TYPE) w[j] is exact and the accumulator wraps
-  const int d = p.acc.F - p.in.F, sh = p.cf.F;
-  const int i_in = p.in.W - p.in.F, i_acc = p.acc.W - p.acc.F;
-  if (d < 0 || sh < 0 || p.acc.O != ACDSP_WRAP || (p.acc.Q != ACDSP_TRN && p.acc.Q != ACDSP_RND)) { return false; }
-  if (p.in.S ? (!p.acc.S || i_acc < i_in) : (i_acc < i_in + (p.acc.S ? 1 : 0))) { return false; }
-  int64_t sum_abs = 0;
-  for (int i = 0; i < p.taps; i++) {
-    if (p.h_coeffs[i] < -32768 || p.h_coeffs[i] > 32767) { return false; }
-    sum_abs += p.h_coeffs[i] < 0 ? -p.h_coeffs[i] : p.h_coeffs[i];
-  }
-  if (sum_abs > 32767) { return false; }            // |sum of products| < 2^30: every intermediate stays inside int32
-  MvStreamArgs a;
-  memset(&a, 0, sizeof a);
-  for (int i = 0; i < p.taps; i++) { a.c16[i] = (int16_t)p.h_coeffs[i]; a.c16o[i + 1] = (int16_t)p.h_coeffs[i]; }
-  a.taps = p.taps; a.h = p.taps / 2; a.mode = p.win_mode;
-  a.hb = p.win_mode == 0 ? 0 : 8 * ((a.h + 7) / 8);
-  a.off = p.win_mode == 0 ? 0 : a.hb - a.h;
-  a.nxg = (a.off + p.taps - 1 + 7) / 8;
-  a.linear = d >= sh;
-  a.ls = a.linear ? d - sh : 0;
-  a.e = a.linear ? 0 : sh - d;
-  if (a.e > 30 || a.ls > 62) { return false; }
-  a.rnd_e = (!a.linear && p.acc.Q == ACDSP_RND) ? (1 << (a.e - 1)) : 0;
-  if (p.acc.W > 61 || a.ls >= p.acc.W) { return false; }
-  // ACC -> OUT
-  if ((p.out.Q != ACDSP_TRN && p.out.Q != ACDSP_RND) || (p.out.O != ACDSP_WRAP && p.out.O != ACDSP_SAT) || p.out.W > 62) { return false; }
-  const int rs = p.acc.F - p.out.F;
-  a.ka = 64 - p.acc.W; a.am = p.acc.S ? ~uint64_t(0) : (~uint64_t(0) >> (64 - p.acc.W));
-  a.rs = rs > 0 ? rs : 0; a.ls2 = rs < 0 ? -rs : 0;
-  if (a.rs > 60 || p.acc.W + a.ls2 > 61) { return false; }
-  a.rnd = (p.out.Q == ACDSP_RND && rs > 0) ? (int64_t(1) << (rs - 1)) : 0;
-  if (p.out.O == ACDSP_SAT) { a.lo = p.out.lo; a.hi = p.out.hi; a.ko = 0; a.om = ~uint64_t(0); }
-  else { a.lo = INT64_MIN; a.hi = INT64_MAX; a.ko = 64 - p.out.W; a.om = p.out.S ? ~uint64_t(0) : (~uint64_t(0) >> (64 - p.out.W)); }
-  // 32-bit form: the accumulator cannot wrap (signed, W_acc >= 31 + ls) and the output shift swallows ls
-  // (|sum| <= sum|c| * 2^(W_in - 1): samples narrower than 16 bits need a narrower accumulator)
-  int sum_bits = 0;
-  while (sum_bits < 62 && (int64_t(1) << sum_bits) <= sum_abs * (int64_t(1) << (p.in.W - (p.in.S ? 1 : 0)))) { sum_bits++; }   // |sum| < 2^sum_bits
-  a.cv32 = p.acc.S && p.acc.W >= sum_bits + 1 + a.ls && rs >= a.ls && rs - a.ls <= 30 && (p.out.S || p.out.W <= 31);
-  if (a.cv32) {
-    a.s32 = rs - a.ls;
-    a.r32 = (p.out.Q == ACDSP_RND && a.s32 > 0) ? (1 << (a.s32 - 1)) : 0;
-    a.lo32 = INT32_MIN; a.hi32 = INT32_MAX; a.ko32 = 0;
-    if (p.out.O == ACDSP_SAT) {
-      if (p.out.lo > INT32_MIN) { a.lo32 = (int32_t)p.out.lo; }
-      if (p.out.hi < INT32_MAX) { a.hi32 = (int32_t)p.out.hi; }
-    } else if (p.out.W < 32) { a.ko32 = 32 - p.out.W; }
-  }
-  a.out_eb = p.out_eb;
-  a.vec_ok = p.out_per_frame % 8 == 0 && p.out_stride % 8 == 0 && ((uintptr_t)p.y % 16) == 0;
-  static const bool no_pk16 = getenv("ACDSP_NO_MVAVG_PK16") != nullptr;   // A/B knob
-  a.pk16 = !no_pk16 && a.cv32 && a.vec_ok && p.out_eb == 2 && a.lo32 == -32768 && a.hi32 == 32767 && a.ko32 == 0 && a.om == ~uint64_t(0);
-  static const bool no_run = getenv("ACDSP_NO_MVAVG_RUN") != nullptr;   // A/B knob: element stores for unaligned output frames
-  a.run_ok = !a.vec_ok && !no_run && ((uintptr_t)p.y % p.out_eb) == 0 && p.out_eb <= 4;   // (8-byte outputs: 4 KB + the offset would not fit the image; they keep element stores, 64 contiguous bytes per lane)
-  a.n_sample = p.n_sample; a.n_frames = p.n_frames; a.opf = p.out_per_frame; a.in_stride = p.in_stride; a.out_stride = p.out_stride;
-  a.tpf = (p.out_per_frame + 511) / 512;
-  a.n_tiles = (int64_t)p.n_obj * p.n_frames * a.tpf;
-  // Frames shorter than a 512-output tile (round 5: 128-sample frames used 16 of a wave's 64 lanes, 0.21 of the roofline): with AC_CLIP /
-  // AC_MIRROR every output of a frame depends on that frame's samples only, frames lie back to back in the row, so a tile takes 512 / n whole
-  // frames -- each in its own slot of the LDS image, both halos patched from the staged samples -- and the row is walked as ONE frame.
-  a.pk_n = 0; a.pk_pitch = 0; a.pk_sh = 0;
-  static const bool no_pk = getenv("ACDSP_NO_MVAVG_PACK") != nullptr;   // A/B knob
-  if (!no_pk && p.win_mode != 0 && (p.n_sample == 64 || p.n_sample == 128 || p.n_sample == 256) && p.n_frames % (512 / p.n_sample) == 0) {
-    a.pk_n = (int32_t)p.n_sample; a.pk_pitch = a.pk_n + 2 * a.hb; a.pk_sh = p.n_sample == 64 ? 6 : (p.n_sample == 128 ? 7 : 8);
-    a.nxg = 0;
-    a.n_sample = p.n_sample * p.n_frames; a.n_frames = 1; a.opf = a.n_sample; a.tpf = a.opf / 512;
-    a.n_tiles = (int64_t)p.n_obj * a.tpf;
-    a.run_ok = 0;   // (packed tiles keep element stores when the output row is off the boundary)
-  }
-  // Frames that are no multiple of the 512-output tile (round 6: frames of 1000 samples at 0.57 where 1024 run 0.68).  Frame-relative tiles start wherever
-  // their frame starts: every 1 KB store run and load straddles cache lines, and the frame's last tile is partly empty.  With AC_CLIP / AC_MIRROR input
-  // and output positions of a row coincide, so the tiles can walk the ROW in aligned 512-output steps and take the frame edges where they fall: at most
-  // one edge per tile image (frames of at least 512 + 2 hb samples), the samples behind it shifted by a gap of 2 hb that holds both halos (ROW instantiations).
-  a.row_n = 0;
-  static const bool no_row = getenv("ACDSP_NO_MVAVG_ROW") != nullptr;   // A/B knob
-  const bool mf_wanted = [&] {
-    ACDSP_TUNE_ENV(mf_env0, "ACDSP_MVAVG_MFMA_MIN");
-    const int mn = mf_env0 ? atoi(mf_env0) : (p.win_mode == 0 ? 9 : 11);
-    return p.frag && p.frag_nb > 0 && a.linear && mn > 0 && p.taps >= mn;
-  }();
-  if (!no_row && !a.pk_n && !mf_wanted && p.win_mode != 0 && p.n_sample % 512 != 0 && p.n_sample >= 512 + 2 * a.hb && a.vec_ok &&
-      p.n_sample * p.n_frames < (int64_t(1) << 31) - 1024) {
-    a.row_n = (int32_t)p.n_sample;
-    a.n_sample = p.n_sample * p.n_frames; a.n_frames = 1; a.opf = a.n_sample; a.tpf = (a.opf + 511) / 512;
-    a.n_tiles = (int64_t)p.n_obj * a.tpf;
-  }
-  // ... and AC_WIN (ROW 2): N - TAPS + 1 outputs per frame lie back to back in the output row while their windows jump TAPS - 1 samples at every frame
-  // edge.  Where both are multiples of 8 (TAPS = 9, 17, 25 ...: the windows stay aligned) the tiles walk the OUTPUT row; the image is the contiguous input
-  // and the lanes behind the edge start TAPS - 1 samples further on.
-  a.row_opf = 0;
-  {
-    ACDSP_TUNE_ENV(roww_env, "ACDSP_MVAVG_ROWW_MAX");   // A/B knob: the longest window that walks the output row (longer ones: matrix cores, frame-relative)
-    // (same box, 512 objects x 2^20 in frames of 1024: 9 taps 0.54 frame-relative v_dot2 / 0.59 matrix cores / 0.69 row walk; 17 taps 0.62 / 0.61 / 0.62; 25 taps
-    // 0.55 / 0.59 / 0.55; 33 taps 0.50 / 0.61 / 0.49 -- the v_dot2 form is VALU-bound from 17 taps on, where the walk buys nothing)
-    const int roww_max = roww_env ? atoi(roww_env) : 9;
-    if (!no_row && p.win_mode == 0 && p.taps <= roww_max && p.taps > 1 && (p.taps - 1) % 8 == 0 && p.out_per_frame >= 512 && p.out_per_frame % 512 != 0 && a.vec_ok &&
-        p.n_sample * p.n_frames < (int64_t(1) << 31) - 1024) {
-      a.row_n = (int32_t)p.n_sample; a.row_opf = (int32_t)p.out_per_frame;
-      a.n_sample = p.n_sample * p.n_frames; a.n_frames = 1; a.opf = p.out_per_frame * p.n_frames; a.tpf = (a.opf + 511) / 512;
-      a.n_tiles = (int64_t)p.n_obj * a.tpf;
-      a.nxg += (p.taps - 1) / 8;
-    }
-  }
-  a.tiles_per_wave = 16;   // 16 KB spans (8 / 16 tiles alike, 32: -5 %, 64: -9 %: profiles/r3_span_sweep.txt)
-  while (a.tiles_per_wave > 1 && a.n_tiles / a.tiles_per_wave < 16384) { a.tiles_per_wave /= 2; }
-  ACDSP_TUNE_ENV(tpw_env, "ACDSP_MVAVG_TPW");   // tuning knob: tiles per wave
-  if (tpw_env && atoi(tpw_env) > 0) { a.tiles_per_wave = atoi(tpw_env); }
-  a.x = (const int16_t *)p.x; a.y = p.y;
-  const int64_t waves = (a.n_tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
-  const int64_t blocks = (waves + 3) / 4;
-  if (blocks > 0x7FFFFFFF) { return false; }
-  dim3 grid((unsigned)blocks);
-  a.xcd_map = (xcd_map_wanted(false) && blocks % 8 == 0) ? 1 : 0;
-  // windows of 17 taps and more: the sums on the matrix cores (fragments built by the handle at set_coeffs: mv_avg_build_frags)
-  ACDSP_TUNE_ENV(mf_env, "ACDSP_MVAVG_MFMA_MIN");   // A/B knob: the smallest window that takes them (0: never)
-  // (same box, 512 objects x 2^20, frames of 1024: v_dot2 0.68 / MFMA 0.62 of the roofline at 9 taps, 0.57 / 0.62 at 11, 0.46 / 0.61 at 33, 0.29 / 0.53 at
-  // 65; AC_WIN 0.54 / 0.58 at 9 taps -- profiles/r6_mvavg_mfma.txt)
-  const int mf_min = mf_env ? atoi(mf_env) : (p.win_mode == 0 ? 9 : 11);
-  if (p.frag && p.frag_nb > 0 && a.linear && !a.pk_n && !a.row_n && mf_min > 0 && p.taps >= mf_min) {
-    a.frag = p.frag;
-    a.kbias = (int32_t)(128 * p.frag_csum);
-// (NR = 9: only REGION -- how far the right-edge patches reach into the image -- depends on it here)
-#define ACDSP_MV_MF(CV_, EDGE_, MF_)                                                                                      \
-  do {                                                                                                                      \
-    if (a.run_ok) { hipLaunchKernelGGL((mv_avg_stream_kernel<9, true, CV_, EDGE_, false, MF_, true>), grid, dim3(256), 0, s, a); } \
-    else { hipLaunchKernelGGL((mv_avg_stream_kernel<9, true, CV_, EDGE_, false, MF_, false>), grid, dim3(256), 0, s, a); }   \
-  } while (0)
-    if (p.frag_nb == 1) {
-      if (a.cv32) { if (a.mode != 0) { ACDSP_MV_MF(true, true, 1); } else { ACDSP_MV_MF(true, false, 1); } }
-      else { if (a.mode != 0) { ACDSP_MV_MF(false, true, 1); } else { ACDSP_MV_MF(false, false, 1); } }
-    } else {
-      if (a.cv32) { if (a.mode != 0) { ACDSP_MV_MF(true, true, 2); } else { ACDSP_MV_MF(true, false, 2); } }
-      else { if (a.mode != 0) { ACDSP_MV_MF(false, true, 2); } else { ACDSP_MV_MF(false, false, 2); } }
-    }
+// The compiled kernels as data, MvCall::inst -> kernel.  mv_avg_stream_kernel: six NR x LINEAR x CV32 x the seven forms of the v_dot2 kernel ...
+#define ACDSP_MV_K(NR, LIN, CV, EDGE, PK, MF, RUN, ROW) {{NR, LIN, CV, EDGE, PK, MF, RUN, ROW}, mv_avg_stream_kernel<NR, LIN, CV, EDGE, PK, MF, RUN, ROW>}
+#define ACDSP_MV_FORMS(NR, LIN, CV)                                                                                              \
+  ACDSP_MV_K(NR, LIN, CV, true, true, 0, false, 0),   /* packed short frames */                                                 \
+  ACDSP_MV_K(NR, LIN, CV, false, false, 0, false, 2), /* row walk, AC_WIN */                                                    \
+  ACDSP_MV_K(NR, LIN, CV, true, false, 0, false, 1),  /* row walk, frame edges inside the tiles */                              \
+  ACDSP_MV_K(NR, LIN, CV, true, false, 0, true, 0), ACDSP_MV_K(NR, LIN, CV, false, false, 0, true, 0), /* aligned runs */     \
+  ACDSP_MV_K(NR, LIN, CV, true, false, 0, false, 0), ACDSP_MV_K(NR, LIN, CV, false, false, 0, false, 0)
+#define ACDSP_MV_NR(NR) ACDSP_MV_FORMS(NR, true, true), ACDSP_MV_FORMS(NR, true, false), ACDSP_MV_FORMS(NR, false, true), ACDSP_MV_FORMS(NR, false, false)
+// ... and on the matrix cores MF x CV32 x EDGE x RUN
+#define ACDSP_MV_MF(MF, CV) ACDSP_MV_K(9, true, CV, true, false, MF, true, 0), ACDSP_MV_K(9, true, CV, true, false, MF, false, 0), \
+                            ACDSP_MV_K(9, true, CV, false, false, MF, true, 0), ACDSP_MV_K(9, true, CV, false, false, MF, false, 0)
+static const MvInst<void (*)(MvStreamArgs)> kStreamKernels[] = {ACDSP_MV_NR(2), ACDSP_MV_NR(3), ACDSP_MV_NR(4), ACDSP_MV_NR(5), ACDSP_MV_NR(7), ACDSP_MV_NR(9),
+                                                                ACDSP_MV_MF(1, true), ACDSP_MV_MF(1, false), ACDSP_MV_MF(2, true), ACDSP_MV_MF(2, false)};
 #undef ACDSP_MV_MF
-    *mfma = true;
-    return true;
-  }
-  const int nr = p.taps <= 9 ? 2 : (p.taps <= 17 ? 3 : (p.taps <= 25 ? 4 : (p.taps <= 33 ? 5 : (p.taps <= 49 ? 7 : 9))));   // taps <= 8 NR - 7
-#define ACDSP_MV_LAUNCH2(NR_, LIN_, CV_)                                                                                           \
-  if (a.pk_n) { hipLaunchKernelGGL((mv_avg_stream_kernel<NR_, LIN_, CV_, true, true>), grid, dim3(256), 0, s, a); }               \
-  else if (a.row_n && a.row_opf) { hipLaunchKernelGGL((mv_avg_stream_kernel<NR_, LIN_, CV_, false, false, 0, false, 2>), grid, dim3(256), 0, s, a); } \
-  else if (a.row_n) { hipLaunchKernelGGL((mv_avg_stream_kernel<NR_, LIN_, CV_, true, false, 0, false, 1>), grid, dim3(256), 0, s, a); } \
-  else if (a.run_ok) {                                                                                                             \
-    if (a.mode != 0) { hipLaunchKernelGGL((mv_avg_stream_kernel<NR_, LIN_, CV_, true, false, 0, true>), grid, dim3(256), 0, s, a); } \
-    else { hipLaunchKernelGGL((mv_avg_stream_kernel<NR_, LIN_, CV_, false, false, 0, true>), grid, dim3(256), 0, s, a); }          \
-  }                                                                                                                                \
-  else if (a.mode != 0) { hipLaunchKernelGGL((mv_avg_stream_kernel<NR_, LIN_, CV_, true>), grid, dim3(256), 0, s, a); }             \
-  else { hipLaunchKernelGGL((mv_avg_stream_kernel<NR_, LIN_, CV_, false>), grid, dim3(256), 0, s, a); }
-#define ACDSP_MV_LAUNCH(NR_)                                                                                                       \
-  if (a.linear) {                                                                                                                   \
-    if (a.cv32) { ACDSP_MV_LAUNCH2(NR_, true, true) } else { ACDSP_MV_LAUNCH2(NR_, true, false) }                                  \
-  } else {                                                                                                                          \
-    if (a.cv32) { ACDSP_MV_LAUNCH2(NR_, false, true) } else { ACDSP_MV_LAUNCH2(NR_, false, false) }                                \
-  }
-  switch (nr) {
-    case 2: ACDSP_MV_LAUNCH(2) break;
-    case 3: ACDSP_MV_LAUNCH(3) break;
-    case 4: ACDSP_MV_LAUNCH(4) break;
-    case 5: ACDSP_MV_LAUNCH(5) break;
-    case 7: ACDSP_MV_LAUNCH(7) break;
-    default: ACDSP_MV_LAUNCH(9) break;
-  }
-#undef ACDSP_MV_LAUNCH2
-#undef ACDSP_MV_LAUNCH
-  return true;
-}
+#undef ACDSP_MV_NR
+#undef ACDSP_MV_FORMS
+#undef ACDSP_MV_K
+static const MvInst<void (*)(MvAvgParams, MvW32Args)> kW32Kernels[] = {{{true, true}, mv_avg_w32_kernel<true, true>}, {{true, false}, mv_avg_w32_kernel<true, false>},
+                                                                        {{false, true}, mv_avg_w32_kernel<false, true>}, {{false, false}, mv_avg_w32_kernel<false, false>}};
+static const MvInst<void (*)(MvAvgParams)> kGeneralKernels[] = {{{true}, mv_avg_kernel<true>}, {{false}, mv_avg_kernel<false>}};
 
-// Toeplitz fragments of the matrix-core forms (mv_avg_stream_kernel, MF instantiations: gran = 8 samples; mv_avg_s8_kernel: gran = 16, the
-// samples its 16-byte tile loads are aligned to).  The window's half length is rounded up to `gran` in front of a tile (hb; 0 under AC_WIN) and
-// the window starts off = hb - TAPS / 2 samples into the image.  Returns the K blocks (1 / 2; 0: the coefficient set or the window does not
-// fit) and fills out[((m nb + b) 2 + plane) 64 + lane][4 dwords]: lane (row i = lane & 15, kg = lane >> 4) holds A[i][16 kg .. 16 kg + 15] of
-// K block b, A[i][kk] = digit_plane(c[64 b + kk - sigma_m(i) - off]), sigma_m(i) = 8 (i >> 2) + (i & 3) + 4 m; c = 256 ch + cl with both digits
-// signed bytes (balanced: cl = int8(c & 255)), so that every product is a signed i8 x i8 one.  *hi_any: some ch is not 0 (plane 1 is needed).
-int mv_avg_build_frags(const int64_t *c, int taps, int win_mode, int gran, uint32_t *out, int64_t *csum, int *hi_any) {
-  const int h = taps / 2, hb = win_mode == 0 ? 0 : gran * ((h + gran - 1) / gran), off = win_mode == 0 ? 0 : hb - h;
-  if (taps > 65 || 31 + off + taps - 1 >= 128) { return 0; }
-  const int nb = (31 + off + taps - 1 < 64) ? 1 : 2;
-  int64_t sum = 0;
-  int hi = 0;
-  for (int t = 0; t < taps; t++) {
-    if (c[t] < -32768 || c[t] > 32639) { return 0; }   // the balanced high digit of 32640 .. 32767 is 128
-    sum += c[t];
-    hi |= (c[t] < -128 || c[t] > 127) ? 1 : 0;
+hipError_t launch_mv_avg(const MvCall &c, hipStream_t s) {
+  switch (c.path) {
+    case 0: case 1: return mv_launch(kGeneralKernels, c, s, c.p);
+    case 2: case 4: return mv_launch(kStreamKernels, c, s, c.a.st);
+    case 3: return mv_launch(kW32Kernels, c, s, c.p, c.a.w32);
+    case 5: return launch_mv_avg_s8(c, s);
+    default: return hipSuccess;   // nothing to launch
   }
-  *csum = sum;
-  *hi_any = hi;
-  for (int m = 0; m < 2; m++) {
-    for (int b = 0; b < nb; b++) {
-      for (int lane = 0; lane < 64; lane++) {
-        const int i = lane & 15, kg = lane >> 4, sig = 8 * (i >> 2) + (i & 3) + 4 * m;
-        for (int dw = 0; dw < 4; dw++) {
-          uint32_t wl = 0, wh = 0;
-          for (int bj = 0; bj < 4; bj++) {
-            const int t = 64 * b + 16 * kg + 4 * dw + bj - sig - off;
-            const int64_t cv = (t >= 0 && t < taps) ? c[t] : 0;
-            const int cl = (int)(int8_t)(uint8_t)(cv & 0xFF), ch = (int)((cv - cl) >> 8);
-            wl |= (uint32_t)(uint8_t)cl << (8 * bj);
-            wh |= (uint32_t)(uint8_t)ch << (8 * bj);
-          }
-          out[(((size_t)(m * nb + b) * 2 + 0) * 64 + lane) * 4 + dw] = wl;
-          out[(((size_t)(m * nb + b) * 2 + 1) * 64 + lane) * 4 + dw] = wh;
-        }
-      }
-    }
-  }
-  return nb;
-}
-
-hipError_t launch_mv_avg(const MvAvgParams &p, hipStream_t s, int *path) {
-  if (p.out_per_frame <= 0 || p.n_frames <= 0) { return hipSuccess; }
-  bool mfma = false;
-  if (p.in_eb == 1 && mv_avg_try_s8(p, s)) { *path = 5; return hipGetLastError(); }   // byte rows outside its class: the container-agnostic kernels below
-  if (try_stream(p, s, &mfma)) { *path = mfma ? 4 : 2; return hipGetLastError(); }
-  if (try_w32(p, s)) { *path = 3; return hipGetLastError(); }
-  *path = p.fast ? 1 : 0;
-  const int64_t pairs = (int64_t)p.n_obj * p.n_frames;
-  dim3 grid((unsigned)((p.out_per_frame + kTile - 1) / kTile), (unsigned)(pairs < 65535 ? pairs : 65535));
-  const size_t lds = (size_t)(kTile + 2 * p.taps - 1) * sizeof(int64_t);
-  if (p.fast) { hipLaunchKernelGGL(mv_avg_kernel<true>, grid, dim3(kTile), lds, s, p); }
-  else { hipLaunchKernelGGL(mv_avg_kernel<false>, grid, dim3(kTile), lds, s, p); }
-  return hipGetLastError();
 }
 
 }  // namespace acdsp

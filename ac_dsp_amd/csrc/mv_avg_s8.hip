@@ -4,8 +4,8 @@
 // v_mfma_i32_16x16x64_i8 as it lies in memory: no split into planes, ONE sample plane, and one product per K block and row order when every
 // coefficient is a single signed byte (two when some coefficient carries a high digit).
 //
-// Class (try_s8): the linear class of try_stream -- the cast of a sample to ACC_TYPE is exact, d = F_acc - F_in >= sh = F_coeff >= 0, a wrapping
-// AC_TRN / AC_RND accumulator (a saturating one that run() has proved sat-free arrives here as a wrapping one), coefficients inside int16 with
+// Class (plan_s8 in mv_avg_plan.hip; the set plan holds the part that depends on the coefficient set): the linear class of plan_stream -- the cast of a sample to ACC_TYPE is exact, d = F_acc - F_in >= sh = F_coeff >= 0, a wrapping
+// AC_TRN / AC_RND accumulator (a saturating one that the set plan has proved sat-free arrives here as a wrapping one), coefficients inside int16 with
 // sum |c| <= 32767 and none above 32639, AC_TRN / AC_RND into AC_WRAP / AC_SAT outputs -- on windows of 1 .. 65 taps, every window mode,
 // n_sample >= TAPS.  Shape: input rows and row pitch aligned to 16 bytes and n_sample % 16 == 0.  Frames of n_sample % 8 == 0 that are no
 // multiple of 16 are NOT taken (an 8-byte load form would halve the bytes per load instruction on a kernel that lives on them; they run on the
@@ -22,30 +22,13 @@
 // K blocks x 2 MFMAs per 512 outputs.  The accumulator-to-output conversion has the two forms of the 16-bit kernel: 32-bit shift / clamp when
 // nothing can wrap, else the 64-bit branch-free form.  Outputs: a lane's eight results leave as one 8-byte store (1-byte containers), one
 // 16-byte store (2-byte) or two / four 16-byte stores (4- / 8-byte); rows whose 8-output groups are not aligned take guarded element stores.
-#include <cstdlib>
 #include <cstring>
 
-#include "fir_kernels.hpp"
+#include "mv_avg_plan.hpp"
 
 namespace acdsp {
 
 namespace {
-
-struct MvS8Args {
-  int32_t h, hb, mode, nld;   // nld: lanes that load (32 for the tile + the 16-byte groups of the window reach)
-  uint32_t flip;              // 0x80808080 on unsigned samples
-  int32_t kbias;              // 128 sum(c) on unsigned samples (+ the rounding constant of the 32-bit epilogue)
-  int32_t ls;                 // d - sh: the sum's weight inside ACC_TYPE
-  int32_t s32, lo32, hi32, ko32;              // 32-bit epilogue: q = (S + r32) >> s32, clamp, wrap (ko32 = 32 - W_out or 0)
-  int32_t ka, rs, ls2, ko;                    // 64-bit epilogue (see IdConv in intg_dump.hip)
-  uint64_t am, om;
-  int64_t rnd, lo, hi;
-  int32_t out_eb, vec_ok;     // vec_ok: every lane's eight outputs are an aligned 8 (1-byte containers) / 16 / 32 / 64 bytes
-  int64_t n_sample, n_frames, opf, in_stride, out_stride, tpf, n_tiles, tiles_per_wave;
-  const unsigned char *x;
-  void *y;
-  const uint32_t *frag;       // [m][b][plane][lane] x 16 bytes
-};
 
 typedef int v4i_s8 __attribute__((ext_vector_type(4)));
 typedef unsigned v4u_s8 __attribute__((ext_vector_type(4)));
@@ -209,83 +192,12 @@ __global__ void __launch_bounds__(256) mv_avg_s8_kernel(MvS8Args a) {
 
 }  // namespace
 
-// true: launched.  Class and shape conditions of mv_avg_s8_kernel (see the header of this file).
-bool mv_avg_try_s8(const MvAvgParams &p, hipStream_t s) {
-  if (p.force_generic || !p.h_coeffs || !p.frag || p.frag_nb < 1 || p.frag_gran != 16 || p.taps > 65 || p.in_eb != 1 || p.in.W > 8) { return false; }
-  if (p.n_sample < p.taps || p.n_sample % 16 != 0 || p.in_stride % 16 != 0 || ((uintptr_t)p.x % 16) != 0) { return false; }
-  // the cast (ACC_TYPE) w[j] is exact, the accumulator wraps, and the products add up unshifted (linear class)
-  const int d = p.acc.F - p.in.F, sh = p.cf.F;
-  const int i_in = p.in.W - p.in.F, i_acc = p.acc.W - p.acc.F;
-  if (sh < 0 || d < sh || p.acc.O != ACDSP_WRAP || (p.acc.Q != ACDSP_TRN && p.acc.Q != ACDSP_RND)) { return false; }
-  if (p.in.S ? (!p.acc.S || i_acc < i_in) : (i_acc < i_in + (p.acc.S ? 1 : 0))) { return false; }
-  int64_t sum_abs = 0;
-  for (int i = 0; i < p.taps; i++) {
-    if (p.h_coeffs[i] < -32768 || p.h_coeffs[i] > 32639) { return false; }   // (what mv_avg_build_frags takes)
-    sum_abs += p.h_coeffs[i] < 0 ? -p.h_coeffs[i] : p.h_coeffs[i];
-  }
-  if (sum_abs > 32767) { return false; }            // |sum of products| < 2^23: every intermediate stays inside int32
-  MvS8Args a;
-  memset(&a, 0, sizeof a);
-  a.h = p.taps / 2; a.mode = p.win_mode;
-  a.hb = p.win_mode == 0 ? 0 : 16 * ((a.h + 15) / 16);
-  const int off = p.win_mode == 0 ? 0 : a.hb - a.h;
-  a.nld = 32 + (off + p.taps - 1 + 15) / 16;
-  a.flip = p.in.S ? 0u : 0x80808080u;
-  a.kbias = p.in.S ? 0 : (int32_t)(128 * p.frag_csum);
-  a.ls = d - sh;
-  if (a.ls > 62 || p.acc.W > 61 || a.ls >= p.acc.W) { return false; }
-  // ACC -> OUT
-  if ((p.out.Q != ACDSP_TRN && p.out.Q != ACDSP_RND) || (p.out.O != ACDSP_WRAP && p.out.O != ACDSP_SAT) || p.out.W > 62) { return false; }
-  const int rs = p.acc.F - p.out.F;
-  a.ka = 64 - p.acc.W; a.am = p.acc.S ? ~uint64_t(0) : (~uint64_t(0) >> (64 - p.acc.W));
-  a.rs = rs > 0 ? rs : 0; a.ls2 = rs < 0 ? -rs : 0;
-  if (a.rs > 60 || p.acc.W + a.ls2 > 61) { return false; }
-  a.rnd = (p.out.Q == ACDSP_RND && rs > 0) ? (int64_t(1) << (rs - 1)) : 0;
-  if (p.out.O == ACDSP_SAT) { a.lo = p.out.lo; a.hi = p.out.hi; a.ko = 0; a.om = ~uint64_t(0); }
-  else { a.lo = INT64_MIN; a.hi = INT64_MAX; a.ko = 64 - p.out.W; a.om = p.out.S ? ~uint64_t(0) : (~uint64_t(0) >> (64 - p.out.W)); }
-  // 32-bit form: the accumulator cannot wrap (signed, W_acc >= sum bits + 1 + ls) and the output shift swallows ls;
-  // |sum| <= sum|c| * 2^(W_in - 1) (signed samples) or sum|c| * 2^W_in (unsigned)
-  int sum_bits = 0;
-  while (sum_bits < 62 && (int64_t(1) << sum_bits) <= sum_abs * (int64_t(1) << (p.in.W - (p.in.S ? 1 : 0)))) { sum_bits++; }   // |sum| < 2^sum_bits
-  const bool cv32 = p.acc.S && p.acc.W >= sum_bits + 1 + a.ls && rs >= a.ls && rs - a.ls <= 30 && (p.out.S || p.out.W <= 31);
-  if (cv32) {
-    a.s32 = rs - a.ls;
-    if (p.out.Q == ACDSP_RND && a.s32 > 0) { a.kbias += 1 << (a.s32 - 1); }   // the rounding constant rides in the sum (|sum| < 2^24, it is <= 2^29)
-    a.lo32 = INT32_MIN; a.hi32 = INT32_MAX; a.ko32 = 0;
-    if (p.out.O == ACDSP_SAT) {
-      if (p.out.lo > INT32_MIN) { a.lo32 = (int32_t)p.out.lo; }
-      if (p.out.hi < INT32_MAX) { a.hi32 = (int32_t)p.out.hi; }
-    } else if (p.out.W < 32) { a.ko32 = 32 - p.out.W; }
-  }
-  a.out_eb = p.out_eb;
-  const int grp = p.out_eb == 1 ? 8 : 16;           // bytes a lane's first store must be aligned to
-  a.vec_ok = p.out_per_frame % 8 == 0 && p.out_stride % 8 == 0 && ((uintptr_t)p.y % grp) == 0 && (p.out_eb == 1 || p.out_eb == 2 || p.out_eb == 4 || p.out_eb == 8);
-  a.n_sample = p.n_sample; a.n_frames = p.n_frames; a.opf = p.out_per_frame; a.in_stride = p.in_stride; a.out_stride = p.out_stride;
-  a.tpf = (p.out_per_frame + 511) / 512;
-  a.n_tiles = (int64_t)p.n_obj * p.n_frames * a.tpf;
-  a.tiles_per_wave = 32;   // 16 KB spans, as the 16-bit kernel walks
-  while (a.tiles_per_wave > 1 && a.n_tiles / a.tiles_per_wave < 16384) { a.tiles_per_wave /= 2; }
-  ACDSP_TUNE_ENV(tpw_env, "ACDSP_MVAVG_TPW");   // tuning knob: tiles per wave, as on the 16-bit kernel (tests/test_mvavg_bytes_gpu.py walks runs of tiles with it)
-  if (tpw_env && atoi(tpw_env) > 0) { a.tiles_per_wave = atoi(tpw_env); }
-  a.x = (const unsigned char *)p.x; a.y = p.y; a.frag = p.frag;
-  const int64_t waves = (a.n_tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
-  const int64_t blocks = (waves + 3) / 4;
-  if (blocks > 0x7FFFFFFF) { return false; }
-  const dim3 grid((unsigned)blocks);
-#define ACDSP_MV_S8(NB_, HI_)                                                                                                  \
-  do {                                                                                                                         \
-    if (cv32) {                                                                                                                \
-      if (a.mode != 0) { hipLaunchKernelGGL((mv_avg_s8_kernel<NB_, HI_, true, true>), grid, dim3(256), 0, s, a); }              \
-      else { hipLaunchKernelGGL((mv_avg_s8_kernel<NB_, HI_, true, false>), grid, dim3(256), 0, s, a); }                         \
-    } else {                                                                                                                   \
-      if (a.mode != 0) { hipLaunchKernelGGL((mv_avg_s8_kernel<NB_, HI_, false, true>), grid, dim3(256), 0, s, a); }             \
-      else { hipLaunchKernelGGL((mv_avg_s8_kernel<NB_, HI_, false, false>), grid, dim3(256), 0, s, a); }                        \
-    }                                                                                                                          \
-  } while (0)
-  if (p.frag_nb == 1) { if (p.frag_hi) { ACDSP_MV_S8(1, true); } else { ACDSP_MV_S8(1, false); } }
-  else { if (p.frag_hi) { ACDSP_MV_S8(2, true); } else { ACDSP_MV_S8(2, false); } }
+// NB x HI x CV32 x EDGE (MvCall::inst; plan_s8 in mv_avg_plan.hip decides)
+#define ACDSP_MV_S8(NB, HI) {{NB, HI, true, true}, mv_avg_s8_kernel<NB, HI, true, true>}, {{NB, HI, true, false}, mv_avg_s8_kernel<NB, HI, true, false>}, \
+                            {{NB, HI, false, true}, mv_avg_s8_kernel<NB, HI, false, true>}, {{NB, HI, false, false}, mv_avg_s8_kernel<NB, HI, false, false>}
+static const MvInst<void (*)(MvS8Args)> kS8Kernels[] = {ACDSP_MV_S8(1, true), ACDSP_MV_S8(1, false), ACDSP_MV_S8(2, true), ACDSP_MV_S8(2, false)};
 #undef ACDSP_MV_S8
-  return true;
-}
+
+hipError_t launch_mv_avg_s8(const MvCall &c, hipStream_t s) { return mv_launch(kS8Kernels, c, s, c.a.s8); }
 
 }  // namespace acdsp

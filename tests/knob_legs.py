@@ -41,7 +41,7 @@ LEGS = {
                             {"fir_cshift:w14_keep_all.cshift": 1, "fir_cshift:w8.cshift": 2})],
     "ACDSP_NO_UNSIGNED16": [leg({"ACDSP_NO_UNSIGNED16": "1"}, ["fir_u16"], {"fir_u16:acc44.kernel": "lossless64", "fir_u16:acc34.kernel": "lossless64"},
                                 {"fir_u16:acc44.kernel": "mfma_i8", "fir_u16:acc34.kernel": "mfma_i8"})],
-    # read in engine_fir.hip, engine_poly.hip and engine_misc.hip (ac_intg_dump, ac_mv_avg)
+    # read in engine_fir.hip, engine_poly.hip, engine_misc.hip (ac_intg_dump) and mv_avg_plan.hip (ac_mv_avg: the call plan)
     "ACDSP_NO_SAT_FREE": [leg({"ACDSP_NO_SAT_FREE": "1"}, ["satfree"],
                               {"satfree:fir.kernel": "satacc16", "satfree:polydec.path": "generic", "satfree:intg.path": "exact_order", "satfree:mvavg.path": "exact_order"},
                               {"satfree:fir.kernel": "mfma_i8", "satfree:polydec.path": "mfma_gen", "satfree:intg.path": "stream", "satfree:mvavg.path": "stream32"})],

@@ -10,12 +10,12 @@ import ac_dsp_amd as A
 F = A.Fmt
 
 
-def _buf(fmt, rows, n):
-    """rows x n samples, 16-byte aligned rows (stride rounded up to 64 samples), small deterministic values"""
+def _buf(fmt, rows, n, dtype=None):
+    """rows x n samples, 16-byte aligned rows (stride rounded up to 64 samples), small deterministic values; dtype: the handle's, on 1-byte rows"""
     stride = (n + 63) // 64 * 64
     x = torch.zeros((rows, stride), dtype=A.torch_dtype_for(fmt), device="cuda")
     A.fill_stimulus(x, 7, min(fmt.W, 12))
-    return x[:, :n]
+    return (x.to(dtype) if dtype is not None and dtype != x.dtype else x)[:, :n]
 
 
 CIC_IN = {"s16": F(16, 1), "s32": F(32, 16), "u12": F(12, 4, False), "s24": F(24, 8), "s40": F(40, 20)}
@@ -90,17 +90,28 @@ def mvavg_grid():
                         continue
                     for oname, fo in (("o16", F(16, 8, True, "RND", "SAT")), ("o_acc", F(fa.W, fa.I))):
                         yield "mvavg|%s|T%d|%s|ns%d|%s" % (tname, taps, mode, ns, oname), (fin, fc, fa, fo, taps, mode, ns)
+    # the three paths no row above reaches: the exact-order kernel (FORCE_GENERIC), and on 1-byte rows the byte kernel (frames of whole
+    # 16-sample groups) and the int64 sums (frames of 24 samples: outside the byte kernel's shape)
+    fin, fc, fa = MV_TYPES["i16"]
+    o16 = F(16, 8, True, "RND", "SAT")
+    for mode in ("MIRROR", "WIN", "CLIP"):
+        yield "mvavg|i16|T9|%s|ns1024|o16|force_generic" % mode, (fin, fc, fa, o16, 9, mode, 1024, {"force_generic": True})
+        for taps in (9, 33):
+            for ns in (24, 1024):
+                if ns >= taps:
+                    yield "mvavg|s8|T%d|%s|ns%d|o16|in_bytes" % (taps, mode, ns), (F(8, 4), fc, fa, o16, taps, mode, ns, {"in_bytes": True})
 
 
 def mvavg_resolve(args):
-    fin, fc, fa, fo, taps, mode, ns = args
+    fin, fc, fa, fo, taps, mode, ns = args[:7]
+    kw = args[7] if len(args) > 7 else {}
     try:
-        eng = A.MvAvg(4096, taps, mode, fin, fc, fa, fo, n_objects=2)
+        eng = A.MvAvg(4096, taps, mode, fin, fc, fa, fo, n_objects=2, **kw)
         w = np.hanning(taps + 2)[1:-1]
         eng.set_coeffs(np.round(w / w.sum() * 2.0 ** (fc.W - fc.I)).astype(np.int64))
     except A.AcdspError:
         return "rejected"
-    eng.run(_buf(fin, 2, 8 * ns), ns)
+    eng.run(_buf(fin, 2, 8 * ns, eng.in_dtype), ns)
     return eng.path
 
 

@@ -334,6 +334,35 @@ def test_clone_of_a_flagged_handle():
     same(words(y), oracle(33, "CLIP", fin, acc_for(fin), fo).run(c, x, n))
 
 
+@pytest.mark.parametrize("fin,in_bytes,paths", [(F(16, 8), False, ["stream", "stream32", "stream"]), (F(8, 4), True, ["stream_s8", "int64_sums", "stream_s8"])], ids=["int16", "bytes"])
+def test_a_new_coefficient_set_replans_a_live_handle(fin, in_bytes, paths):
+    """What a handle decides per coefficient set is rebuilt by every set_coeffs: a normalised window (sum |c| = 2^14: the streaming / byte kernel), then all
+    taps 8191 (sum |c| > 32767: off both, on to the 32-bit sliding window / the int64 sums), then the window again -- every run against the oracle, and a
+    clone taken under the second set decides as its source does."""
+    taps, n, n_obj = 9, 1024, 2
+    fc, fa, fo = F(16, 2), F(40, 18), F(16, 8, True, "RND", "SAT")
+    w = np.hanning(taps + 2)[1:-1]
+    set_a = np.round(w / w.sum() * 2.0 ** 14).astype(np.int64)
+    set_a[taps // 2] += 2 ** 14 - set_a.sum()
+    set_b = np.full(taps, 8191, dtype=np.int64)
+    x = rand_fmt(np.random.default_rng(41), fin, (n_obj, 2 * n))
+    orc = oracle(taps, "MIRROR", fin, fa, fo, n_obj=n_obj, fc=fc)
+    want = {"a": orc.run(set_a, x, n), "b": orc.run(set_b, x, n)}
+    eng = A.MvAvg(4096, taps, "MIRROR", fin, fc, fa, fo, n_objects=n_obj, in_bytes=in_bytes)
+    xd = to_dev(x, eng.in_dtype)
+    for k, (name, c) in enumerate((("a", set_a), ("b", set_b), ("a", set_a))):
+        eng.set_coeffs(c)
+        y = words(eng.run(xd, n))
+        assert eng.path == paths[k], (k, eng.path)
+        same(y, want[name], "set %s, run %d" % (name, k))
+        if k == 1:
+            twin = eng.clone()
+            assert twin.path == eng.path
+            same(words(twin.run(xd, n)), want["b"], "clone under set b")
+            assert twin.path == paths[1], twin.path
+            twin.close()
+
+
 @pytest.mark.parametrize("fin,fo", [(F(8, 4), F(8, 4, True, "RND", "SAT")), (F(8, 8, False), F(8, 8, False, "RND", "SAT"))], ids=["int8", "uint8"])
 def test_run_host_on_numpy_byte_rows(fin, fo):
     rng = np.random.default_rng(81)

@@ -62,3 +62,11 @@ def test_the_ops_grid_reaches_every_cic_family():
     assert {"recurrence", "mfma_gen", "two_stage", "wide"} <= {v for k, v in t.items() if k.startswith("cic|dec")}
     assert {"mfma_gen", "fir_identity", "wide"} <= {v for k, v in t.items() if k.startswith("cic|intr")}
     assert {"stream", "tile", "mfma"} <= {v for k, v in t.items() if k.startswith("intgdump")}
+
+
+def test_the_ops_grid_reaches_every_mvavg_path():
+    """all six names of MvAvg.path: the general kernels (exact order, int64 sums), the streaming kernel in both forms, the 32-bit
+    sliding window and the byte kernel"""
+    with open(TABLE_OPS) as f:
+        got = {v for k, v in json.load(f).items() if k.startswith("mvavg")}
+    assert got == {"exact_order", "int64_sums", "stream", "stream32", "stream_mfma", "stream_s8"}, got
